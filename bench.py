@@ -3,6 +3,7 @@
 (5-frame 384x288 HRNet-W48 clips, MI loss on, backbone unfrozen, Adam) on N MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     (+ one step's outputs as DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -276,6 +277,36 @@ def dcn_roofline(dev, B, dtype, reps=30, C=48, G=12, H=96, W=72):
     return fwd, bwd
 
 
+DUMP_SAMPLE = 1 << 20      # elements drawn from each parameter-sized arena (4 MB apiece in float32)
+
+
+def training_state(trainer):
+    """The tensors an optimisation step reads and updates: parameters, Adam state, module buffers (BatchNorm running
+    statistics and counters), the fp16 overflow guard -- the set Trainer._capture_plan rolls back after its warm-up."""
+    ts = [trainer.flat, trainer.opt.m, trainer.opt.v, trainer.opt.state] + list(trainer.model.buffers())
+    return ts + ([trainer.overflow] if trainer.overflow is not None else [])
+
+
+def dump_outputs(d, trainer, outs):
+    """--dump-outputs: what one step of the timed path handed its caller, as float32 .npy files under `d` -- the two
+    heatmap outputs and the MI terms step() returns, the loss parts and PCK rows the trainer keeps on the device, and a
+    fixed, seeded sample of the updated parameter arena and of the step's gradient arena (the whole arenas are 4 bytes
+    per parameter, 258 MB apiece at W48).  Files of two builds run with the same arguments compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    torch.cuda.synchronize()
+    n = trainer.flat.numel()
+    idx = torch.randint(0, n, (min(n, DUMP_SAMPLE),), generator=torch.Generator().manual_seed(0)).sort().values
+    arrays = {'final_hm': outs[0], 'kf_bb_hm': outs[1], 'loss_parts': trainer.loss_parts,
+              'params_sample': trainer.flat.detach().cpu()[idx], 'grad_sample': trainer.grad.cpu()[idx]}
+    if len(outs) > 2:
+        arrays['mi'] = torch.stack([o.reshape(()) for o in outs[2:]])
+    if trainer.acc is not None:
+        arrays['pck'] = trainer.acc
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def cpu_baseline_worker(args):
     """The oracle (CPU restatement of the reference path) timed on this box's host cores: ONE clip,
     forward + loss + backward + Adam, fp32.  Baseline only.  Runs in its own process (see cpu_baseline)."""
@@ -358,7 +389,13 @@ def main():
                          'loses more to thread hand-offs across the sockets than it gains')
     ap.add_argument('--deterministic', action='store_true', help='fixed-point DCN backward (bitwise reproducible steps)')
     ap.add_argument('--cpu-timeout', type=int, default=240)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, run the timed path once more from the seeded start state and write what '
+                         'that step computed as DIR/<name>.npy (float32): the same arguments give the same outputs to '
+                         'rounding (bit for bit with --deterministic)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.cpu_baseline_only:
         return cpu_baseline_worker(args)
     if args.also == 'none':
@@ -395,15 +432,20 @@ def main():
     use_graph = (not args.no_graph) and (world == 1 or os.environ.get('FAMI_DDP_GRAPH', '1') != '0')
     kf, sup, joints, vis = synth_batch(args.batch, args.sup, args.img_h, args.img_w, 17, dev, 19970808 + rank)
 
-    def make_trainer():
-        """-> (trainer, model, plan name, fallback notes).  N>1: the launch plans in order of preference -- segmented graphs
-        with overlapped all-reduce, serial graphs, eager hooks; a plan whose capture / first step fails on ANY rank is
-        dropped by all of them (agreed through a MIN all-reduce), so a scaling run reports a number and says which plan
-        produced it instead of dying in the capture."""
+    def start_state(trainer, keep):
+        # the seeded training state a freshly built Trainer holds (host copies; None unless outputs are dumped)
+        return [t.detach().cpu() for t in training_state(trainer)] if keep else None
+
+    def make_trainer(keep=False):
+        """-> (trainer, model, plan name, fallback notes, start_state(trainer, keep)).  N>1: the launch plans in order of
+        preference -- segmented graphs with overlapped all-reduce, serial graphs, eager hooks; a plan whose capture / first
+        step fails on ANY rank is dropped by all of them (agreed through a MIN all-reduce), so a scaling run reports a number
+        and says which plan produced it instead of dying in the capture."""
         if world == 1:
             model = build(args, dev)
-            return Trainer(model, lr=1e-3, use_mi=True, use_graph=use_graph, targets_from_joints=True,
-                           bucket_mb=args.bucket_mb), model, None, []
+            trainer = Trainer(model, lr=1e-3, use_mi=True, use_graph=use_graph, targets_from_joints=True,
+                              bucket_mb=args.bucket_mb)
+            return trainer, model, None, [], start_state(trainer, keep)
         first = os.environ.get('FAMI_DDP_PLAN', 'overlap')
         plans = ([(first, True)] + [(q, True) for q in ('overlap', 'serial') if q != first and first == 'overlap']
                  if use_graph else []) + [('eager-hooks', False)]
@@ -411,10 +453,11 @@ def main():
         for name, ug in plans:
             if ug:
                 os.environ['FAMI_DDP_PLAN'] = name
-            ok, trainer, model = 1, None, None
+            ok, trainer, model, start = 1, None, None, None
             try:
                 model = build(args, dev)
                 trainer = Trainer(model, lr=1e-3, use_mi=True, use_graph=ug, targets_from_joints=True, bucket_mb=args.bucket_mb)
+                start = start_state(trainer, keep)
                 trainer.step(kf, sup, joints, vis)
                 torch.cuda.synchronize(dev)
             except Exception as e:                       # noqa: BLE001 -- reported in the JSON line
@@ -423,16 +466,16 @@ def main():
             flag = torch.tensor([ok], device=dev, dtype=torch.int32)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             if int(flag.item()) == 1:
-                return trainer, model, name, notes
+                return trainer, model, name, notes, start
             if ok:
                 notes.append('%s dropped: failed on another rank' % name)
             del trainer, model
             torch.cuda.empty_cache()
         raise SystemExit('no data-parallel launch plan ran: ' + '; '.join(notes))
 
-    def timed_run(dtype, steps, warmup):
+    def timed_run(dtype, steps, warmup, dump=None):
         args.dtype = dtype
-        trainer, model, plan_name, plan_notes = make_trainer()
+        trainer, model, plan_name, plan_notes, start = make_trainer(keep=bool(dump))
         for _ in range(max(warmup, 1)):
             trainer.step(kf, sup, joints, vis)
         barrier()
@@ -473,13 +516,24 @@ def main():
             info.update({"allreduce_ms_expected_ring": round(2 * (world - 1) / world * wire / 153e9 * 1e3, 3),
                          "allreduce_ms_expected_mesh": round(2 * wire / world / 153e9 * 1e3, 3),
                          "allreduce_wire_bytes": int(wire)})
+        if dump:
+            # the dumped step: the timed path (same Trainer, same captured plan, same batch) once more, from the seeded state
+            # the Trainer was built with.  The last timed step itself starts from weights in which the earlier steps' atomic
+            # accumulations (float-atomic DCN input gradient, fp64 slot atomics) leave run-to-run differences in the last bits,
+            # and Adam amplifies them over the steps; from the seeded state two runs differ by one step's rounding at most.
+            for t, s in zip(training_state(trainer), start):
+                t.copy_(s)
+            outs = trainer.step(kf, sup, joints, vis)
+            barrier()
+            if rank == 0:
+                dump_outputs(dump, trainer, outs)
         del trainer, model
         gc.collect()                 # (the Trainer is a reference cycle: its hipGraph goes now, not inside the next capture)
         torch.cuda.empty_cache()
         return dt, loss, info
 
     primary = args.dtype
-    dt, loss, info = timed_run(primary, args.steps, args.warmup)
+    dt, loss, info = timed_run(primary, args.steps, args.warmup, dump=args.dump_outputs)
     other = None
     if args.also and args.also != primary and world == 1:      # the extra dtype line is a single-GPU report
         o_steps = max(3, min(args.steps, 20))
