@@ -8,9 +8,15 @@ File format of engine/defaults/checkpoints.py:45-67: ``epoch_{n}_state.pth`` hol
 state_dict (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``, parameters numbered in ``model.parameters()`` order
 restricted to ``requires_grad``, as posetimation/optimizer/optimizer.py:18-22,66-68 builds it).
 
-Limitation: the flat Adam is ONE parameter group.  The reference's optional second group (TRAIN.LR_SECOND_GROUP:
-a list of two Adams, optimizer.py:24-64) is not representable; `load_adam_state_dict` raises on a parameter-count
-mismatch instead of loading a partial state.
+SGD (train.FlatSGD, TRAIN.OPTIMIZER 'sgd') converts to and from a ``torch.optim.SGD`` state_dict: per-parameter
+``momentum_buffer`` once a step with momentum has run, no per-parameter state otherwise.  torch's SGD keeps no step
+count; a loaded buffer puts the flat SGD past its first step, so the next update takes the running momentum rule.
+
+Learning-rate groups (Trainer lr_groups, TRAIN.LR_SECOND_GROUP): the reference builds a list of two Adams
+(optimizer.py:18-55,69-72) and saves a list of two state dicts, each numbering only its own parameters; `resume`
+matches them to the optimizers by parameter count (checkpoints.py:85-99).  A Trainer with groups writes and reads
+exactly that list.  The single-group Adam format is the one `adam_state_dict` writes.  A state of the other optimizer
+kind, or a parameter count that matches no group, raises instead of loading a partial state.
 """
 import os
 import os.path as osp
@@ -82,13 +88,129 @@ def load_adam_state_dict(trainer, sd):
         opt.state.copy_(torch.tensor([t, g['lr'], 1.0 - opt.betas[0] ** t, 1.0 - opt.betas[1] ** t]))
 
 
+def _kind(sd):
+    g = sd['param_groups'][0]
+    return 'adam' if 'betas' in g else 'sgd' if 'momentum' in g else 'unknown'
+
+
+def _group_state_dict(opt, rows):
+    """One flat optimizer (a learning-rate group over the table rows `rows`) -> torch.optim.Adam / SGD.state_dict() of
+    a torch optimizer built on just those parameters."""
+    step = float(opt.state[0].item())
+    state = {}
+    if opt.kind == 'adam':
+        for i, (p, off, n) in enumerate(rows):
+            state[i] = {'step': torch.tensor(step), 'exp_avg': opt.m[off:off + n].view(p.shape).detach().cpu().clone(),
+                        'exp_avg_sq': opt.v[off:off + n].view(p.shape).detach().cpu().clone()}
+        group = {'lr': float(opt.state[1].item()), 'initial_lr': float(opt.initial_lr), 'betas': tuple(opt.betas),
+                 'eps': opt.eps, 'weight_decay': opt.wd, 'amsgrad': False, 'maximize': False, 'foreach': None,
+                 'capturable': False, 'differentiable': False, 'fused': None, 'params': list(range(len(rows)))}
+    else:
+        if opt.buf is not None and step >= 1:          # torch creates the buffers at the first step with momentum
+            for i, (p, off, n) in enumerate(rows):
+                state[i] = {'momentum_buffer': opt.buf[off:off + n].view(p.shape).detach().cpu().clone()}
+        group = {'lr': float(opt.state[1].item()), 'initial_lr': float(opt.initial_lr), 'momentum': opt.momentum,
+                 'dampening': opt.dampening, 'weight_decay': opt.wd, 'nesterov': opt.nesterov, 'maximize': False,
+                 'foreach': None, 'differentiable': False, 'fused': None, 'params': list(range(len(rows)))}
+    return {'state': state, 'param_groups': [group]}
+
+
+def _load_group(opt, rows, sd):
+    """torch.optim.Adam / SGD.state_dict() -> one flat optimizer over the table rows `rows` (arenas outside the rows,
+    which other groups may share, are left alone)."""
+    g = sd['param_groups'][0]
+    if _kind(sd) != opt.kind:
+        raise ValueError('optimizer state of kind %s cannot load into a %s optimizer' % (_kind(sd), opt.kind))
+    if len(g['params']) != len(rows):
+        raise ValueError('optimizer state has %d parameters, the group has %d trainable ones' % (len(g['params']), len(rows)))
+    with torch.no_grad():
+        if opt.kind == 'adam':
+            opt.set_hyper(betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay'])
+            steps = set()
+            for i, (p, off, n) in enumerate(rows):
+                st = sd['state'].get(i)
+                m, v = opt.m[off:off + n], opt.v[off:off + n]
+                if st is None:
+                    m.zero_()
+                    v.zero_()
+                    continue
+                m.copy_(st['exp_avg'].reshape(-1).to(m.device))
+                v.copy_(st['exp_avg_sq'].reshape(-1).to(v.device))
+                steps.add(float(st['step']))
+            if len(steps) > 1:
+                raise ValueError('per-parameter step counts differ; the flat Adam keeps one')
+            t = steps.pop() if steps else 0.0
+            vec = [t, g['lr'], 1.0 - opt.betas[0] ** t, 1.0 - opt.betas[1] ** t]
+        else:
+            # momentum and friends are kernel arguments: set_hyper bumps hyper_version (a graph-mode Trainer re-captures)
+            opt.set_hyper(momentum=g['momentum'], dampening=g['dampening'], weight_decay=g['weight_decay'],
+                          nesterov=g['nesterov'])
+            seen = False
+            for i, (p, off, n) in enumerate(rows):
+                st = sd['state'].get(i)
+                b = st.get('momentum_buffer') if st is not None else None
+                if opt.buf is None:
+                    continue
+                if b is None:
+                    opt.buf[off:off + n].zero_()
+                else:
+                    opt.buf[off:off + n].copy_(b.reshape(-1).to(opt.buf.device))
+                    seen = True
+            vec = [1.0 if seen else 0.0, g['lr'], 1.0]        # step >= 1: the next update takes the running rule
+        opt.lr = float(g['lr'])
+        opt.initial_lr = float(g.get('initial_lr', g['lr']))
+        opt.state.copy_(torch.tensor(vec))
+
+
+def _groups(trainer):
+    opts = getattr(trainer, 'optimizers', None) or [trainer.opt]
+    rows = getattr(trainer, 'group_rows', None) or [list(range(len(trainer.table)))]
+    return opts, [[trainer.table[i] for i in r] for r in rows]
+
+
+def optimizer_state_dicts(trainer):
+    """A Trainer's optimizer part of the checkpoint: [adam_state_dict] for the single-group Adam, else one torch state
+    dict per learning-rate group (the reference's list of optimizers, base group first)."""
+    opts, rows = _groups(trainer)
+    if len(opts) == 1 and opts[0].kind == 'adam':
+        return [adam_state_dict(trainer)]
+    return [_group_state_dict(o, r) for o, r in zip(opts, rows)]
+
+
+def load_optimizer_state_dicts(trainer, sds):
+    """The inverse of optimizer_state_dicts; consumes the dicts it loads from the list `sds`.  Several groups take their
+    dicts by parameter count, as the reference's resume does (checkpoints.py:85-99)."""
+    opts, rows = _groups(trainer)
+    if not sds:
+        raise ValueError('the checkpoint holds no optimizer state')
+    if len(opts) == 1:
+        sd = sds.pop(0)
+        if _kind(sd) != opts[0].kind:
+            raise ValueError('optimizer state of kind %s cannot load into a %s optimizer' % (_kind(sd), opts[0].kind))
+        if opts[0].kind == 'adam':
+            load_adam_state_dict(trainer, sd)
+        else:
+            _load_group(opts[0], rows[0], sd)
+        return
+    for k, (o, r) in enumerate(zip(opts, rows)):
+        match = next((sd for sd in sds if len(sd['param_groups'][0]['params']) == len(r)), None)
+        if match is None:
+            raise ValueError('no optimizer state in the checkpoint has the %d parameters of learning-rate group %d' %
+                             (len(r), k))
+        _load_group(o, r, match)
+        sds.remove(match)
+
+
 def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
-    """`optimizer`: a train.Trainer (flat Adam) or any torch optimizer / list of them (reference signature)."""
+    """`optimizer`: a train.Trainer (flat Adam / SGD, one state dict per learning-rate group) or any torch optimizer /
+    list of them (reference signature)."""
     os.makedirs(save_folder, exist_ok=True)
     path = osp.join(save_folder, 'epoch_{}_state.pth'.format(epoch))
     sd = {k: v.detach().cpu() for k, v in _strip_module(model.state_dict()).items()}
     opts = optimizer if isinstance(optimizer, list) else [optimizer]
-    osd = [adam_state_dict(o) if hasattr(o, 'table') else o.state_dict() for o in opts]
+    osd = []
+    for o in opts:
+        osd.extend(optimizer_state_dicts(o) if hasattr(o, 'table') else [o.state_dict()])
     torch.save({'begin_epoch': epoch, 'state_dict': sd, 'optimizer': osd}, path)
     return path
 
@@ -107,9 +229,12 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
         for k, v in sd.items():          # in place: parameters may be views into the trainer's flat arena
             own[k].copy_(v.to(own[k].device))
     opts = optimizer if isinstance(optimizer, list) else [optimizer]
-    for o, osd in zip(opts, ckpt['optimizer']):
+    osds = list(ckpt['optimizer'])
+    for o in opts:
+        if not osds:
+            break
         if hasattr(o, 'table'):
-            load_adam_state_dict(o, osd)
+            load_optimizer_state_dicts(o, osds)
         else:
-            o.load_state_dict(osd)
+            o.load_state_dict(osds.pop(0))
     return model, optimizer, begin_epoch

@@ -9,6 +9,9 @@ zero_grad / backward / Adam step) -- the reference loop itself is not importable
   (one allocation each); nn.Parameter objects are views, so state_dict() is
   unchanged.  Adam is ONE kernel over the arena; the data-parallel all-reduce
   needs no flatten/unflatten copies: a bucket is a slice of the gradient arena.
+  TRAIN.OPTIMIZER 'sgd' is ONE fused SGD kernel the same way (FlatSGD).  A second
+  learning-rate group (TRAIN.LR_SECOND_GROUP) keeps the one arena: each group
+  updates its own contiguous arena runs with its own device state vector.
 * one process per GPU; gradients are averaged with RCCL all-reduce over xGMI,
   bucket by bucket, each bucket launched as soon as the backward tape has
   enqueued the last contribution to it (reverse registration order: the head
@@ -36,13 +39,22 @@ class FlatAdam:
     (posetimation/optimizer/optimizer.py:66-68 builds the reference's).  The step count, the learning rate and the two
     bias corrections live in a device vector, so an LR schedule needs no re-capture of a hipGraph; betas / eps /
     weight decay are kernel arguments: changing them (set_hyper, or loading a checkpoint) bumps `hyper_version`,
-    which makes a graph-mode Trainer re-capture."""
+    which makes a graph-mode Trainer re-capture.
 
-    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    runs: the arena ranges [(lo, hi)] this optimizer updates (None: the whole arena) -- one learning-rate group of a
+    Trainer (parameter_groups).  share: another group's optimizer whose gradient and moment arenas this one uses."""
+
+    kind = 'adam'
+
+    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, runs=None, share=None):
         self.p = flat_param
-        self.grad = torch.zeros_like(flat_param)
-        self.m = torch.zeros_like(flat_param)
-        self.v = torch.zeros_like(flat_param)
+        if share is None:
+            self.grad = torch.zeros_like(flat_param)
+            self.m = torch.zeros_like(flat_param)
+            self.v = torch.zeros_like(flat_param)
+        else:
+            self.grad, self.m, self.v = share.grad, share.m, share.v
+        self.runs = [(0, flat_param.numel())] if runs is None else [(int(a), int(b)) for a, b in runs]
         self.betas, self.eps, self.wd = tuple(betas), eps, weight_decay
         self.lr = float(lr)
         # the undecayed rate an LR schedule scales (torch stores it as param_groups[0]['initial_lr'] the first time a
@@ -50,6 +62,10 @@ class FlatAdam:
         self.initial_lr = float(lr)
         self.hyper_version = 0
         self.state = torch.tensor([0.0, lr, 1.0, 1.0], device=flat_param.device)   # step, lr, bc1, bc2
+
+    def tensors(self):
+        """the device state a step mutates besides the parameters (a graph capture's warm-up restores it)"""
+        return [self.m, self.v, self.state]
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -69,25 +85,118 @@ class FlatAdam:
             lib().call('fami_adam_prep_f32', _p(self.state), self.betas[0], self.betas[1], s)
         else:
             lib().call('fami_adam_prep_checked_f32', _p(self.state), self.betas[0], self.betas[1], _p(flag), s)
-        lib().call('fami_adam_f32', _p(self.p), _p(self.grad), _p(self.m), _p(self.v), self.p.numel(), _p(self.state),
-                   self.betas[0], self.betas[1], self.eps, self.wd, s)
+        for lo, hi in self.runs:
+            self._launch(lo, hi, s)
 
     def prep(self, s=None):
         """the step's scalars alone (step count, bias corrections): a step split into ranges prepares once, up front"""
         lib().call('fami_adam_prep_f32', _p(self.state), self.betas[0], self.betas[1], _stream(self.p.device) if s is None else s)
 
     def apply(self, lo, hi, s=None):
-        """the update of arena[lo:hi] with the prepared scalars"""
-        if hi > lo:
-            lib().call('fami_adam_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]), hi - lo,
-                       _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, _stream(self.p.device) if s is None else s)
+        """the update of arena[lo:hi] (restricted to this optimizer's runs) with the prepared scalars"""
+        s = _stream(self.p.device) if s is None else s
+        for a, b in _clip(self.runs, lo, hi):
+            self._launch(a, b, s)
+
+    def _launch(self, lo, hi, s):
+        lib().call('fami_adam_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]), hi - lo,
+                   _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, s)
+
+
+class FlatSGD:
+    """torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) on one flat fp32 arena: TRAIN.OPTIMIZER 'sgd'
+    (posetimation/optimizer/optimizer.py:58-64; MOMENTUM 0.9 / WD 1e-4 / NESTEROV False in posetimation/config/
+    defaults.py:137-140).  The protocol of FlatAdam: the step count (it selects the momentum buffer's first-step rule),
+    the learning rate and the skip decision of the checked step live in a device vector; momentum / dampening / weight
+    decay / nesterov are kernel arguments (set_hyper bumps `hyper_version`).  The momentum buffer exists only with a
+    momentum, as torch's does."""
+
+    kind = 'sgd'
+
+    def __init__(self, flat_param, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, runs=None,
+                 share=None):
+        _check_sgd(lr, momentum, dampening, weight_decay, nesterov)
+        self.p = flat_param
+        self.grad = torch.zeros_like(flat_param) if share is None else share.grad
+        self.momentum, self.dampening, self.wd, self.nesterov = float(momentum), float(dampening), float(weight_decay), bool(nesterov)
+        self.buf = None
+        if self.momentum != 0.0:
+            self.buf = share.buf if share is not None and share.buf is not None else torch.zeros_like(flat_param)
+        self.runs = [(0, flat_param.numel())] if runs is None else [(int(a), int(b)) for a, b in runs]
+        self.lr = float(lr)
+        self.initial_lr = float(lr)
+        self.hyper_version = 0
+        self.state = torch.tensor([0.0, lr, 1.0], device=flat_param.device)        # step, lr, apply
+
+    def tensors(self):
+        return ([] if self.buf is None else [self.buf]) + [self.state]
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self.state[1] = self.lr
+
+    def set_hyper(self, momentum=None, dampening=None, weight_decay=None, nesterov=None):
+        new = (self.momentum if momentum is None else float(momentum), self.dampening if dampening is None else float(dampening),
+               self.wd if weight_decay is None else float(weight_decay), self.nesterov if nesterov is None else bool(nesterov))
+        if new != (self.momentum, self.dampening, self.wd, self.nesterov):
+            _check_sgd(self.lr, *new)
+            self.momentum, self.dampening, self.wd, self.nesterov = new
+            if self.momentum != 0.0 and self.buf is None:
+                self.buf = torch.zeros_like(self.p)
+            self.hyper_version += 1
+
+    def step(self, flag=None):
+        """flag: device u32 raised by fami_unscale_check_f32 on non-finite gradients -> the step is skipped."""
+        s = _stream(self.p.device)
+        if flag is None:
+            lib().call('fami_sgd_prep_f32', _p(self.state), s)
+        else:
+            lib().call('fami_sgd_prep_checked_f32', _p(self.state), _p(flag), s)
+        for lo, hi in self.runs:
+            self._launch(lo, hi, s)
+
+    def prep(self, s=None):
+        lib().call('fami_sgd_prep_f32', _p(self.state), _stream(self.p.device) if s is None else s)
+
+    def apply(self, lo, hi, s=None):
+        s = _stream(self.p.device) if s is None else s
+        for a, b in _clip(self.runs, lo, hi):
+            self._launch(a, b, s)
+
+    def _launch(self, lo, hi, s):
+        buf = None if self.momentum == 0.0 else _p(self.buf[lo:hi])
+        lib().call('fami_sgd_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), buf, hi - lo, _p(self.state), self.momentum,
+                   self.dampening, self.wd, int(self.nesterov), s)
+
+
+def _check_sgd(lr, momentum, dampening, weight_decay, nesterov):
+    """torch.optim.SGD.__init__'s argument checks"""
+    if lr < 0.0:
+        raise ValueError('Invalid learning rate: {}'.format(lr))
+    if momentum < 0.0:
+        raise ValueError('Invalid momentum value: {}'.format(momentum))
+    if weight_decay < 0.0:
+        raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
+    if nesterov and (momentum <= 0 or dampening != 0):
+        raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+
+
+def _clip(runs, lo, hi):
+    """the non-empty pieces of [lo, hi) inside the runs"""
+    out = []
+    for a, b in runs:
+        a, b = max(a, lo), min(b, hi)
+        if b > a:
+            out.append((a, b))
+    return out
 
 
 class MultiStepLR:
     """torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones, gamma, last_epoch) for the flat Adam: what
     posetimation/optimizer/scheduler.py:14-35 builds from TRAIN.LR_STEP / TRAIN.LR_FACTOR ([8, 12, 16] x 0.1 in
-    configs/Alignment/Base_PoseTrack17.yaml) and engine/defaults/trainer.py steps once per epoch.  `opt` is a FlatAdam
-    or a Trainer; the new rate is written into the optimizer's device-resident state, so captured graphs keep replaying."""
+    configs/Alignment/Base_PoseTrack17.yaml) and engine/defaults/trainer.py steps once per epoch.  `opt` is a FlatAdam /
+    FlatSGD (one learning-rate group: an entry of Trainer.optimizers) or a Trainer (its base group); the new rate is
+    written into the optimizer's device-resident state, so captured graphs keep replaying."""
 
     def __init__(self, opt, milestones, gamma=0.1, last_epoch=-1, base_lr=None):
         import bisect
@@ -153,6 +262,102 @@ def flatten_parameters(model):
         off += n
     # the table stays in model.parameters() order: torch.optim.Adam numbers its state that way (checkpoint.py)
     return flat, [(p, where[id(p)], p.numel()) for p in ps]
+
+
+def parameter_groups(model, lr_groups=None):
+    """-> [[(name, param)], ...]: the base learning-rate group, then one group per `lr_groups` entry (name_prefixes, lr):
+    the trainable parameters whose names start with one of its prefixes (the first matching entry wins).  That is
+    posetimation/optimizer/optimizer.py:18-55 for TRAIN.LR_SECOND_GROUP: `name.startswith` over model.named_parameters(),
+    frozen parameters in no group, each group in model.parameters() order."""
+    lr_groups = list(lr_groups or ())
+    prefixes = [(p,) if isinstance(p, str) else tuple(p) for p, _ in lr_groups]
+    groups = [[] for _ in range(1 + len(lr_groups))]
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        k = next((j + 1 for j, pre in enumerate(prefixes) if name.startswith(pre)), 0)
+        groups[k].append((name, p))
+    return groups
+
+
+def _runs(spans):
+    """[(off, n)] -> the sorted, merged arena ranges [(lo, hi)] they cover"""
+    out = []
+    for off, n in sorted(spans):
+        if out and out[-1][1] == off:
+            out[-1] = (out[-1][0], off + n)
+        else:
+            out.append((off, off + n))
+    return out
+
+
+def build_optimizers(model, flat, table, optimizer='adam', lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                     nesterov=False, lr_groups=None):
+    """The flat optimizer(s) of a Trainer -> (optimizers, rows): one FlatAdam / FlatSGD per learning-rate group
+    (parameter_groups), the base group first; rows[k] = the indices into `table` of group k's parameters.  Without
+    lr_groups: ONE optimizer over the whole arena, exactly the launches of a plain FlatAdam / FlatSGD.  With them, every
+    group updates only its own arena runs, keeps its own device state vector (rate, step count) and shares the
+    gradient and moment arenas of the base group."""
+    if optimizer == 'adam':
+        if momentum or dampening or nesterov:
+            raise ValueError('momentum / dampening / nesterov are arguments of the sgd optimizer, not of adam')
+
+        def make(rate, runs, share):
+            return FlatAdam(flat, lr=rate, weight_decay=weight_decay, runs=runs, share=share)
+    elif optimizer == 'sgd':
+        def make(rate, runs, share):
+            return FlatSGD(flat, lr=rate, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                           nesterov=nesterov, runs=runs, share=share)
+    else:
+        raise ValueError("optimizer must be 'adam' or 'sgd', not %r" % (optimizer,))
+    if not lr_groups:
+        return [make(lr, None, None)], [list(range(len(table)))]
+    index = {id(p): i for i, (p, _, _) in enumerate(table)}
+    rates = [lr] + [float(r) for _, r in lr_groups]
+    opts, rows = [], []
+    for k, (members, rate) in enumerate(zip(parameter_groups(model, lr_groups), rates)):
+        if not members:
+            # (torch.optim raises on an empty parameter list too)
+            raise ValueError('learning-rate group %d (%s) has no trainable parameter' %
+                             (k, 'base' if k == 0 else lr_groups[k - 1][0]))
+        idx = [index[id(p)] for _, p in members]
+        opts.append(make(rate, _runs([table[i][1:] for i in idx]), opts[0] if opts else None))
+        rows.append(idx)
+    return opts, rows
+
+
+def optimizer_kwargs(cfg):
+    """The Trainer's optimizer arguments from a reference config: posetimation/optimizer/optimizer.py:16-76 reads
+    TRAIN.OPTIMIZER / LR / MOMENTUM / WD / NESTEROV / LR_SECOND_GROUP / LR_SECOND_GROUP_VALUE (defaults
+    posetimation/config/defaults.py:137-140 and mppe_config.py:306-307).  Its Adam is built from `lr` alone
+    (optimizer.py:68,72), so TRAIN.WD reaches SGD only."""
+    t = cfg['TRAIN']
+    kind = t.get('OPTIMIZER', 'adam')
+    lr = float(t.get('LR', 0.001))
+    second = list(t.get('LR_SECOND_GROUP', None) or [None])
+    groups = None if second[0] is None else [(tuple(second), float(t.get('LR_SECOND_GROUP_VALUE', 1e-6)))]
+    if kind == 'sgd':
+        if groups:
+            raise ValueError("TRAIN.OPTIMIZER 'sgd' with TRAIN.LR_SECOND_GROUP cannot be built: the reference hands "
+                             "torch.optim.SGD a list of parameter-group lists (optimizer.py:50-53,58-59), which torch "
+                             "rejects with a TypeError")
+        return {'optimizer': 'sgd', 'lr': lr, 'momentum': float(t.get('MOMENTUM', 0.9)),
+                'weight_decay': float(t.get('WD', 1e-4)), 'nesterov': bool(t.get('NESTEROV', False))}
+    if kind == 'adam':
+        return {'optimizer': 'adam', 'lr': lr, 'lr_groups': groups}
+    raise ValueError("TRAIN.OPTIMIZER must be 'adam' or 'sgd', not %r" % (kind,))
+
+
+def build_lr_scheduler(cfg, trainer, last_epoch=-1):
+    """posetimation/optimizer/scheduler.py:14-27: TRAIN.LR_SCHEDULER 'MultiStepLR' over TRAIN.LR_STEP / LR_FACTOR -- one
+    MultiStepLR for one learning-rate group, a list of them (one per group, each decaying its own rate) otherwise."""
+    t = cfg['TRAIN']
+    if t.get('LR_SCHEDULER', 'MultiStepLR') != 'MultiStepLR':
+        raise ValueError('TRAIN.LR_SCHEDULER must be MultiStepLR, not %r' % (t.get('LR_SCHEDULER'),))
+    steps, factor = t.get('LR_STEP', [90, 110]), float(t.get('LR_FACTOR', 0.1))
+    opts = getattr(trainer, 'optimizers', None) or [trainer]
+    out = [MultiStepLR(o, steps, factor, last_epoch=last_epoch) for o in opts]
+    return out[0] if len(out) == 1 else out
 
 
 class WeightPacker:
@@ -369,7 +574,12 @@ class Trainer:
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
-                 loss_scale=None, pck=True, data_parallel=None):
+                 loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
+                 weight_decay=0.0, nesterov=False, lr_groups=None):
+        """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
+        weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
+        (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
+        from a reference config."""
         self.model = model
         self.route = getattr(model, 'route', None)      # kernel-routing state (None: process default), as the model's engines
         self.targets_from_joints, self.sigma = targets_from_joints, sigma
@@ -383,7 +593,15 @@ class Trainer:
         self.flat, self.table = flatten_parameters(model)
         # overflow guard of the static loss scale: a device flag raised by the unscale pass, consumed by the optimizer
         self.overflow = torch.zeros(2, dtype=torch.int32, device=self.dev) if self.loss_scale != 1.0 else None   # {raised, skipped steps}
-        self.opt = FlatAdam(self.flat, lr=lr)
+        # one flat optimizer per learning-rate group; `opt` is the base group's (the only one without lr_groups)
+        self.optimizers, self.group_rows = build_optimizers(
+            model, self.flat, self.table, optimizer=optimizer, lr=lr, momentum=momentum, dampening=dampening,
+            weight_decay=weight_decay, nesterov=nesterov, lr_groups=lr_groups)
+        self.opt = self.optimizers[0]
+        # the checked step of several groups: each further group reads a copy of the overflow flag, the base group
+        # (stepped last) reads, clears and counts the flag itself
+        self._group_flags = (torch.zeros(len(self.optimizers) - 1, 2, dtype=torch.int32, device=self.dev)
+                             if self.overflow is not None and len(self.optimizers) > 1 else None)
         self.grad = self.opt.grad
         self._adam_split = self._find_adam_split(model)
         self._adam_done = False
@@ -438,6 +656,14 @@ class Trainer:
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
             self.broadcast_parameters()
+
+    @classmethod
+    def from_cfg(cls, cfg, model, **trainer_kw):
+        """A Trainer with the optimizer the reference's build_optimizer makes of `cfg` (optimizer_kwargs); `trainer_kw`
+        takes the other Trainer arguments and wins over the config."""
+        kw = optimizer_kwargs(cfg)
+        kw.update(trainer_kw)
+        return cls(model, **kw)
 
     def _lc(self, name, *args):
         """a library entry point under this trainer's route (weight packs and plans must see what its engines see)"""
@@ -506,7 +732,8 @@ class Trainer:
         if split is not None:
             # Adam in two parts (see _find_adam_split): the scalars now, everything but the stem stretch when backward reaches the
             # stage-2 boundary (side lane), the stem stretch behind the backward pass
-            self.opt.prep(eng.stream)
+            for o in self.optimizers:
+                o.prep(eng.stream)
 
             def on_mark(name):
                 if name == 'stage2' and early['ev'] is None:
@@ -515,8 +742,9 @@ class Trainer:
                     n = self.flat.numel()
 
                     def upd(st):
-                        self.opt.apply(0, split[0], st)
-                        self.opt.apply(split[1], n, st)
+                        for o in self.optimizers:
+                            o.apply(0, split[0], st)
+                            o.apply(split[1], n, st)
                     early['ev'] = eng.side_launch(upd)
             eng.on_mark = on_mark
         # conv weight images of this step: the forward orientation in one launch now, the input-gradient orientation in a
@@ -625,11 +853,13 @@ class Trainer:
             eng.wait_main(packed_bwd)
         eng.backward(on_params_done=hook)
         if split is not None:
+            for o in self.optimizers:
+                if early['ev'] is not None:
+                    o.apply(split[0], split[1], eng.stream)
+                else:
+                    o.apply(0, self.flat.numel(), eng.stream)
             if early['ev'] is not None:
-                self.opt.apply(split[0], split[1], eng.stream)
                 eng.wait_main(early['ev'])
-            else:
-                self.opt.apply(0, self.flat.numel(), eng.stream)
             self._adam_done = True
         self.conv_flops = eng.conv_flops        # nn.Conv2d FLOPs of one step (forward + both gradients; reporting)
         if on_bucket is not None:
@@ -671,7 +901,30 @@ class Trainer:
             self._adam_done = False
             return
         self._unscale()
+        self._step_optimizers()
+
+    def _step_optimizers(self):
+        """every group's step (prep + its runs); one group: exactly FlatAdam.step / FlatSGD.step"""
+        for k, o in enumerate(self.optimizers[1:]):
+            flag = None
+            if self._group_flags is not None:
+                flag = self._group_flags[k]
+                flag[0].copy_(self.overflow[0])
+            o.step(flag)
         self.opt.step(self.overflow)
+
+    def _opt_tensors(self):
+        """the parameter arena and every optimizer's device state (shared arenas once)"""
+        out, seen = [self.flat], set()
+        for o in self.optimizers:
+            for t in o.tensors():
+                if id(t) not in seen:
+                    seen.add(id(t))
+                    out.append(t)
+        return out
+
+    def _hyper_version(self):
+        return tuple(o.hyper_version for o in self.optimizers)
 
     def _unscale(self):
         """gradient arena *= 1 / (world * loss_scale): the data-parallel mean and the static loss scale in one pass."""
@@ -712,7 +965,7 @@ class Trainer:
         # warm-up on a side stream (allocator + pack caches).  The warm-up steps must not count as training steps: the
         # parameters, Adam state and module buffers (BN running statistics, batch counters) are restored afterwards, so
         # the first step() of a graph-mode Trainer is exactly one optimisation step, like the eager one.
-        snap = [t.clone() for t in (self.flat, self.opt.m, self.opt.v, self.opt.state)]
+        snap = [t.clone() for t in self._opt_tensors()]
         ovf = None if self.overflow is None else self.overflow.clone()     # {raised, skipped steps}: warm-up steps do not count
         bufs = [(b, b.clone()) for b in self.model.buffers()]
         side = torch.cuda.Stream(self.dev)
@@ -722,7 +975,7 @@ class Trainer:
                 self._eager_step(st['kf'], st['sup'], st['target'], st['weight'])
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
-        for dst, src in zip((self.flat, self.opt.m, self.opt.v, self.opt.state), snap):
+        for dst, src in zip(self._opt_tensors(), snap):
             dst.copy_(src)
         for b, src in bufs:
             b.copy_(src)
@@ -751,11 +1004,11 @@ class Trainer:
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, pool=pool, capture_error_mode='thread_local'):
                 self._unscale()
-                self.opt.step(self.overflow)
+                self._step_optimizers()
             plan.append(('graph', g2))
         else:
             outs, plan = self._capture_overlap(st)
-        entry = (plan, st, outs, self.opt.hyper_version)
+        entry = (plan, st, outs, self._hyper_version())
         return entry
 
     def _capture_overlap(self, st):
@@ -802,7 +1055,7 @@ class Trainer:
             g2.capture_begin(pool=pool, capture_error_mode='thread_local')
             try:
                 self._unscale()
-                self.opt.step(self.overflow)
+                self._step_optimizers()
             finally:
                 g2.capture_end()
             plan.append(('graph', g2))
@@ -823,7 +1076,7 @@ class Trainer:
             return self._eager_step(kf_x, sup_x, target, weight)
         key = (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape))
         entry = self._cache.get(key)
-        if entry is None or entry[3] != self.opt.hyper_version:
+        if entry is None or entry[3] != self._hyper_version():
             entry = self._cache[key] = self._capture(kf_x, sup_x, target, weight)
         plan, st, outs, _ = entry
         st['kf'].copy_(kf_x, non_blocking=True)

@@ -284,6 +284,14 @@ int fami_adam_f32(float* p, const float* g, float* m, float* v, long n, const fl
  * counts the skip: flag is a device u32[2] = {raised, skipped steps so far}. */
 int fami_unscale_check_f32(float* g, long n, float f, unsigned* flag, fami_stream_t stream);
 int fami_adam_prep_checked_f32(float* state4, float beta1, float beta2, unsigned* flag, fami_stream_t stream);
+/* torch.optim.SGD (posetimation/optimizer/optimizer.py:58-64) over a flat fp32 arena.  state3 (device float[3]) =
+ * {step, lr, apply}: prep increments step; the checked prep skips the step like fami_adam_prep_checked_f32 (apply = 0).
+ * d = g + wd p; with momentum: buf = d on step 1, else momentum buf + (1 - dampening) d; d = nesterov ? d + momentum buf
+ * : buf; p -= lr d.  buf may be NULL when momentum == 0.  Any 4-byte aligned sub-range of an arena is accepted. */
+int fami_sgd_prep_f32(float* state3, fami_stream_t stream);
+int fami_sgd_prep_checked_f32(float* state3, unsigned* flag, fami_stream_t stream);
+int fami_sgd_f32(float* p, const float* g, float* buf, long n, const float* state3, float momentum, float dampening,
+                 float weight_decay, int nesterov, fami_stream_t stream);
 
 /* ---- temporal alignment ----------------------------------------------------------------------
  * fami_shift_bilinear_*: kornia.geometry.warp_affine(src, [[1,0,tx],[0,1,ty]], dsize) at
