@@ -161,48 +161,34 @@ class Engine:
         self._merge = []               # [(id(param), private buffer)] folded into the owner's buffer at the join
         self.defer_bn = None           # list while BatchNorm running-stat updates are deferred (shared modules on lanes)
         self._side_events = []         # side_launch events lane 0 has not waited for yet (join_side)
-        # weight-gradient lane (opt-in, FAMI_WGRAD_LANE=1): conv wgrad kernels are leaves of the backward graph, so they
-        # can run on their own stream beside the dgrad -> BN chain.  Measured on MI355X: no gain (f32 75.5 vs 75.5 ms,
-        # bf16 45.9 vs 44.6 ms per step) -- every kernel already fills the chip -- hence off by default.
-        self.regressor_lanes = options.flag('FAMI_REGRESSOR_LANES', '1')   # shared-weight regressors on lanes
-        self.mi_lanes = self.use_lanes and options.flag('FAMI_MI_LANES', '1')   # the six MI terms of the loss on three lanes
-        self.fuse_lanes = options.flag('FAMI_FUSE_LANES', '1')   # fuse terms on the lane of their source branch
         # lanes stay forked across the modules of an HRNet stage (modules.HRNetBody.run): a module's fuse sum i runs on lane i behind
         # events of the other lanes instead of on lane 0 behind a join.  The Trainer switches it off when gradient buckets are
         # all-reduced during backward (their hooks fire between forked regions).
-        self.persist_lanes = options.flag('FAMI_PERSIST_LANES', '1')
-        self.use_wlane = options.number('FAMI_WGRAD_LANE', '0') if self.use_lanes else 0      # 1: every weight gradient on the weight-gradient streams in turn, 2: the stage convolutions' on one stream per lane
-        self.wlane_scope_now = False
+        self.persist_lanes = True
+        # weight-gradient streams: weight gradients are leaves of the backward graph, so inside a `wlane_scope` they run on streams of
+        # their own beside the input-gradient chain.  That pays only where the step is ONE serial chain of kernels: the head (between
+        # the first DCN forward and the last DCN backward, 3.5 ms with exactly one kernel in flight in the rocprof trace; the model body
+        # brackets it) and the stem / layer1 / transitions, which run before the branches fork (HRNetBody.run; round 5: f32
+        # 45.68 -> 45.43 and 45.31 -> 45.17 ms, on in every mode).  For the stage convolutions, beside the other lanes, every such
+        # placement measured slower (docs/HISTORY.md, round-5 log: a leaf in front of a chain kernel delays the chain).
+        self.head_wlane = self.use_lanes
+        self.wlane_scope = False
+        self.wlane_pair = False        # inside the stem stretch's scope (HRNetBody.run)
+        # four streams each, taken in turn: launches on one capture stream are ordered among themselves in the graph although they
+        # are independent leaves (stem / head streams 1 / 1 ... 8 / 8: docs/HISTORY.md, round-5 log, "Weight-gradient streams")
+        self.stem_wlanes = 4
+        self.head_wlanes = 4
         self._wstreams = []        # weight-gradient streams of this step (the first is shared with the head's scope)
         self._wowner = {}          # parameter id -> index of the weight-gradient stream its gradients go to
         self._wflip = 0
-        self.wlane_pair = False
-        # round 4: two streams measured neutral (bf16 23.00 vs 23.01 ms, f32 47.47 vs 47.38); end of round 5 (tools/ab_env.py, two boxes):
-        # f32 45.26 -> 44.96 and 44.72 -> 44.46 ms, bf16 20.15 -> 20.08 and 20.05 -> 19.96 with two; then stem / head streams 2 / 1, 2 / 2,
-        # 4 / 2, 4 / 4, 8 / 8: bf16 19.28 / 19.18 / 19.12 / 19.05 / 19.07 (second run), f32 44.87 / 44.41 / 44.40 / 44.19 / 44.38 -- launches
-        # on one capture stream are ordered among themselves in the graph although they are independent leaves: four each
-        self.stem_wlanes = options.number('FAMI_STEM_WGRAD_LANES', '4')
         self._wdirty = False
-        # ... but for the HEAD it pays (FAMI_HEAD_WGRAD_LANE, default 1): between the first DCN forward and the last DCN backward
-        # the step is one serial chain of kernels (rocprof trace: 3.5 ms with exactly one kernel in flight), and the weight
-        # gradients in it are leaves.  A model body brackets that part with wlane_scope = True.
-        self.head_wlane = self.use_lanes and options.flag('FAMI_HEAD_WGRAD_LANE', '1')
-        self.head_wlanes = options.number('FAMI_HEAD_WGRAD_LANES', '4')       # number of weight-gradient streams of the head's scope
-        self.wlane_scope = False
-        # the same for the backbone's serial head and tail: stem, layer1 and the transitions run before the branches fork
-        # (their backward after the branches have joined), FAMI_STEM_WGRAD_LANE
-        # round 3: measured neutral (f32 49.1 -> 49.3, bf16 26.6 -> 26.5 ms).  Round 4, interleaved graph replays on one box
-        # (tools/ab_env.py): f32 equal on two boxes (46.39 / 46.15, 47.96 / 48.04); bf16 with the 128-workgroup weight gradients
-        # 25.50 -> 25.10 ms: on in the 16-bit modes
-        # round 5 (tools/ab_env.py, two runs of 6 / 10 rounds on two boxes): f32 45.68 -> 45.43 and 45.31 -> 45.17 ms with it: on in every mode
-        self.stem_wlane = options.flag('FAMI_STEM_WGRAD_LANE')
         self._sliced = []              # parents of batch_slice views: their gradient buffers are created (zero-filled) on
                                        # lane 0 before backward starts, so no lane ever races a slice write against the fill
         self._keep = []                # every buffer handed out this step stays alive until the step has been enqueued:
                                        # the caching allocator must not recycle a block across lanes within a step
         # two-launch BatchNorm (fami_bn_train_fwd2 / fami_bn_bwd2: fp64 slot atomics, finalize folded into the apply pass).
         # Sums arrive in atomic order, so the deterministic mode keeps the three-launch forms.
-        self.bn2 = (not self.deterministic) and options.flag('FAMI_BN2', '1')
+        self.bn2 = not self.deterministic
         # BatchNorm statistics folded into the neighbouring convolutions' epilogues (conv.hip EpiBN): the forward
         # statistics into the producing convolution, the backward statistics into the input-gradient convolution that
         # makes the last contribution to the BatchNorm output's gradient.  FAMI_FUSE_BN = 0 | fwd | bwd | 1 (both).
@@ -228,26 +214,13 @@ class Engine:
         self.fuse_bn_fwd3 = fz == 'fwd3' or (fz == 'auto' and self.half)
         self.fuse_bn_bwd = self.bn2 and fz in ('1', 'bwd')
         self.fuse_bn_bwd_auto = self.bn2 and self.half and fz in ('auto', 'autoall', 'bwdauto')
-        # ... and where the phased kernel (conv3x3_t7_kernel) takes it: 0 never, 1 (default) its non-accumulating launches with a
-        # recomputed mask (-0.04 ms), 2 all of them (+0.12 ms: the accumulating variant spills)
-        # round 6 (the input gradient now shares its launch with the weight gradient, csrc/conv_pair.h): 2 -- bf16 step 18.36 -> 18.24 ms
-        # against 1 (tools/ab_env.py, one box), ~100 statistics launches fewer
-        self.fuse_bn_bwd_t7 = options.number('FAMI_FUSE_BN_T7', '2')
-        # order of a convolution's two backward launches: input gradient (the chain's next link) before the weight gradient (a leaf)?
-        # tools/ab_env.py, two runs on two boxes: f32 storage 45.80 -> 45.48 and 45.95 -> 45.63 ms with it (half of it each from the
-        # lanes with / without a weight-gradient stream); bf16 20.21 -> 20.40 and 20.13 -> 20.19 / 20.25: f32 only.
-        # 1: everywhere, 2: only where the weight gradient has its own lane, 3: only elsewhere
-        self.dgrad_first = options.number('FAMI_DGRAD_FIRST', '0' if self.half else '1')
-        # ... and the forward statistics stay a pass of their own behind the 32-channel-phase instances of that kernel (layers of
-        # 64-multiple channels: HRNet-W64's branches, stage 1's 64 -> 64).  W64 fp16 step, tools/ab_env.py on one box: epilogues
-        # everywhere 29.40 ms, forward only 29.05, none 28.59 (while its EpiBN instances spilled); without spills: forward 28.47 vs 28.45
-        # without, backward 28.25: bit 1 on
-        self.fuse_bn_c64 = options.number('FAMI_FUSE_BN_C64', '2')      # bit 0: forward statistics, bit 1: backward statistics (under the rule of FAMI_FUSE_BN_T7)
-        self.fuse_bn_skip = set(filter(None, options.get('FAMI_FUSE_BN_SKIP', '').replace('+', ',').split(',')))      # probes: '1x1', 's2'
-        self.concat_one = options.flag('FAMI_CONCAT_ONE', '1')      # Engine.concat: one launch for up to four sources
+        # ... and the forward statistics stay a pass of their own behind the 32-channel-phase instances of the phased kernel
+        # (conv3x3_t7_kernel; layers of 64-multiple channels: HRNet-W64's branches, stage 1's 64 -> 64).  W64 fp16 step, tools/ab_env.py
+        # on one box: epilogues everywhere 29.40 ms, forward only 29.05, none 28.59 (while its EpiBN instances spilled); without spills:
+        # forward 28.47 vs 28.45 without, backward 28.25: bit 1 on
+        self.fuse_bn_c64 = 2      # bit 0: forward statistics, bit 1: backward statistics
         # the two predictor convolutions of a DCN layer as one (CatParam; needs the Trainer's arena layout): FAMI_MERGE_PREDICTORS
         self.merge_predictors = options.flag('FAMI_MERGE_PREDICTORS', '1')
-        self.fuse_term_bn2 = options.flag('FAMI_FUSE_TERM_BN2', '1')
         # BatchNorm + ReLU applied by the CONSUMER convolution while it stages its input (Engine.conv_bn_relu_into, conv_epi.h
         # XBN): 104 launches and one tensor write + read per BasicBlock less.  FAMI_XBN = 0 | 1; default: on in f32 storage,
         # off in the 16-bit modes.  Measured on MI355X (interleaved A/B of the step, both orders, 10 rounds): f32 50.95 ->
@@ -269,10 +242,7 @@ class Engine:
         # deferred slab reduces of the weight-gradient kernels: described on the host as they are enqueued and launched
         # 16 at a time per stream (fami_wgrad_reduce_batch) at the joins / bucket boundaries / the end of backward --
         # 303 tiny launches per step otherwise sit between every weight gradient and the next kernel of its lane
-        self.defer_reduce = options.flag('FAMI_DEFER_REDUCE', '1')
-        # a 3x3 stride-1 convolution's input gradient and weight gradient as one launch (16-bit storage; csrc/conv_pair.h):
-        # 0 off | 1 where the weight gradient would run on the convolution's own lane | 2 also inside the weight-gradient-stream scopes
-        self.bwd_pair = options.number('FAMI_BWD_PAIR', '1')
+        self.defer_reduce = True
         self.npair = 0                 # combined launches enqueued this step (tests / reporting)
         self._red = {}                 # raw stream -> [ctypes descriptor buffers]
         self._red_dw = {}              # raw stream -> {dw pointers with a pending reduce}
@@ -362,8 +332,6 @@ class Engine:
         own = self._wowner.get(key) if key is not None else None
         if own is not None and own < n:
             target = self._wstreams[own]
-        elif self.use_wlane == 2 and not pair and not self.wlane_scope_now:      # (probe: stage convolutions, one weight-gradient stream per lane)
-            target = self._wstreams[self.lane % n]
         else:
             self._wflip = (self._wflip + 1) % n
             target = self._wstreams[self._wflip]
@@ -911,19 +879,21 @@ class Engine:
                 if out.grad is None:
                     return
                 dy = out.grad
-                on_wl = (self.use_wlane or wl) and need_w
-                self.wlane_scope_now = bool(wl)
+                on_wl = wl and need_w
                 # input gradient + weight gradient as ONE launch (fami_conv2d_bwd_pair_*, csrc/conv_pair.h): the weight gradient is a
-                # leaf that otherwise sits between the input gradient and the next link of the chain on this lane
-                if (self.bwd_pair and x.requires_grad and self.rq(weight) and (xb is None or not self.half) and self.defer_reduce
-                        and not _ABL_WGRAD and (kh, kw, stride, pad, dil) == (3, 3, 1, 1, 1)
-                        and (self.bwd_pair == 2 or not on_wl)
+                # leaf that otherwise sits between the input gradient and the next link of the chain on this lane.  Not inside the
+                # weight-gradient-stream scopes, where the weight gradient leaves the chain anyway (docs/HISTORY.md, round-6 log); the
+                # route field bwd_pair turns it off (fami_conv2d_bwd_pair_ok* answer 0)
+                if (x.requires_grad and self.rq(weight) and (xb is None or not self.half) and self.defer_reduce
+                        and not _ABL_WGRAD and (kh, kw, stride, pad, dil) == (3, 3, 1, 1, 1) and not on_wl
                         and (self.Q.fami_conv2d_bwd_pair_ok(*geo) if self.half else self.Q.fami_conv2d_bwd_pair_ok_f32(*geo))):
                     do_x(pair=True)
                     if self.rq(bias):
                         do_bias()
                     return
-                xfirst = self.dgrad_first == 1 or (self.dgrad_first == 2 and on_wl) or (self.dgrad_first == 3 and not on_wl)
+                # the input gradient (the chain's next link) before the weight gradient (a leaf) in f32 storage, after it in the 16-bit
+                # modes (docs/HISTORY.md, round-5 log, "Enqueue order of a convolution's backward launches")
+                xfirst = not self.half
                 if xfirst:
                     do_x()
                 saved = self._enter_wlane(wpair, id(weight)) if on_wl else None
@@ -953,9 +923,10 @@ class Engine:
                     rec = x.bnrec
                     pays = False
                     if self.fuse_bn_bwd_auto and rec is not None and (kh, stride, pad, dil) == (3, 1, 1, 1):
+                        # every launch of the phased kernel (kind 2; kind 3 under fuse_bn_c64) carries the statistics too: with the
+                        # combined backward launches ~100 statistics launches fewer (docs/HISTORY.md, round-6 log)
                         kind = self.Q.fami_conv_t6_eligible(N, Ho, Wo, Co, Ci)
-                        t7 = self.fuse_bn_bwd_t7
-                        pays = kind == 1 or ((kind == 2 or (kind == 3 and (self.fuse_bn_c64 & 2))) and (t7 == 2 or (t7 == 1 and not acc and rec['rmode'] != 1)))
+                        pays = kind in (1, 2) or (kind == 3 and bool(self.fuse_bn_c64 & 2))
                     stats = None
                     if (rec is not None and (self.fuse_bn_bwd or fuse_here or pays) and x.uses == 0 and not x.nofuse and x.lanes is not None
                             and len(x.lanes) == 1 and not x.f32grad):
@@ -991,8 +962,6 @@ class Engine:
 
     def conv_fuses_stats(self, N, Ho, Wo, Ci, Co, kh, st, pd, dl):
         """Does the forward statistics pass of the BatchNorm behind this convolution go into its epilogue (given bn_fusable)?"""
-        if ('1x1' in self.fuse_bn_skip and kh == 1) or ('s2' in self.fuse_bn_skip and st == 2):
-            return False
         if self.fuse_bn_fwd3:
             kinds = (1, 2, 3) if (self.fuse_bn_c64 & 1) else (1, 2)
             return self.half and (kh, st, pd, dl) == (3, 1, 1, 1) and self.Q.fami_conv_t6_eligible(N, Ho, Wo, Ci, Co) in kinds
@@ -1249,8 +1218,8 @@ class Engine:
                 st = h['stats']
                 # two-launch form (statistics into fp64 slot rows, finalize folded into the apply pass) where the BatchNorm is
                 # large enough for it -- the three-launch form's one-workgroup finalize sat between the two passes of all 53
-                # fuse-term BatchNorms of a step (5 us each); FAMI_FUSE_TERM_BN2=0 restores it
-                two = self.bn2 and self.fuse_term_bn2 and self.bn_fusable(Pk, C)
+                # fuse-term BatchNorms of a step (5 us each)
+                two = self.bn2 and self.bn_fusable(Pk, C)
                 ws = self.zeros_bytes(self.Q.fami_bn_slots_bytes(C)) if two else self.ws(self.Q.fami_bn_workspace(C))
                 if shift == 0:
                     if two:
@@ -1327,7 +1296,7 @@ class Engine:
         y = self.act(N, H, W, Ct)
         n = len(xs)
         # one launch for the lot (the head's three concatenations); distinct tensors only: the backward writes every slice at once
-        one = self.concat_one and 2 <= n <= 4 and all(x.shape[3] % 4 == 0 for x in xs) and len({id(x) for x in xs}) == n
+        one = 2 <= n <= 4 and all(x.shape[3] % 4 == 0 for x in xs) and len({id(x) for x in xs}) == n
         cs = (ctypes.c_int * 4)(*[x.shape[3] for x in xs]) if one else None
         if one:
             self.acall('fami_concat_channels', (ctypes.c_void_p * 4)(*[x.data.data_ptr() for x in xs]), cs, n, _p(y), P)

@@ -12,8 +12,6 @@ Reference: posetimation/layers/basic_model.py:25-63 (BasicBlock), :66-113
 """
 import torch.nn as nn
 
-from . import options
-
 BN_MOMENTUM = 0.1
 
 
@@ -136,68 +134,21 @@ class HighResolutionModule(nn.Module):
                 rows.append(nn.ModuleList(row))
             self.fuse_layers = nn.ModuleList(rows)
 
-    def run_branches(self, eng, xs):
-        """The parallel branches are independent until the fuse: each runs on its own stream lane."""
-        ys = []
-        forked = eng.fork(self.num_branches)
-        for b in range(self.num_branches):
-            if forked:
-                eng.set_lane(b)
-            y = xs[b]
-            for blk in self.branches[b]:
-                y = blk.run(eng, y)
-            ys.append(y)
-        if forked:
-            eng.join(self.num_branches)
-        return ys
-
-    def run_fuse(self, eng, ys):
-        """out_i = relu(sum_j f_ij(x_j)).  Every f_ij -- conv chain, BatchNorm statistics, and in backward the gradient
-        into x_j -- depends on branch j only, so the terms run on stream lane j; the sums follow the join."""
+    def _branches_and_terms(self, eng, xs, forked):
+        """Lane j runs branch j's blocks and then every fuse term f_ij that reads its output: the term's conv chain, its BatchNorm
+        statistics and, in backward, its gradient into x_j depend on branch j only.  Not forked (FAMI_LANES=0, one branch): the
+        same order on the current lane.  -> (branch outputs, fuse-term handles [i][j])"""
         nb = self.num_branches
-        if nb == 1:
-            return ys
-        handles = [[None] * nb for _ in self.fuse_layers]
-        forked = eng.fork(nb) if eng.fuse_lanes else False
+        rows = self.fuse_layers or ()
+        ys, handles = [], [[None] * nb for _ in rows]
         for j in range(nb):
             if forked:
                 eng.set_lane(j)
-            for i, row in enumerate(self.fuse_layers):
-                if j == i:
-                    handles[i][j] = eng.fuse_term(ys[j], None, 0)
-                elif j > i:
-                    handles[i][j] = eng.conv_fuse_term(ys[j], row[j][0], row[j][1], j - i)
-                else:
-                    z = ys[j]
-                    chain = row[j]
-                    for k in range(len(chain) - 1):
-                        z = run_cbr(eng, chain[k], z)
-                    handles[i][j] = eng.conv_fuse_term(z, chain[-1][0], chain[-1][1], 0)
-        if forked:
-            eng.join(nb)
-        return [eng.fuse(hs) for hs in handles]
-
-    def run_both(self, eng, xs):
-        """run_branches + run_fuse inside ONE forked region: lane j runs branch j and then the fuse terms that read it -- no
-        join / fork pair between the two halves (a lane join costs the chip an idle gap on every lane but the slowest).
-        -> (branch outputs, fused outputs)"""
-        nb = self.num_branches
-        if nb == 1 or not eng.fuse_lanes or not options.flag('FAMI_MERGE_FORK'):
-            ys = self.run_branches(eng, xs)
-            return ys, self.run_fuse(eng, ys)
-        forked = eng.fork(nb)
-        if not forked:
-            ys = self.run_branches(eng, xs)
-            return ys, self.run_fuse(eng, ys)
-        ys = []
-        handles = [[None] * nb for _ in self.fuse_layers]
-        for j in range(nb):
-            eng.set_lane(j)
             y = xs[j]
             for blk in self.branches[j]:
                 y = blk.run(eng, y)
             ys.append(y)
-            for i, row in enumerate(self.fuse_layers):
+            for i, row in enumerate(rows):
                 if j == i:
                     handles[i][j] = eng.fuse_term(y, None, 0)
                 elif j > i:
@@ -208,33 +159,27 @@ class HighResolutionModule(nn.Module):
                     for k in range(len(chain) - 1):
                         z = run_cbr(eng, chain[k], z)
                     handles[i][j] = eng.conv_fuse_term(z, chain[-1][0], chain[-1][1], 0)
-        eng.join(nb)
+        return ys, handles
+
+    def run_both(self, eng, xs):
+        """The module in a forked region of its own: branches and fuse terms on their lanes with no join / fork pair between the
+        two (a lane join costs the chip an idle gap on every lane but the slowest), out_i = relu(sum_j f_ij(x_j)) on lane 0 behind
+        the join.  -> (branch outputs, fused outputs)"""
+        nb = self.num_branches
+        forked = eng.fork(nb)
+        ys, handles = self._branches_and_terms(eng, xs, forked)
+        if forked:
+            eng.join(nb)
+        if nb == 1:
+            return ys, ys
         return ys, [eng.fuse(hs) for hs in handles]
 
     def run_lanes(self, eng, xs, last=False):
         """One module INSIDE a region the caller has forked (HRNetBody.run keeps the lanes of a stage forked across its modules):
-        lane j runs branch j and the fuse terms that read it; fused output i is summed on lane i behind an all-to-all of lane
-        events (Engine.lanes_sync) -- no join, no sums on lane 0.  -> (branch outputs, fused outputs, joined)"""
+        fused output i is summed on lane i behind an all-to-all of lane events (Engine.lanes_sync) -- no join, no sums on lane 0.
+        -> (branch outputs, fused outputs, joined)"""
         nb = self.num_branches
-        ys = []
-        handles = [[None] * nb for _ in self.fuse_layers]
-        for j in range(nb):
-            eng.set_lane(j)
-            y = xs[j]
-            for blk in self.branches[j]:
-                y = blk.run(eng, y)
-            ys.append(y)
-            for i, row in enumerate(self.fuse_layers):
-                if j == i:
-                    handles[i][j] = eng.fuse_term(y, None, 0)
-                elif j > i:
-                    handles[i][j] = eng.conv_fuse_term(y, row[j][0], row[j][1], j - i)
-                else:
-                    z = y
-                    chain = row[j]
-                    for k in range(len(chain) - 1):
-                        z = run_cbr(eng, chain[k], z)
-                    handles[i][j] = eng.conv_fuse_term(z, chain[-1][0], chain[-1][1], 0)
+        ys, handles = self._branches_and_terms(eng, xs, True)
         if last or len(handles) < nb:
             # the stage's last module: its sums follow the stage's join on lane 0.  (With the all-to-all here the backward pass would
             # open the stage with a fork and record the all-to-all's events right behind the fork's waits, no kernel in between --
@@ -302,8 +247,8 @@ class HRNetBody(nn.Module):
     def run(self, eng, x):
         """x: engine tensor [N,H,W,3] -> (heatmap T [N,H/4,W/4,J], stage-4 outputs, pre-stage-4 inputs)."""
         outer = eng.wlane_scope
-        eng.wlane_scope = outer or eng.stem_wlane     # serial chain: weight gradients on their own lane (Engine.__init__)
-        eng.wlane_pair = True                         # ... on two of them, alternately (Engine._enter_wlane)
+        eng.wlane_scope = True                        # serial chain: weight gradients on streams of their own (Engine.__init__)
+        eng.wlane_pair = True                         # ... `stem_wlanes` of them, in turn (Engine._enter_wlane)
         eng.serial_scope = True                       # ... and BatchNorm backward statistics in the dgrad epilogues
         x = eng.conv_bn(x, self.conv1, self.bn1, relu=True)
         x = eng.conv_bn(x, self.conv2, self.bn2, relu=True)
@@ -319,7 +264,7 @@ class HRNetBody(nn.Module):
                 eng.join_late_weights()      # the Trainer packs the weight images of stage 3 .. the head beside the stem
             tr = getattr(self, 'transition%d' % (s - 1))
             xs = []
-            eng.wlane_scope = outer or eng.stem_wlane
+            eng.wlane_scope = True
             eng.wlane_pair = True
             for i in range(self.stage_branches[s]):
                 if tr[i] is None:
@@ -338,7 +283,7 @@ class HRNetBody(nn.Module):
             if s == 2:
                 eng.mark('stage2')      # backward: every gradient but the stem stretch's is final here (train.Trainer: early Adam)
             nb = self.stage_branches[s]
-            persist = eng.persist_lanes and eng.fuse_lanes and nb > 1 and eng.fork(nb)      # the stage's lanes stay forked across its modules
+            persist = eng.persist_lanes and nb > 1 and eng.fork(nb)      # the stage's lanes stay forked across its modules
             joined = False
             for mi, mod in enumerate(getattr(self, 'stage%d' % s)):
                 if persist and not joined:

@@ -766,12 +766,10 @@ class Trainer:
             self.packer.run(st, 1)
             for w, buf, geo, _ in dcn:
                 self._lc('fami_dcn_pack_weight_bwd_f32', _p(w.data), _p(buf), *geo, st)
-        if options.flag('FAMI_ABL_PACK') and getattr(self, '_abl_packed', False):
-            packed_fwd = packed_bwd = None          # (upper-bound experiment, WRONG results: the images of the first step stay)
-        elif eng.use_lanes and options.flag('FAMI_PACK_SPLIT'):
+        if eng.use_lanes:
             # (round 5: starting the late / input-gradient packs at stage 2 / 3 on the weight-gradient stream instead of beside the stem
-            #  stretch measured no gain -- bf16 20.26 vs 20.23 ms, f32 45.92 vs 45.72; all packing removed is worth 0.37 / 0.72 ms, FAMI_ABL_PACK)
-            if self.packer.n_early > 0 and options.flag('FAMI_PACK_EARLY'):
+            #  stretch measured no gain -- bf16 20.26 vs 20.23 ms, f32 45.92 vs 45.72; all packing removed is worth 0.37 / 0.72 ms)
+            if self.packer.n_early > 0:
                 self.packer.run(eng.stream, 'early')
                 eng.late_weights_ready = eng.side_launch(lambda st: self.packer.run(st, 'late'))   # HRNetBody.run waits before stage 3
             else:
@@ -784,7 +782,6 @@ class Trainer:
             for w, buf, geo, _ in dcn:
                 self._lc('fami_dcn_pack_weight_bwd_f32', _p(w.data), _p(buf), *geo, eng.stream)
             packed_fwd = packed_bwd = None
-        self._abl_packed = True
         eng.prepacked = self.packer.views
         eng.prepacked_dcn_bwd = {id(w): buf for w, buf, _, _ in dcn}
         eng.prepacked_dcn_fwd = {id(w): fbuf for w, _, _, fbuf in dcn}
@@ -826,20 +823,19 @@ class Trainer:
         if self.use_mi and aux['mis']:
             a, b = self.alpha, self.beta
             coef = [-b * a, b * a, a, -a, a, -a]        # core fn :119-148
-            lanes = eng.use_lanes and eng.mi_lanes
-            if lanes:
+            if eng.use_lanes:      # the six seeds on three lanes
                 eng._do_fork(3)        # (not taped: the seeds are enqueued here, ahead of the tape walk)
             pending = []
             same = aux.get('mi_same', {})      # repeated terms (mi_6 is mi_2): one gradient pass with the summed coefficient
             for k, j in same.items():
                 coef[j] += coef[k]
             for k, ((val, seed), c) in enumerate(zip(aux['mis'], coef)):
-                if lanes:
+                if eng.use_lanes:
                     eng.set_lane(k % 3)
                 eng.call('fami_axpby_f32', _p(val), None, _p(self.loss_parts[1 + k:2 + k]), 1, 1.0, 0.0)
                 if k not in same:
                     pending.append(seed(c * ls, None, True))
-            if lanes:
+            if eng.use_lanes:
                 eng._do_join(3)
             for fin in pending:        # the accumulations into the (shared) gradient buffers, in term order, on lane 0
                 fin()
@@ -882,9 +878,9 @@ class Trainer:
         """(lo, hi): the arena range of the stem / layer1 / first-transition parameters, whose gradients are the LAST the backward
         pass completes.  Everything outside it is final when backward reaches the boundary of stage 2 (modules.HRNetBody.run marks
         it), so its Adam update can run on a side lane beside the rest of the backward pass instead of behind it (the one-launch
-        Adam is 0.33 ms of pure HBM traffic at the end of every step).  None: no such split (FAMI_EARLY_ADAM=0, fp16's checked step,
-        data-parallel plans, a frozen backbone)."""
-        if not options.flag('FAMI_EARLY_ADAM') or self.loss_scale != 1.0:
+        Adam is 0.33 ms of pure HBM traffic at the end of every step).  None: no such split (fp16's checked step, data-parallel
+        plans, a frozen backbone)."""
+        if self.loss_scale != 1.0:
             return None
         hr = getattr(model, 'hrnet', None)
         if hr is None or not hasattr(hr, 'stage2') or not hasattr(hr, 'conv1'):

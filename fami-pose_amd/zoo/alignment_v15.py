@@ -18,7 +18,6 @@ import os.path as osp
 import torch
 import torch.nn as nn
 
-from .. import options
 from ..modules import ChainOfBasicBlocks, conv_bn_relu, run_conv
 from ..runtime import EngineModule
 from .hrnet import HRNetPlus, _hyper_parameters
@@ -154,13 +153,6 @@ class Alignment_V15(EngineModule):
     def _translation(self, eng, diff):
         seq = self.feat_global_offset_layers
         z = seq[0].run(eng, diff)
-        if options.number('FAMI_ABL_REGTAIL'):
-            # upper-bound experiment (WRONG results, refused without FAMI_ALLOW_WRONG=1): the regressor ends after its first
-            # n - 1 stride-2 stages; what a fused kernel for the rest of the chain could save at most
-            from ..engine import T
-            for i in range(1, options.number('FAMI_ABL_REGTAIL')):
-                z = seq[i].run(eng, z)
-            return T(torch.zeros(diff.shape[0], 2, device=eng.dev))
         for i in range(1, 6):
             z = seq[i].run(eng, z)
         z = eng.flatten_chw(z)
@@ -185,7 +177,7 @@ class Alignment_V15(EngineModule):
         sups = [eng.batch_slice(feat, (1 + i) * B, (2 + i) * B) for i in range(S)]
         diffs = [eng.sub(sup, kf) for sup in sups]
         aligned, shifts = [], []
-        forked = eng.fork(min(S, 4)) if eng.regressor_lanes else False
+        forked = eng.fork(min(S, 4))
         if forked:
             eng.defer_bn = []
         for i in range(S):
@@ -231,7 +223,7 @@ class Alignment_V15(EngineModule):
             # tensors): computed once; the output list still carries six scalars and each keeps its own gradient seed
             terms = [lambda: label_mi(all_agg), lambda: feat_mi(kf, all_agg), lambda: label_mi(agg_sup),
                      lambda: feat_mi(agg_sup, all_agg), lambda: label_mi(kf)]
-            forked = eng.fork(3) if eng.mi_lanes else False
+            forked = eng.fork(3)
             mis = []
             for i, fn in enumerate(terms):
                 if forked:

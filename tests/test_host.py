@@ -207,7 +207,7 @@ def test_every_environment_switch_goes_through_the_one_parser():
     assert used and used <= set(options.SWITCHES), sorted(used - set(options.SWITCHES))
     with pytest.raises(KeyError):
         options.get('FAMI_NOT_A_SWITCH')
-    assert options.flag('FAMI_LANES') and not options.flag('FAMI_WGRAD_LANE')
+    assert options.flag('FAMI_LANES') and not options.flag('FAMI_DETERMINISTIC')
     # the route struct mirrors the header: ints / longs only, first field its own size
     names = [n for n, _ in Route._fields_]
     assert names[0] == 'size' and len(names) > 60 and {'use_t6', 'dcn_bwd2', 'wg6_target', 'bn_small_elems'} <= set(names)

@@ -38,7 +38,7 @@ def stretch(record, back, upto=4):
     eng = Engine(dev, grad_views=tr.views, record=record, dtype=adt)
     tr.packer.run(eng.stream); eng.prepacked = tr.packer.views
     x = eng.frames(kf, sup)
-    eng.wlane_scope = eng.stem_wlane; eng.wlane_pair = True; eng.serial_scope = True
+    eng.wlane_scope = True; eng.wlane_pair = True; eng.serial_scope = True
     x = eng.conv_bn(x, hr.conv1, hr.bn1, relu=True)
     x = eng.conv_bn(x, hr.conv2, hr.bn2, relu=True)
     for blk in list(hr.layer1)[:upto]:
