@@ -17,6 +17,11 @@ Learning-rate groups (Trainer lr_groups, TRAIN.LR_SECOND_GROUP): the reference b
 matches them to the optimizers by parameter count (checkpoints.py:85-99).  A Trainer with groups writes and reads
 exactly that list.  The single-group Adam format is the one `adam_state_dict` writes.  A state of the other optimizer
 kind, or a parameter count that matches no group, raises instead of loading a partial state.
+
+A Trainer with a dynamic loss scale (loss_scale='dynamic') adds one entry, ``'loss_scaler'``, in the layout of
+``torch.amp.GradScaler.state_dict()`` (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker), and
+`resume` restores it; a checkpoint without the entry leaves a dynamic Trainer at its initial scale.  Without a dynamic
+scale the file has exactly the three keys above.  max_grad_norm is a hyper-parameter of the run, not state: not saved.
 """
 import os
 import os.path as osp
@@ -211,7 +216,11 @@ def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
     osd = []
     for o in opts:
         osd.extend(optimizer_state_dicts(o) if hasattr(o, 'table') else [o.state_dict()])
-    torch.save({'begin_epoch': epoch, 'state_dict': sd, 'optimizer': osd}, path)
+    ckpt = {'begin_epoch': epoch, 'state_dict': sd, 'optimizer': osd}
+    dyn = [o for o in opts if getattr(o, 'dynamic_scale', False)]
+    if dyn:
+        ckpt['loss_scaler'] = dyn[0].scaler_state_dict()
+    torch.save(ckpt, path)
     return path
 
 
@@ -237,4 +246,8 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
             load_optimizer_state_dicts(o, osds)
         else:
             o.load_state_dict(osds.pop(0))
+    if 'loss_scaler' in ckpt:
+        for o in opts:
+            if getattr(o, 'dynamic_scale', False):
+                o.load_scaler_state_dict(ckpt['loss_scaler'])
     return model, optimizer, begin_epoch

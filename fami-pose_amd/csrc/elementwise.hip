@@ -309,22 +309,47 @@ __global__ void adam_prep_kernel(float* state, float beta1, float beta2, unsigne
     state[3] = 1.f - powf(beta2, t);
   }
 }
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, const float* __restrict__ state, float beta1,
-                            float beta2, float eps, float wd) {
+// torch.optim.Adam's single-tensor rule for one element (amsgrad = False, maximize = False).  Every rounding is spelled out
+// (fmaf where the compiler has always fused, separately rounded products elsewhere) instead of left to fp-contraction: the
+// plain and the scaled kernel inline this into different surroundings, and must agree bit for bit at a multiplier of 1.
+__device__ __forceinline__ void adam_elem(float& p, float gi, float& m, float& v, float beta1, float beta2, float eps,
+                                          float wd, float step_size, float bc2s) {
+#pragma clang fp contract(off)
+  const float pi = p;
+  if (wd != 0.f) gi = fmaf(wd, pi, gi);
+  const float mi = beta1 * m + (1.f - beta1) * gi;
+  const float vi = beta2 * v + (1.f - beta2) * gi * gi;
+  m = mi;
+  v = vi;
+  p = fmaf(-step_size, mi / (sqrtf(vi) / bc2s + eps), pi);
+}
+// SCALED: the gradient is gmul[0] * g on load (the clip coefficient of fami_clip_coef_f32); the arena is not rewritten
+template <bool SCALED>
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, long n, const float* __restrict__ state, float beta1,
+                                          float beta2, float eps, float wd, const float* __restrict__ gmul) {
   const float lr = state[1], bc1 = state[2], bc2s = sqrtf(state[3]);
   if (bc1 == 0.f) return;   // skipped step (non-finite gradients, see adam_prep_kernel); bc1 > 0 from step 1 on otherwise
   const float step_size = lr / bc1;
+  const float gm = SCALED ? gmul[0] : 1.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    const float pi = p[i];
-    if (wd != 0.f) gi += wd * pi;
-    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
+    const float gi = SCALED ? mul_rn(gm, g[i]) : g[i];
+    float pe = p[i], me = m[i], ve = v[i];
+    adam_elem(pe, gi, me, ve, beta1, beta2, eps, wd, step_size, bc2s);
+    m[i] = me;
+    v[i] = ve;
+    p[i] = pe;
   }
+}
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, long n, const float* __restrict__ state, float beta1,
+                            float beta2, float eps, float wd) {
+  adam_body<false>(p, g, m, v, n, state, beta1, beta2, eps, wd, nullptr);
+}
+__global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, long n, const float* __restrict__ state, float beta1,
+                                   float beta2, float eps, float wd, const float* __restrict__ gmul) {
+  adam_body<true>(p, g, m, v, n, state, beta1, beta2, eps, wd, gmul);
 }
 
 
@@ -556,6 +581,15 @@ int fami_adam_f32(float* p, const float* g, float* m, float* v, long n, const fl
   FAMI_REQUIRE(p && g && m && v && state && n > 0, "fami_adam_f32", "bad argument");
   hipLaunchKernelGGL(adam_kernel, dim3(fami_ew_grid(n)), dim3(256), 0, s, p, g, m, v, n, state, beta1, beta2, eps, weight_decay);
   FAMI_CHECK_LAUNCH("fami_adam_f32");
+  return FAMI_OK;
+}
+// the same update with the gradient gmul[0] * g (gmul: device float, e.g. the clip coefficient): bitwise fami_adam_f32 at gmul[0] == 1
+int fami_adam_scaled_f32(float* p, const float* g, float* m, float* v, long n, const float* state, float beta1, float beta2,
+                         float eps, float weight_decay, const float* gmul, hipStream_t s) {
+  FAMI_REQUIRE(p && g && m && v && state && gmul && n > 0, "fami_adam_scaled_f32", "bad argument");
+  hipLaunchKernelGGL(adam_scaled_kernel, dim3(fami_ew_grid(n)), dim3(256), 0, s, p, g, m, v, n, state, beta1, beta2, eps,
+                     weight_decay, gmul);
+  FAMI_CHECK_LAUNCH("fami_adam_scaled_f32");
   return FAMI_OK;
 }
 

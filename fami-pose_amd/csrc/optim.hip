@@ -6,6 +6,13 @@
 // tail elements around it, so an arena sub-range with unaligned bounds (the Trainer's in-backward split) still works.
 // The step count, the learning rate and the skip decision live in a device vector, as Adam's do: a captured hipGraph
 // keeps replaying across LR changes and across the first-step rule of the momentum buffer.
+//
+// Global-norm gradient clipping and dynamic loss scaling, device-resident (nothing here needs a host sync or a re-capture):
+// the sum of squares of the gradient arena as a partial-slab reduction (sumsq_kernel: one fixed contiguous chunk and one
+// plain store per workgroup, no float atomics, so the result is a pure function of (g, n, alignment) and bitwise equal run to
+// run), alone or fused into the unscale-and-check pass; clip_coef_kernel turns the slab into {total_norm, coef}
+// (torch.nn.utils.clip_grad_norm_, norm_type 2); the *_scaled optimizer entry points multiply the gradient by a device
+// scalar on load instead of rewriting the arena; loss_scale_update_kernel is torch.amp.GradScaler's update rule.
 #include "common.h"
 
 // state = {step, lr, apply}
@@ -24,30 +31,34 @@ __global__ void sgd_prep_kernel(float* state, unsigned* flag) {
   }
 }
 
-// torch.optim.SGD's single-tensor rule for one element (maximize = False)
+// torch.optim.SGD's single-tensor rule for one element (maximize = False).  Every rounding is spelled out (fmaf where the
+// compiler has always fused, separately rounded products elsewhere) instead of left to fp-contraction: the plain and the
+// scaled kernels inline this into different surroundings, and their results must agree bit for bit at a multiplier of 1.
 template <bool MOM>
 __device__ __forceinline__ void sgd_elem(float& p, float g, float& b, float lr, float mom, float damp1, float wd,
                                          bool first, int nesterov) {
+#pragma clang fp contract(off)
   float d = g;
-  if (wd != 0.f) d += wd * p;
+  if (wd != 0.f) d = fmaf(wd, p, d);
   if (MOM) {
     b = first ? d : mom * b + damp1 * d;          // the first step clones d: undampened
-    d = nesterov ? d + mom * b : b;
+    d = nesterov ? fmaf(mom, b, d) : b;
   }
-  p -= lr * d;
+  p = fmaf(-lr, d, p);
 }
 
 // head: the elements in front of the first 16-byte boundary of p (g and buf share p's alignment; head = n when they
 // do not, and every element takes the scalar path)
-template <bool MOM>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                  float* __restrict__ buf, long n, long head,
-                                                  const float* __restrict__ state, float mom, float dampening,
-                                                  float wd, int nesterov) {
+// SCALED: the gradient is gmul[0] * g on load (the clip coefficient of fami_clip_coef_f32); the arena is not rewritten
+template <bool MOM, bool SCALED>
+__device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                         long head, const float* __restrict__ state, float mom, float dampening, float wd,
+                                         int nesterov, const float* __restrict__ gmul) {
   if (state[2] == 0.f) return;   // skipped step (non-finite gradients, see sgd_prep_kernel)
   const float lr = state[1];
   const bool first = state[0] <= 1.f;
   const float damp1 = 1.f - dampening;
+  const float gm = SCALED ? gmul[0] : 1.f;
   const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
   const long n4 = (n - head) >> 2, tail = head + n4 * 4;
   for (long i = tid; i < n4; i += stride) {
@@ -59,7 +70,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       float pe = pv[t], be = bv[t];
-      sgd_elem<MOM>(pe, gv[t], be, lr, mom, damp1, wd, first, nesterov);
+      sgd_elem<MOM>(pe, SCALED ? mul_rn(gm, gv[t]) : gv[t], be, lr, mom, damp1, wd, first, nesterov);
       pv[t] = pe;
       bv[t] = be;
     }
@@ -71,9 +82,148 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   for (long j = tid; j < nrest; j += stride) {
     const long i = j < head ? j : tail + (j - head);
     float pe = p[i], be = MOM ? buf[i] : 0.f;
-    sgd_elem<MOM>(pe, g[i], be, lr, mom, damp1, wd, first, nesterov);
+    sgd_elem<MOM>(pe, SCALED ? mul_rn(gm, g[i]) : g[i], be, lr, mom, damp1, wd, first, nesterov);
     p[i] = pe;
     if (MOM) buf[i] = be;
+  }
+}
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                  float* __restrict__ buf, long n, long head,
+                                                  const float* __restrict__ state, float mom, float dampening,
+                                                  float wd, int nesterov) {
+  sgd_body<MOM, false>(p, g, buf, n, head, state, mom, dampening, wd, nesterov, nullptr);
+}
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_scaled_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ buf, long n, long head,
+                                                         const float* __restrict__ state, float mom, float dampening,
+                                                         float wd, int nesterov, const float* __restrict__ gmul) {
+  sgd_body<MOM, true>(p, g, buf, n, head, state, mom, dampening, wd, nesterov, gmul);
+}
+
+// ---- the sum of squares of a gradient arena ------------------------------------------------------------------------------
+// SUMSQ_PARTS workgroups of 256 lanes, always all of them: workgroup b owns the contiguous run of ceil(n4 / SUMSQ_PARTS) 16-byte
+// vectors [b * chunk, (b + 1) * chunk) of the aligned body and stores ONE float into partials[b] (0 when its run is empty);
+// workgroup 0 also takes the scalar head / tail elements (at most 3 + 3), one per lane.  Per lane: one fp32 accumulator per
+// vector component over ceil(chunk / 256) vectors in address order, the four components pairwise (2 additions) plus the
+// scalar rest (1), wave_sum (6), the four waves through LDS pairwise (2).  The longest chain of fp32 additions is therefore
+//   k = ceil(ceil(n4 / 2048) / 256) + 11      (42 at the 64 655 204 elements of the W48 arena)
+// and the relative error of the sum of non-negative squares at most (k + 1) 2^-24.  No atomics: the slab is a pure function of
+// (g, n, alignment).  RW: the unscale-and-check pass in front of it -- g *= f * (fdev ? fdev[0] : 1), *flag raised on inf /
+// NaN, exactly what unscale_check_kernel leaves in the arena -- with the squares taken from the unscaled values on their way
+// back to memory (partials may then be null: no reduction).
+constexpr int SUMSQ_PARTS = 2048;
+
+template <bool RW>
+__device__ __forceinline__ f32x4 sumsq_vec(float* __restrict__ a, float mul, bool& bad) {
+  f32x4 v = ld4(a);
+  if (RW) {
+    v = v * mul;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bad |= !(fabsf(v[t]) <= 3.4028235e38f);
+    st4(a, v);
+  }
+  return v;
+}
+
+template <bool RW>
+__global__ __launch_bounds__(256) void sumsq_kernel(float* __restrict__ g, long n, long head, float f,
+                                                    const float* __restrict__ fdev, unsigned* __restrict__ flag,
+                                                    float* __restrict__ partials) {
+  const float mul = RW ? (fdev ? f * fdev[0] : f) : 1.f;
+  const long n4 = (n - head) >> 2, tail = head + n4 * 4;
+  const long chunk = (n4 + gridDim.x - 1) / gridDim.x;
+  const long lo = blockIdx.x * chunk, hi = lo + chunk < n4 ? lo + chunk : n4;
+  float* __restrict__ body = g + head;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  bool bad = false;
+  long i = lo + threadIdx.x;
+  for (; i + 3 * 256 < hi; i += 4 * 256) {       // four 16-byte loads in flight per lane; summed in address order
+    const f32x4 v0 = sumsq_vec<RW>(body + i * 4, mul, bad);
+    const f32x4 v1 = sumsq_vec<RW>(body + (i + 256) * 4, mul, bad);
+    const f32x4 v2 = sumsq_vec<RW>(body + (i + 512) * 4, mul, bad);
+    const f32x4 v3 = sumsq_vec<RW>(body + (i + 768) * 4, mul, bad);
+    acc += v0 * v0;
+    acc += v1 * v1;
+    acc += v2 * v2;
+    acc += v3 * v3;
+  }
+  for (; i < hi; i += 256) {
+    const f32x4 v = sumsq_vec<RW>(body + i * 4, mul, bad);
+    acc += v * v;
+  }
+  float rest = 0.f;
+  const long nrest = head + (n - tail);          // <= 6: [0, head) and [tail, n), one element per lane of workgroup 0
+  if (blockIdx.x == 0 && threadIdx.x < nrest) {
+    const long j = threadIdx.x < head ? threadIdx.x : tail + (threadIdx.x - head);
+    float v = g[j];
+    if (RW) {
+      v *= mul;
+      bad |= !(fabsf(v) <= 3.4028235e38f);
+      g[j] = v;
+    }
+    rest = v * v;
+  }
+  if (RW && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+  if (!partials) return;
+  float s = wave_sum(((acc[0] + acc[1]) + (acc[2] + acc[3])) + rest);
+  __shared__ float red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// clip = {total_norm, coef}: the slab summed in double in a fixed order (each lane a contiguous run of partials in index
+// order, then wave_sum_d and the four waves pairwise), total_norm = sqrt(sum) rounded to fp32 once,
+// coef = min(1, max_norm / (total_norm + 1e-6f)) -- clip_grad_norm_'s rule.  A non-finite norm raises flag[0] (coef = 0): the
+// checked prep kernels then skip and count the step like an fp16 overflow.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int nparts,
+                                                        const float* __restrict__ max_norm, float* __restrict__ clip,
+                                                        unsigned* __restrict__ flag) {
+  const int per = (nparts + 255) / 256;
+  double s = 0.0;
+  for (int j = 0; j < per; ++j) {
+    const int i = threadIdx.x * per + j;
+    if (i < nparts) s += (double)partials[i];
+  }
+  s = wave_sum_d(s);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    float coef = fminf(1.f, max_norm[0] / (norm + 1e-6f));
+    if (!(fabsf(norm) <= 3.4028235e38f)) {
+      coef = 0.f;
+      flag[0] = 1u;
+    }
+    clip[0] = norm;
+    clip[1] = coef;
+  }
+}
+
+// scaler = {scale, 1 / scale, growth tracker}: torch's _amp_update_scale_.  Reads flag[0] and leaves it alone (the checked
+// prep of the optimizer clears it afterwards).
+__global__ void loss_scale_update_kernel(float* __restrict__ scaler, const unsigned* __restrict__ flag, float growth,
+                                         float backoff, int interval) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    float scale = scaler[0];
+    if (flag[0]) {
+      scale *= backoff;
+      scaler[2] = 0.f;
+    } else {
+      const float t = scaler[2] + 1.f;
+      if (t >= (float)interval) {
+        const float grown = scale * growth;
+        if (fabsf(grown) <= 3.4028235e38f) scale = grown;     // growth that would reach inf is refused
+        scaler[2] = 0.f;
+      } else {
+        scaler[2] = t;
+      }
+    }
+    scaler[0] = scale;
+    scaler[1] = 1.f / scale;
   }
 }
 
@@ -93,17 +243,21 @@ int fami_sgd_prep_checked_f32(float* state, unsigned* flag, hipStream_t s) {
   FAMI_CHECK_LAUNCH("fami_sgd_prep_checked_f32");
   return FAMI_OK;
 }
+// head elements of the scalar path in front of the 16-byte aligned body (n: no common alignment, everything scalar)
+static long sgd_head(const float* p, const float* g, const float* buf, long n, bool mom) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p) & 15;
+  const bool same = (reinterpret_cast<uintptr_t>(g) & 15) == a && (!mom || (reinterpret_cast<uintptr_t>(buf) & 15) == a);
+  long head = n;
+  if (same && (a & 3) == 0) head = ((16 - (long)a) & 15) >> 2;
+  return head > n ? n : head;
+}
 int fami_sgd_f32(float* p, const float* g, float* buf, long n, const float* state, float momentum, float dampening,
                  float weight_decay, int nesterov, hipStream_t s) {
   FAMI_REQUIRE(p && g && state && n > 0 && (momentum == 0.f || buf), "fami_sgd_f32", "bad argument");
   FAMI_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), "fami_sgd_f32",
                "nesterov needs a momentum and zero dampening");
   const bool mom = momentum != 0.f;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p) & 15;
-  const bool same = (reinterpret_cast<uintptr_t>(g) & 15) == a && (!mom || (reinterpret_cast<uintptr_t>(buf) & 15) == a);
-  long head = n;
-  if (same && (a & 3) == 0) head = ((16 - (long)a) & 15) >> 2;
-  if (head > n) head = n;
+  const long head = sgd_head(p, g, buf, n, mom);
   const dim3 grid(fami_ew_grid(head == n ? n : (n + 3) / 4));     // a chip-sized grid (<= 2048 blocks) strides the rest
   if (mom)
     hipLaunchKernelGGL(sgd_kernel<true>, grid, dim3(256), 0, s, p, g, buf, n, head, state, momentum, dampening,
@@ -112,6 +266,60 @@ int fami_sgd_f32(float* p, const float* g, float* buf, long n, const float* stat
     hipLaunchKernelGGL(sgd_kernel<false>, grid, dim3(256), 0, s, p, g, (float*)nullptr, n, head, state, momentum,
                        dampening, weight_decay, nesterov);
   FAMI_CHECK_LAUNCH("fami_sgd_f32");
+  return FAMI_OK;
+}
+// the same update with the gradient gmul[0] * g (gmul: device float, e.g. the clip coefficient): bitwise fami_sgd_f32 at gmul[0] == 1
+int fami_sgd_scaled_f32(float* p, const float* g, float* buf, long n, const float* state, float momentum, float dampening,
+                        float weight_decay, int nesterov, const float* gmul, hipStream_t s) {
+  FAMI_REQUIRE(p && g && state && gmul && n > 0 && (momentum == 0.f || buf), "fami_sgd_scaled_f32", "bad argument");
+  FAMI_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), "fami_sgd_scaled_f32",
+               "nesterov needs a momentum and zero dampening");
+  const bool mom = momentum != 0.f;
+  const long head = sgd_head(p, g, buf, n, mom);
+  const dim3 grid(fami_ew_grid(head == n ? n : (n + 3) / 4));
+  if (mom)
+    hipLaunchKernelGGL(sgd_scaled_kernel<true>, grid, dim3(256), 0, s, p, g, buf, n, head, state, momentum, dampening,
+                       weight_decay, nesterov, gmul);
+  else
+    hipLaunchKernelGGL(sgd_scaled_kernel<false>, grid, dim3(256), 0, s, p, g, (float*)nullptr, n, head, state, momentum,
+                       dampening, weight_decay, nesterov, gmul);
+  FAMI_CHECK_LAUNCH("fami_sgd_scaled_f32");
+  return FAMI_OK;
+}
+
+// ---- gradient norm, clip coefficient, loss-scale update
+int fami_sumsq_parts(void) { return SUMSQ_PARTS; }
+// elements in front of the first 16-byte boundary of a 4-byte aligned g
+static long sumsq_head(const float* g, long n) {
+  const long head = ((16 - (long)(reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2;
+  return head > n ? n : head;
+}
+// partials (device float[fami_sumsq_parts()]): every slot is written; their sum is sum_i g[i]^2
+int fami_sumsq_f32(const float* g, long n, float* partials, hipStream_t s) {
+  FAMI_REQUIRE(g && partials && n > 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0, "fami_sumsq_f32", "bad argument");
+  hipLaunchKernelGGL(sumsq_kernel<false>, dim3(SUMSQ_PARTS), dim3(256), 0, s, const_cast<float*>(g), n, sumsq_head(g, n), 1.f,
+                     (const float*)nullptr, (unsigned*)nullptr, partials);
+  FAMI_CHECK_LAUNCH("fami_sumsq_f32");
+  return FAMI_OK;
+}
+// fami_unscale_check_f32 with an optional device factor (fdev) and the sum of squares of the unscaled values (partials; may be null)
+int fami_unscale_check_sumsq_f32(float* g, long n, float f, const float* fdev, unsigned* flag, float* partials, hipStream_t s) {
+  FAMI_REQUIRE(g && flag && n > 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0, "fami_unscale_check_sumsq_f32", "bad argument");
+  hipLaunchKernelGGL(sumsq_kernel<true>, dim3(SUMSQ_PARTS), dim3(256), 0, s, g, n, sumsq_head(g, n), f, fdev, flag, partials);
+  FAMI_CHECK_LAUNCH("fami_unscale_check_sumsq_f32");
+  return FAMI_OK;
+}
+int fami_clip_coef_f32(const float* partials, int nparts, const float* max_norm_dev, float* clip, unsigned* flag, hipStream_t s) {
+  FAMI_REQUIRE(partials && nparts > 0 && max_norm_dev && clip && flag, "fami_clip_coef_f32", "bad argument");
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, s, partials, nparts, max_norm_dev, clip, flag);
+  FAMI_CHECK_LAUNCH("fami_clip_coef_f32");
+  return FAMI_OK;
+}
+int fami_loss_scale_update_f32(float* scaler, const unsigned* flag, float growth, float backoff, int interval, hipStream_t s) {
+  FAMI_REQUIRE(scaler && flag && growth >= 1.f && backoff > 0.f && backoff <= 1.f && interval > 0,
+               "fami_loss_scale_update_f32", "bad argument");
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, s, scaler, flag, growth, backoff, interval);
+  FAMI_CHECK_LAUNCH("fami_loss_scale_update_f32");
   return FAMI_OK;
 }
 

@@ -42,9 +42,12 @@ class FlatAdam:
     which makes a graph-mode Trainer re-capture.
 
     runs: the arena ranges [(lo, hi)] this optimizer updates (None: the whole arena) -- one learning-rate group of a
-    Trainer (parameter_groups).  share: another group's optimizer whose gradient and moment arenas this one uses."""
+    Trainer (parameter_groups).  share: another group's optimizer whose gradient and moment arenas this one uses.
+    gmul (set_grad_multiplier): a device float the gradient is multiplied by on load -- the clip coefficient of
+    fami_clip_coef_f32; the gradient arena itself is not rewritten.  None: exactly the launches of the plain update."""
 
     kind = 'adam'
+    gmul = None
 
     def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, runs=None, share=None):
         self.p = flat_param
@@ -62,6 +65,11 @@ class FlatAdam:
         self.initial_lr = float(lr)
         self.hyper_version = 0
         self.state = torch.tensor([0.0, lr, 1.0, 1.0], device=flat_param.device)   # step, lr, bc1, bc2
+
+    def set_grad_multiplier(self, t):
+        """t: device float tensor [1] read by every later update (None: back to the unscaled update).  A graph-mode
+        Trainer bakes the choice into its captured plan: it sets it once, at construction."""
+        self.gmul = _check_gmul(t, self.p)
 
     def tensors(self):
         """the device state a step mutates besides the parameters (a graph capture's warm-up restores it)"""
@@ -99,6 +107,10 @@ class FlatAdam:
             self._launch(a, b, s)
 
     def _launch(self, lo, hi, s):
+        if self.gmul is not None:
+            lib().call('fami_adam_scaled_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]),
+                       hi - lo, _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, _p(self.gmul), s)
+            return
         lib().call('fami_adam_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]), hi - lo,
                    _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, s)
 
@@ -109,9 +121,10 @@ class FlatSGD:
     defaults.py:137-140).  The protocol of FlatAdam: the step count (it selects the momentum buffer's first-step rule),
     the learning rate and the skip decision of the checked step live in a device vector; momentum / dampening / weight
     decay / nesterov are kernel arguments (set_hyper bumps `hyper_version`).  The momentum buffer exists only with a
-    momentum, as torch's does."""
+    momentum, as torch's does.  gmul / set_grad_multiplier: as FlatAdam's."""
 
     kind = 'sgd'
+    gmul = None
 
     def __init__(self, flat_param, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, runs=None,
                  share=None):
@@ -127,6 +140,9 @@ class FlatSGD:
         self.initial_lr = float(lr)
         self.hyper_version = 0
         self.state = torch.tensor([0.0, lr, 1.0], device=flat_param.device)        # step, lr, apply
+
+    def set_grad_multiplier(self, t):
+        self.gmul = _check_gmul(t, self.p)
 
     def tensors(self):
         return ([] if self.buf is None else [self.buf]) + [self.state]
@@ -165,8 +181,18 @@ class FlatSGD:
 
     def _launch(self, lo, hi, s):
         buf = None if self.momentum == 0.0 else _p(self.buf[lo:hi])
+        if self.gmul is not None:
+            lib().call('fami_sgd_scaled_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), buf, hi - lo, _p(self.state),
+                       self.momentum, self.dampening, self.wd, int(self.nesterov), _p(self.gmul), s)
+            return
         lib().call('fami_sgd_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), buf, hi - lo, _p(self.state), self.momentum,
                    self.dampening, self.wd, int(self.nesterov), s)
+
+
+def _check_gmul(t, like):
+    if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == 1 and t.device == like.device):
+        raise ValueError('the gradient multiplier is one fp32 element on the device of the parameters')
+    return t
 
 
 def _check_sgd(lr, momentum, dampening, weight_decay, nesterov):
@@ -570,16 +596,31 @@ class Trainer:
     loss_scale: gradients of the 16-bit activation modes are seeded with `loss_scale * dLoss` and the flat fp32
     gradient arena is divided by it before Adam (static scaling; fp16's smallest normal is 6e-5 while the MSE seed is
     ~2e-6 * error).  Default: 8192 for fp16, 1 otherwise (bf16 has fp32's exponent range).
+    loss_scale='dynamic': torch.amp.GradScaler's rule on the device -- the scale lives in a device vector
+    {scale, 1 / scale, growth tracker}, halves (backoff_factor) on a step whose gradients hold inf / NaN (that step is
+    skipped and counted) and doubles (growth_factor) after growth_interval clean steps; `scaler` overrides GradScaler's
+    defaults (init_scale, growth_factor, backoff_factor, growth_interval).  The seeds read the scale and the unscale
+    pass its reciprocal from that vector, so a captured plan keeps replaying while the scale moves.
+
+    max_grad_norm: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) between backward and the optimizer, on the
+    device: the 2-norm of the whole flat gradient arena (every trainable parameter once) after the data-parallel mean
+    and the loss unscale, reduced by a partial-slab kernel (fused into the unscale pass where one runs), then
+    coef = min(1, max / (norm + 1e-6)), which every learning-rate group's update kernel multiplies the gradients by on
+    load -- the arena is not rewritten.  A non-finite norm skips (and counts) the step; torch would let it through.
+    The threshold is a device scalar (set_max_grad_norm): no re-capture.  The total norm has to exist before the first
+    update, so the in-backward optimizer split (_find_adam_split) is off while clipping -- or a dynamic scale -- is on,
+    as it is for the checked fp16 step.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
-                 weight_decay=0.0, nesterov=False, lr_groups=None):
+                 weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
-        from a reference config."""
+        from a reference config.  max_grad_norm / loss_scale='dynamic' / scaler: see the class docstring (the reference
+        configuration has no such keys: from_cfg takes them as keyword arguments)."""
         self.model = model
         self.route = getattr(model, 'route', None)      # kernel-routing state (None: process default), as the model's engines
         self.targets_from_joints, self.sigma = targets_from_joints, sigma
@@ -588,16 +629,53 @@ class Trainer:
             raise RuntimeError('Trainer needs the model on the GPU (HIP path only)')
         self.mse_weight, self.alpha, self.beta, self.use_mi = mse_weight, alpha, beta, use_mi
         self.act_dtype = getattr(model, 'act_dtype', torch.float32)
+        self.dynamic_scale = isinstance(loss_scale, str)
+        if self.dynamic_scale and loss_scale != 'dynamic':
+            raise ValueError("loss_scale is None, a number or 'dynamic', not %r" % (loss_scale,))
+        if scaler is not None and not self.dynamic_scale:
+            raise ValueError("`scaler` configures loss_scale='dynamic'")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError('max_grad_norm must be positive, not %r' % (max_grad_norm,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.scaler_cfg = None
+        if self.dynamic_scale:
+            # torch.amp.GradScaler's names, defaults and argument checks
+            cfg = {'init_scale': 65536.0, 'growth_factor': 2.0, 'backoff_factor': 0.5, 'growth_interval': 2000}
+            unknown = set(scaler or ()) - set(cfg)
+            if unknown:
+                raise ValueError('unknown scaler argument(s): %s' % ', '.join(sorted(unknown)))
+            cfg.update(scaler or {})
+            if not (cfg['init_scale'] > 0.0 and cfg['growth_factor'] > 1.0 and 0.0 < cfg['backoff_factor'] < 1.0 and
+                    int(cfg['growth_interval']) >= 1):
+                raise ValueError('scaler needs init_scale > 0, growth_factor > 1, 0 < backoff_factor < 1 and '
+                                 'growth_interval >= 1: %r' % (cfg,))
+            self.scaler_cfg = cfg
+            loss_scale = cfg['init_scale']
+        # (with 'dynamic': the INITIAL scale; loss_scale_value() reads the current one)
         self.loss_scale = float(loss_scale if loss_scale is not None else
                                 (8192.0 if self.act_dtype == torch.float16 else 1.0))
         self.flat, self.table = flatten_parameters(model)
-        # overflow guard of the static loss scale: a device flag raised by the unscale pass, consumed by the optimizer
-        self.overflow = torch.zeros(2, dtype=torch.int32, device=self.dev) if self.loss_scale != 1.0 else None   # {raised, skipped steps}
+        # overflow guard of the loss scale / of the gradient norm: a device flag raised by the unscale pass (inf / NaN
+        # gradients) or by the clip coefficient (non-finite norm), consumed by the optimizer
+        guarded = self.loss_scale != 1.0 or self.dynamic_scale or self.max_grad_norm is not None
+        self.overflow = torch.zeros(2, dtype=torch.int32, device=self.dev) if guarded else None   # {raised, skipped steps}
+        # device state of the two options: {scale, 1 / scale, growth tracker} and {total norm, coefficient, threshold} + the
+        # partial sums of the norm
+        self.scaler_state = (torch.tensor([self.loss_scale, 1.0 / self.loss_scale, 0.0], device=self.dev)
+                       if self.dynamic_scale else None)
+        self._scaler_version = 0
+        self.clip = self._partials = None
+        if self.max_grad_norm is not None:
+            self.clip = torch.tensor([0.0, 1.0, self.max_grad_norm], device=self.dev)
+            self._partials = torch.zeros(lib().cdll.fami_sumsq_parts(), device=self.dev)
         # one flat optimizer per learning-rate group; `opt` is the base group's (the only one without lr_groups)
         self.optimizers, self.group_rows = build_optimizers(
             model, self.flat, self.table, optimizer=optimizer, lr=lr, momentum=momentum, dampening=dampening,
             weight_decay=weight_decay, nesterov=nesterov, lr_groups=lr_groups)
         self.opt = self.optimizers[0]
+        if self.clip is not None:
+            for o in self.optimizers:          # every group multiplies its gradients by the ONE coefficient
+                o.set_grad_multiplier(self.clip[1:2])
         # the checked step of several groups: each further group reads a copy of the overflow flag, the base group
         # (stepped last) reads, clears and counts the flag itself
         self._group_flags = (torch.zeros(len(self.optimizers) - 1, 2, dtype=torch.int32, device=self.dev)
@@ -816,9 +894,10 @@ class Trainer:
             for k, hm in enumerate((final_nchw, outs[1])):
                 eng.call('fami_pck_accuracy_f32', _p(hm), _p(target), _p(self.acc[k]), _p(iws), _p(mws), B, J, Hh, Wh,
                          0.5)
-        ls = self.loss_scale
+        # the loss scale of the seeds: a host factor, or (dynamic) the device scalar the scale update rewrites
+        ls, ls_dev = (1.0, self.scaler_state[0:1]) if self.dynamic_scale else (self.loss_scale, None)
         dpred = torch.empty_like(final_nchw)
-        eng.call('fami_wmse_bwd_f32', _p(final_nchw), _p(target), _p(w), _p(dpred), B * J, L, float(scale * ls), None, 0)
+        eng.call('fami_wmse_bwd_f32', _p(final_nchw), _p(target), _p(w), _p(dpred), B * J, L, float(scale * ls), _p(ls_dev), 0)
         eng.seed_nchw(aux['final'], dpred)
         if self.use_mi and aux['mis']:
             a, b = self.alpha, self.beta
@@ -834,7 +913,7 @@ class Trainer:
                     eng.set_lane(k % 3)
                 eng.call('fami_axpby_f32', _p(val), None, _p(self.loss_parts[1 + k:2 + k]), 1, 1.0, 0.0)
                 if k not in same:
-                    pending.append(seed(c * ls, None, True))
+                    pending.append(seed(c * ls, ls_dev, True))
             if eng.use_lanes:
                 eng._do_join(3)
             for fin in pending:        # the accumulations into the (shared) gradient buffers, in term order, on lane 0
@@ -879,8 +958,8 @@ class Trainer:
         pass completes.  Everything outside it is final when backward reaches the boundary of stage 2 (modules.HRNetBody.run marks
         it), so its Adam update can run on a side lane beside the rest of the backward pass instead of behind it (the one-launch
         Adam is 0.33 ms of pure HBM traffic at the end of every step).  None: no such split (fp16's checked step, data-parallel
-        plans, a frozen backbone)."""
-        if self.loss_scale != 1.0:
+        plans, a frozen backbone; gradient clipping, which needs the total norm before any update; a dynamic loss scale)."""
+        if self.loss_scale != 1.0 or self.dynamic_scale or self.max_grad_norm is not None:
             return None
         hr = getattr(model, 'hrnet', None)
         if hr is None or not hasattr(hr, 'stage2') or not hasattr(hr, 'conv1'):
@@ -910,8 +989,9 @@ class Trainer:
         self.opt.step(self.overflow)
 
     def _opt_tensors(self):
-        """the parameter arena and every optimizer's device state (shared arenas once)"""
-        out, seen = [self.flat], set()
+        """the parameter arena and every optimizer's device state (shared arenas once), with the loss-scaler vector and the
+        clip vector where they exist: what a capture's warm-up steps must not leave changed"""
+        out, seen = [self.flat] + [t for t in (self.scaler_state, self.clip) if t is not None], set()
         for o in self.optimizers:
             for t in o.tensors():
                 if id(t) not in seen:
@@ -920,16 +1000,79 @@ class Trainer:
         return out
 
     def _hyper_version(self):
-        return tuple(o.hyper_version for o in self.optimizers)
+        return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version,)
 
     def _unscale(self):
-        """gradient arena *= 1 / (world * loss_scale): the data-parallel mean and the static loss scale in one pass."""
+        """gradient arena *= 1 / (world * loss_scale): the data-parallel mean and the static loss scale in one pass.
+        With gradient clipping and / or a dynamic loss scale: the same pass reads 1 / scale from the device and leaves
+        the sum of squares of what it wrote (the standalone read-only reduction when there is nothing to multiply), then
+        the clip coefficient, then the scale update -- which must see the overflow flag before the optimizers' checked
+        prep clears it, once per step."""
+        if self.clip is not None or self.dynamic_scale:
+            return self._unscale_norm_update()
         f = 1.0 / ((self.world if self.ddp else 1) * self.loss_scale)
         if self.overflow is not None:
             # static loss scaling (fp16): the same pass also looks for inf / NaN; Adam then skips the step
             self._lc('fami_unscale_check_f32', _p(self.grad), self.grad.numel(), f, _p(self.overflow), _stream(self.dev))
         elif f != 1.0:
             self._lc('fami_axpby_f32', _p(self.grad), None, _p(self.grad), self.grad.numel(), f, 0.0, _stream(self.dev))
+
+    def _unscale_norm_update(self):
+        s, n = _stream(self.dev), self.grad.numel()
+        f = 1.0 / ((self.world if self.ddp else 1) * (1.0 if self.dynamic_scale else self.loss_scale))
+        if self.dynamic_scale or f != 1.0:
+            self._lc('fami_unscale_check_sumsq_f32', _p(self.grad), n, f, _p(self.scaler_state[1:2]) if self.dynamic_scale else None,
+                     _p(self.overflow), _p(self._partials), s)
+        else:
+            self._lc('fami_sumsq_f32', _p(self.grad), n, _p(self._partials), s)
+        if self.clip is not None:
+            self._lc('fami_clip_coef_f32', _p(self._partials), self._partials.numel(), _p(self.clip[2:3]), _p(self.clip[0:2]),
+                     _p(self.overflow), s)
+        if self.dynamic_scale:
+            c = self.scaler_cfg
+            self._lc('fami_loss_scale_update_f32', _p(self.scaler_state), _p(self.overflow), float(c['growth_factor']),
+                     float(c['backoff_factor']), int(c['growth_interval']), s)
+
+    def set_max_grad_norm(self, v):
+        """A new clip threshold, written into the device scalar the coefficient kernel reads: captured plans keep replaying
+        (like set_lr).  Clipping itself is switched on at construction."""
+        if self.clip is None:
+            raise ValueError('this Trainer was built without max_grad_norm')
+        if not float(v) > 0.0:
+            raise ValueError('max_grad_norm must be positive, not %r' % (v,))
+        self.max_grad_norm = float(v)
+        self.clip[2] = self.max_grad_norm
+
+    def grad_norm(self):
+        """Total 2-norm of the last step's gradients before clipping (host float; forces a sync -- logging only)."""
+        return None if self.clip is None else float(self.clip[0].item())
+
+    def clip_coef(self):
+        """The factor the last step's gradients were multiplied by, min(1, max_grad_norm / (norm + 1e-6)) (host float;
+        forces a sync -- logging only)."""
+        return None if self.clip is None else float(self.clip[1].item())
+
+    def loss_scale_value(self):
+        """The current loss scale (host float; with a dynamic scale it forces a sync -- logging only)."""
+        return float(self.scaler_state[0].item()) if self.dynamic_scale else self.loss_scale
+
+    def scaler_state_dict(self):
+        """torch.amp.GradScaler.state_dict() of the dynamic loss scale (synchronises)."""
+        scale, _, tracker = self.scaler_state.tolist()
+        c = self.scaler_cfg
+        return {'scale': scale, 'growth_factor': float(c['growth_factor']), 'backoff_factor': float(c['backoff_factor']),
+                'growth_interval': int(c['growth_interval']), '_growth_tracker': int(tracker)}
+
+    def load_scaler_state_dict(self, sd):
+        """The inverse.  Growth / backoff factor and interval are kernel arguments of the captured plan: a change re-captures."""
+        c = self.scaler_cfg
+        new = {'growth_factor': float(sd['growth_factor']), 'backoff_factor': float(sd['backoff_factor']),
+               'growth_interval': int(sd['growth_interval'])}
+        if any(c[k] != v for k, v in new.items()):
+            c.update(new)
+            self._scaler_version += 1
+        scale = float(sd['scale'])
+        self.scaler_state.copy_(torch.tensor([scale, 1.0 / scale, float(sd['_growth_tracker'])]))
 
     def _eager_step(self, kf_x, sup_x, target, weight):
         if self.ddp:

@@ -292,6 +292,33 @@ int fami_sgd_prep_f32(float* state3, fami_stream_t stream);
 int fami_sgd_prep_checked_f32(float* state3, unsigned* flag, fami_stream_t stream);
 int fami_sgd_f32(float* p, const float* g, float* buf, long n, const float* state3, float momentum, float dampening,
                  float weight_decay, int nesterov, fami_stream_t stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) and dynamic loss scaling
+ * (torch.amp.GradScaler), device-resident: no host sync, no re-capture of a hipGraph when the threshold or the scale moves.
+ * fami_sumsq_f32: the sum of squares of g[0..n) as fami_sumsq_parts() fp32 partial sums (every slot is written; one
+ *   fixed contiguous chunk per workgroup, no atomics: bitwise reproducible for a given (g, n, alignment of g)).
+ * fami_unscale_check_sumsq_f32: fami_unscale_check_f32 -- g *= f * (fdev ? fdev[0] : 1), *flag raised on inf / NaN --
+ *   that also leaves the sum of squares of the unscaled values in partials (may be NULL).
+ * fami_clip_coef_f32: clip (device float[2]) = {total_norm, coef}; the partials are summed in double in a fixed order,
+ *   coef = min(1, max_norm_dev[0] / (total_norm + 1e-6f)).  A non-finite norm raises flag[0] (coef = 0), so the checked
+ *   prep kernels skip and count the step like an fp16 overflow.  That differs from torch on purpose: clip_grad_norm_'s
+ *   default error_if_nonfinite=False lets a NaN norm through into every parameter.
+ * fami_adam_scaled_f32 / fami_sgd_scaled_f32: fami_adam_f32 / fami_sgd_f32 with the gradient gmul[0] * g on load (gmul:
+ *   device float, e.g. clip + 1); the gradient arena is not rewritten; gmul[0] == 1 gives the unscaled result bit for bit.
+ * fami_loss_scale_update_f32: scaler (device float[3]) = {scale, 1 / scale, growth tracker}; flag[0] raised: scale *=
+ *   backoff, tracker = 0; otherwise tracker += 1 and at `interval`: scale *= growth (refused when that is inf), tracker =
+ *   0.  It only reads the flag: enqueue it before the checked prep that clears it. */
+int fami_sumsq_parts(void);
+int fami_sumsq_f32(const float* g, long n, float* partials, fami_stream_t stream);
+int fami_unscale_check_sumsq_f32(float* g, long n, float f, const float* fdev, unsigned* flag, float* partials,
+                                 fami_stream_t stream);
+int fami_clip_coef_f32(const float* partials, int nparts, const float* max_norm_dev, float* clip, unsigned* flag,
+                       fami_stream_t stream);
+int fami_adam_scaled_f32(float* p, const float* g, float* m, float* v, long n, const float* state4, float beta1,
+                         float beta2, float eps, float weight_decay, const float* gmul, fami_stream_t stream);
+int fami_sgd_scaled_f32(float* p, const float* g, float* buf, long n, const float* state3, float momentum,
+                        float dampening, float weight_decay, int nesterov, const float* gmul, fami_stream_t stream);
+int fami_loss_scale_update_f32(float* scaler, const unsigned* flag, float growth, float backoff, int interval,
+                               fami_stream_t stream);
 
 /* ---- temporal alignment ----------------------------------------------------------------------
  * fami_shift_bilinear_*: kornia.geometry.warp_affine(src, [[1,0,tx],[0,1,ty]], dsize) at
