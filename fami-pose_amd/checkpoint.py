@@ -22,6 +22,12 @@ A Trainer with a dynamic loss scale (loss_scale='dynamic') adds one entry, ``'lo
 ``torch.amp.GradScaler.state_dict()`` (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker), and
 `resume` restores it; a checkpoint without the entry leaves a dynamic Trainer at its initial scale.  Without a dynamic
 scale the file has exactly the three keys above.  max_grad_norm is a hyper-parameter of the run, not state: not saved.
+
+A Trainer with gradient accumulation (accum_steps = N > 1) adds ``'grad_accum'``: ``{'steps': N, 'position': k}`` with k the
+micro-batches in the open window and, when k > 0, ``'arena'`` (the accumulation arena, host fp32) and ``'loss_sum'`` (the
+open window's seven loss parts), so a run saved inside a window continues bit for bit.  `resume` restores the entry into
+a Trainer with the same accum_steps and raises ValueError on any other; a checkpoint without the entry starts an
+accumulating Trainer at position 0.  Trainers without accumulation write today's keys exactly.
 """
 import os
 import os.path as osp
@@ -220,6 +226,9 @@ def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
     dyn = [o for o in opts if getattr(o, 'dynamic_scale', False)]
     if dyn:
         ckpt['loss_scaler'] = dyn[0].scaler_state_dict()
+    acc = [o for o in opts if getattr(o, 'accum_steps', 1) > 1]
+    if acc:
+        ckpt['grad_accum'] = acc[0].accum_state_dict()
     torch.save(ckpt, path)
     return path
 
@@ -227,6 +236,12 @@ def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
 def resume(model, optimizer, checkpoint_file, **kwargs):
     ckpt = torch.load(checkpoint_file, map_location='cpu')
     begin_epoch = ckpt['begin_epoch'] + 1
+    opts = optimizer if isinstance(optimizer, list) else [optimizer]
+    if 'grad_accum' in ckpt:          # checked before anything is loaded: a refused resume leaves model and trainer as they were
+        for o in opts:
+            if hasattr(o, 'table') and int(ckpt['grad_accum']['steps']) != getattr(o, 'accum_steps', 1):
+                raise ValueError('the checkpoint was written with accum_steps=%d, this Trainer has accum_steps=%d' %
+                                 (int(ckpt['grad_accum']['steps']), getattr(o, 'accum_steps', 1)))
     sd = _strip_module(ckpt['state_dict'])
     sd = {(k[7:] if k.startswith('preact.') else k): v for k, v in sd.items()}
     with torch.no_grad():
@@ -237,7 +252,6 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
             raise RuntimeError('state_dict mismatch: missing %s unexpected %s' % (missing[:5], extra[:5]))
         for k, v in sd.items():          # in place: parameters may be views into the trainer's flat arena
             own[k].copy_(v.to(own[k].device))
-    opts = optimizer if isinstance(optimizer, list) else [optimizer]
     osds = list(ckpt['optimizer'])
     for o in opts:
         if not osds:
@@ -250,4 +264,10 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
         for o in opts:
             if getattr(o, 'dynamic_scale', False):
                 o.load_scaler_state_dict(ckpt['loss_scaler'])
+    for o in opts:
+        if getattr(o, 'accum_steps', 1) > 1:
+            if 'grad_accum' in ckpt:
+                o.load_accum_state_dict(ckpt['grad_accum'])
+            else:
+                o.reset_window()
     return model, optimizer, begin_epoch

@@ -110,16 +110,39 @@ __global__ __launch_bounds__(256) void sgd_scaled_kernel(float* __restrict__ p, 
 // scalar rest (1), wave_sum (6), the four waves through LDS pairwise (2).  The longest chain of fp32 additions is therefore
 //   k = ceil(ceil(n4 / 2048) / 256) + 11      (42 at the 64 655 204 elements of the W48 arena)
 // and the relative error of the sum of non-negative squares at most (k + 1) 2^-24.  No atomics: the slab is a pure function of
-// (g, n, alignment).  RW: the unscale-and-check pass in front of it -- g *= f * (fdev ? fdev[0] : 1), *flag raised on inf /
+// (g, n, alignment).  SUMSQ_RW: the unscale-and-check pass in front of it -- g *= f * (fdev ? fdev[0] : 1), *flag raised on inf /
 // NaN, exactly what unscale_check_kernel leaves in the arena -- with the squares taken from the unscaled values on their way
-// back to memory (partials may then be null: no reduction).
+// back to memory (partials may then be null: no reduction).  SUMSQ_ACC: the pass that closes a gradient-accumulation window,
+// g = rn(rn(acc + g) * mul) with the same check and the same squares -- the layout is g's alone, so the slab is what SUMSQ_READ
+// gives on the arena this pass leaves; acc is only read, as 16-byte vectors where it shares g's alignment (AVEC) and as four
+// scalar loads per vector where it does not.
 constexpr int SUMSQ_PARTS = 2048;
+enum { SUMSQ_READ = 0, SUMSQ_RW = 1, SUMSQ_ACC = 2 };
 
-template <bool RW>
-__device__ __forceinline__ f32x4 sumsq_vec(float* __restrict__ a, float mul, bool& bad) {
+// rn(rn(a + g) * mul): an add feeding a multiply has no fused form, and none may appear -- both roundings spelled out
+__device__ __forceinline__ float accum_elem(float a, float g, float mul) {
+#pragma clang fp contract(off)
+  const float s = a + g;
+  return s * mul;
+}
+
+template <int MODE, bool AVEC>
+__device__ __forceinline__ f32x4 sumsq_vec(float* __restrict__ a, const float* __restrict__ c, float mul, bool& bad) {
   f32x4 v = ld4(a);
-  if (RW) {
-    v = v * mul;
+  if (MODE != SUMSQ_READ) {
+    if (MODE == SUMSQ_ACC) {
+      f32x4 w;
+      if (AVEC) {
+        w = ld4(c);
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w[t] = c[t];
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = accum_elem(w[t], v[t], mul);
+    } else {
+      v = v * mul;
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t) bad |= !(fabsf(v[t]) <= 3.4028235e38f);
     st4(a, v);
@@ -127,30 +150,31 @@ __device__ __forceinline__ f32x4 sumsq_vec(float* __restrict__ a, float mul, boo
   return v;
 }
 
-template <bool RW>
-__global__ __launch_bounds__(256) void sumsq_kernel(float* __restrict__ g, long n, long head, float f,
-                                                    const float* __restrict__ fdev, unsigned* __restrict__ flag,
+template <int MODE, bool AVEC>
+__global__ __launch_bounds__(256) void sumsq_kernel(float* __restrict__ g, const float* __restrict__ accum, long n, long head,
+                                                    float f, const float* __restrict__ fdev, unsigned* __restrict__ flag,
                                                     float* __restrict__ partials) {
-  const float mul = RW ? (fdev ? f * fdev[0] : f) : 1.f;
+  const float mul = MODE != SUMSQ_READ ? (fdev ? f * fdev[0] : f) : 1.f;
   const long n4 = (n - head) >> 2, tail = head + n4 * 4;
   const long chunk = (n4 + gridDim.x - 1) / gridDim.x;
   const long lo = blockIdx.x * chunk, hi = lo + chunk < n4 ? lo + chunk : n4;
   float* __restrict__ body = g + head;
+  const float* __restrict__ abody = MODE == SUMSQ_ACC ? accum + head : nullptr;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   bool bad = false;
   long i = lo + threadIdx.x;
   for (; i + 3 * 256 < hi; i += 4 * 256) {       // four 16-byte loads in flight per lane; summed in address order
-    const f32x4 v0 = sumsq_vec<RW>(body + i * 4, mul, bad);
-    const f32x4 v1 = sumsq_vec<RW>(body + (i + 256) * 4, mul, bad);
-    const f32x4 v2 = sumsq_vec<RW>(body + (i + 512) * 4, mul, bad);
-    const f32x4 v3 = sumsq_vec<RW>(body + (i + 768) * 4, mul, bad);
+    const f32x4 v0 = sumsq_vec<MODE, AVEC>(body + i * 4, abody + i * 4, mul, bad);
+    const f32x4 v1 = sumsq_vec<MODE, AVEC>(body + (i + 256) * 4, abody + (i + 256) * 4, mul, bad);
+    const f32x4 v2 = sumsq_vec<MODE, AVEC>(body + (i + 512) * 4, abody + (i + 512) * 4, mul, bad);
+    const f32x4 v3 = sumsq_vec<MODE, AVEC>(body + (i + 768) * 4, abody + (i + 768) * 4, mul, bad);
     acc += v0 * v0;
     acc += v1 * v1;
     acc += v2 * v2;
     acc += v3 * v3;
   }
   for (; i < hi; i += 256) {
-    const f32x4 v = sumsq_vec<RW>(body + i * 4, mul, bad);
+    const f32x4 v = sumsq_vec<MODE, AVEC>(body + i * 4, abody + i * 4, mul, bad);
     acc += v * v;
   }
   float rest = 0.f;
@@ -158,14 +182,17 @@ __global__ __launch_bounds__(256) void sumsq_kernel(float* __restrict__ g, long 
   if (blockIdx.x == 0 && threadIdx.x < nrest) {
     const long j = threadIdx.x < head ? threadIdx.x : tail + (threadIdx.x - head);
     float v = g[j];
-    if (RW) {
-      v *= mul;
+    if (MODE != SUMSQ_READ) {
+      if (MODE == SUMSQ_ACC)
+        v = accum_elem(accum[j], v, mul);
+      else
+        v *= mul;
       bad |= !(fabsf(v) <= 3.4028235e38f);
       g[j] = v;
     }
     rest = v * v;
   }
-  if (RW && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+  if (MODE != SUMSQ_READ && flag && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
   if (!partials) return;
   float s = wave_sum(((acc[0] + acc[1]) + (acc[2] + acc[3])) + rest);
   __shared__ float red[4];
@@ -297,16 +324,34 @@ static long sumsq_head(const float* g, long n) {
 // partials (device float[fami_sumsq_parts()]): every slot is written; their sum is sum_i g[i]^2
 int fami_sumsq_f32(const float* g, long n, float* partials, hipStream_t s) {
   FAMI_REQUIRE(g && partials && n > 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0, "fami_sumsq_f32", "bad argument");
-  hipLaunchKernelGGL(sumsq_kernel<false>, dim3(SUMSQ_PARTS), dim3(256), 0, s, const_cast<float*>(g), n, sumsq_head(g, n), 1.f,
-                     (const float*)nullptr, (unsigned*)nullptr, partials);
+  hipLaunchKernelGGL((sumsq_kernel<SUMSQ_READ, true>), dim3(SUMSQ_PARTS), dim3(256), 0, s, const_cast<float*>(g),
+                     (const float*)nullptr, n, sumsq_head(g, n), 1.f, (const float*)nullptr, (unsigned*)nullptr, partials);
   FAMI_CHECK_LAUNCH("fami_sumsq_f32");
   return FAMI_OK;
 }
 // fami_unscale_check_f32 with an optional device factor (fdev) and the sum of squares of the unscaled values (partials; may be null)
 int fami_unscale_check_sumsq_f32(float* g, long n, float f, const float* fdev, unsigned* flag, float* partials, hipStream_t s) {
   FAMI_REQUIRE(g && flag && n > 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0, "fami_unscale_check_sumsq_f32", "bad argument");
-  hipLaunchKernelGGL(sumsq_kernel<true>, dim3(SUMSQ_PARTS), dim3(256), 0, s, g, n, sumsq_head(g, n), f, fdev, flag, partials);
+  hipLaunchKernelGGL((sumsq_kernel<SUMSQ_RW, true>), dim3(SUMSQ_PARTS), dim3(256), 0, s, g, (const float*)nullptr, n,
+                     sumsq_head(g, n), f, fdev, flag, partials);
   FAMI_CHECK_LAUNCH("fami_unscale_check_sumsq_f32");
+  return FAMI_OK;
+}
+// the closing pass of a gradient-accumulation window: g = (acc + g) * f * (fdev ? fdev[0] : 1), each operation rounded once;
+// flag (may be null: no check) raised on inf / NaN in what was written, partials (may be null) = fami_sumsq_f32 of the result
+int fami_accum_unscale_check_sumsq_f32(float* g, const float* acc, long n, float f, const float* fdev, unsigned* flag,
+                                       float* partials, hipStream_t s) {
+  FAMI_REQUIRE(g && acc && n > 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(acc)) & 3) == 0,
+               "fami_accum_unscale_check_sumsq_f32", "bad argument");
+  // the work layout is g's (the slab must be fami_sumsq_f32's on the result); acc is read as vectors only where it shares g's
+  // alignment, which is sgd_head's decision
+  const long head = sumsq_head(g, n);
+  const bool avec = sgd_head(g, acc, nullptr, n, false) == head;
+  if (avec)
+    hipLaunchKernelGGL((sumsq_kernel<SUMSQ_ACC, true>), dim3(SUMSQ_PARTS), dim3(256), 0, s, g, acc, n, head, f, fdev, flag, partials);
+  else
+    hipLaunchKernelGGL((sumsq_kernel<SUMSQ_ACC, false>), dim3(SUMSQ_PARTS), dim3(256), 0, s, g, acc, n, head, f, fdev, flag, partials);
+  FAMI_CHECK_LAUNCH("fami_accum_unscale_check_sumsq_f32");
   return FAMI_OK;
 }
 int fami_clip_coef_f32(const float* partials, int nparts, const float* max_norm_dev, float* clip, unsigned* flag, hipStream_t s) {

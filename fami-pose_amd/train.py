@@ -610,17 +610,40 @@ class Trainer:
     The threshold is a device scalar (set_max_grad_norm): no re-capture.  The total norm has to exist before the first
     update, so the in-backward optimizer split (_find_adam_split) is off while clipping -- or a dynamic scale -- is on,
     as it is for the checked fp16 step.
+
+    accum_steps = N > 1: gradient accumulation.  step() is called once per micro-batch and runs forward, loss, PCK and
+    backward exactly as without it (BatchNorm batch statistics, running statistics and batch counters are per micro-batch,
+    the seeds are unchanged); N calls make one window and one update.  A second fp32 arena holds the running sum: a call
+    at window position k < N - 1 only copies (k = 0) or adds (fami_axpby_f32, alpha = beta = 1) the gradient arena into
+    it -- no unscale, no norm, no scale update, no optimizer, no all-reduce.  The call at position N - 1 closes the
+    window with ONE pass over both arenas, grad = (accum + grad) * 1 / (N * loss_scale)
+    (fami_accum_unscale_check_sumsq_f32: also the inf / NaN check and the sum of squares where the trainer is guarded /
+    clips), then the clip coefficient, the scale update and the optimizers as above: `grad` then holds the window's mean
+    gradient before clipping, a non-finite value in any micro-batch skips (and counts) the window once, and a dynamic
+    scale moves once per window.  Graph mode replays the one captured forward + backward graph of the batch shape at
+    every window position and one shape-independent captured tail at the last; the accumulating launches are enqueued
+    behind the replay, so a window position never captures.  Data parallel: micro-batches before the last run without
+    communication and without bucket hooks; at the last one grad = accum + grad, then the bucketed all-reduce of the
+    arena, then the unscale pass with 1 / N folded into its factor, then the optimizers -- for all three plans (overlap,
+    serial, eager hooks): the exchange already happens once per N backward passes, and its overlap with the last
+    backward pass is deliberately not kept.  The in-backward optimizer split is off.  None and 1: no arena, the launch
+    sequence above launch for launch.  Windows always hold N micro-batches and may span epochs (reset_window() drops an
+    open one); set_lr / set_max_grad_norm inside a window act at its update.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
-                 weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None):
+                 weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
         from a reference config.  max_grad_norm / loss_scale='dynamic' / scaler: see the class docstring (the reference
-        configuration has no such keys: from_cfg takes them as keyword arguments)."""
+        configuration has no such keys: from_cfg takes them as keyword arguments).  accum_steps: micro-batches per update
+        (class docstring; None = 1)."""
+        if accum_steps is not None and (isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1):
+            raise ValueError('accum_steps is None or an integer >= 1, not %r' % (accum_steps,))
+        self.accum_steps = 1 if accum_steps is None else accum_steps
         self.model = model
         self.route = getattr(model, 'route', None)      # kernel-routing state (None: process default), as the model's engines
         self.targets_from_joints, self.sigma = targets_from_joints, sigma
@@ -681,6 +704,14 @@ class Trainer:
         self._group_flags = (torch.zeros(len(self.optimizers) - 1, 2, dtype=torch.int32, device=self.dev)
                              if self.overflow is not None and len(self.optimizers) > 1 else None)
         self.grad = self.opt.grad
+        # gradient accumulation: the running sum of the open window, {open window, last closed window} x the seven loss
+        # parts summed over their calls, and the host-side position (micro-batches in the open window)
+        self.accum = self._window_loss = None
+        self.window_position = 0
+        self._tail = None         # (graph of the window-closing tail, optimizer hyper version): one for every batch shape
+        if self.accum_steps > 1:
+            self.accum = torch.zeros_like(self.grad)
+            self._window_loss = torch.zeros(2, 7, device=self.dev)
         self._adam_split = self._find_adam_split(model)
         self._adam_done = False
         self.views = {id(p): self.grad[o:o + n].view(p.shape) for p, o, n in self.table}
@@ -958,8 +989,9 @@ class Trainer:
         pass completes.  Everything outside it is final when backward reaches the boundary of stage 2 (modules.HRNetBody.run marks
         it), so its Adam update can run on a side lane beside the rest of the backward pass instead of behind it (the one-launch
         Adam is 0.33 ms of pure HBM traffic at the end of every step).  None: no such split (fp16's checked step, data-parallel
-        plans, a frozen backbone; gradient clipping, which needs the total norm before any update; a dynamic loss scale)."""
-        if self.loss_scale != 1.0 or self.dynamic_scale or self.max_grad_norm is not None:
+        plans, a frozen backbone; gradient clipping, which needs the total norm before any update; a dynamic loss scale; gradient
+        accumulation, whose update follows the last backward pass of a window)."""
+        if self.loss_scale != 1.0 or self.dynamic_scale or self.max_grad_norm is not None or self.accum_steps > 1:
             return None
         hr = getattr(model, 'hrnet', None)
         if hr is None or not hasattr(hr, 'stage2') or not hasattr(hr, 'conv1'):
@@ -1010,7 +1042,7 @@ class Trainer:
         prep clears it, once per step."""
         if self.clip is not None or self.dynamic_scale:
             return self._unscale_norm_update()
-        f = 1.0 / ((self.world if self.ddp else 1) * self.loss_scale)
+        f = 1.0 / ((self.world if self.ddp else 1) * self.accum_steps * self.loss_scale)
         if self.overflow is not None:
             # static loss scaling (fp16): the same pass also looks for inf / NaN; Adam then skips the step
             self._lc('fami_unscale_check_f32', _p(self.grad), self.grad.numel(), f, _p(self.overflow), _stream(self.dev))
@@ -1019,12 +1051,17 @@ class Trainer:
 
     def _unscale_norm_update(self):
         s, n = _stream(self.dev), self.grad.numel()
-        f = 1.0 / ((self.world if self.ddp else 1) * (1.0 if self.dynamic_scale else self.loss_scale))
+        f = 1.0 / ((self.world if self.ddp else 1) * self.accum_steps * (1.0 if self.dynamic_scale else self.loss_scale))
         if self.dynamic_scale or f != 1.0:
             self._lc('fami_unscale_check_sumsq_f32', _p(self.grad), n, f, _p(self.scaler_state[1:2]) if self.dynamic_scale else None,
                      _p(self.overflow), _p(self._partials), s)
         else:
             self._lc('fami_sumsq_f32', _p(self.grad), n, _p(self._partials), s)
+        self._coef_and_scale_update(s)
+
+    def _coef_and_scale_update(self, s):
+        """the clip coefficient from the slab, then the loss-scale update: both read the overflow flag the pass in front of them
+        raised, before the optimizers' checked prep clears it"""
         if self.clip is not None:
             self._lc('fami_clip_coef_f32', _p(self._partials), self._partials.numel(), _p(self.clip[2:3]), _p(self.clip[0:2]),
                      _p(self.overflow), s)
@@ -1074,7 +1111,95 @@ class Trainer:
         scale = float(sd['scale'])
         self.scaler_state.copy_(torch.tensor([scale, 1.0 / scale, float(sd['_growth_tracker'])]))
 
+    # ------------------------------------------------------------------ gradient accumulation (accum_steps > 1)
+    def _accumulate(self):
+        """window position k < N - 1, behind the backward pass: accum = grad (k = 0) or accum = accum + grad"""
+        self._lc('fami_axpby_f32', _p(self.grad), _p(self.accum) if self.window_position else None, _p(self.accum),
+                 self.grad.numel(), 1.0, 1.0, _stream(self.dev))
+
+    def _close_window(self):
+        """the tail of a window's last call, single process: grad = (accum + grad) / (N * loss scale) with the check and the
+        slab in the same pass, then what _unscale_norm_update and _step_optimizers enqueue"""
+        s = _stream(self.dev)
+        f = 1.0 / (self.accum_steps * (1.0 if self.dynamic_scale else self.loss_scale))
+        self._lc('fami_accum_unscale_check_sumsq_f32', _p(self.grad), _p(self.accum), self.grad.numel(), f,
+                 _p(self.scaler_state[1:2]) if self.dynamic_scale else None, _p(self.overflow),
+                 _p(self._partials) if self.clip is not None else None, s)
+        self._coef_and_scale_update(s)
+        self._step_optimizers()
+
+    def _exchange_window(self):
+        """data parallel, a window's last call: grad = accum + grad, then every bucket's all-reduce (outside any graph)"""
+        self._lc('fami_axpby_f32', _p(self.accum), _p(self.grad), _p(self.grad), self.grad.numel(), 1.0, 1.0, _stream(self.dev))
+        for lo, hi in self.reducer.ranges():
+            self.reducer.allreduce(lo, hi)
+        self.reducer.wait()
+
+    def _ddp_tail(self):
+        """... and behind the exchange: the existing unscale path (1 / (world * N * loss scale)) and the optimizers"""
+        self._unscale()
+        self._step_optimizers()
+
+    def _window_call_done(self, closing):
+        """the loss parts of this call into the window sum (one 7-element launch; row 0: the open window, row 1: the last
+        closed one) and the host-side position"""
+        w = self._window_loss
+        self._lc('fami_axpby_f32', _p(self.loss_parts), _p(w[0]) if self.window_position else None, _p(w[1 if closing else 0]),
+                 7, 1.0, 1.0, _stream(self.dev))
+        self.window_position = 0 if closing else self.window_position + 1
+
+    def reset_window(self):
+        """Drop an open window: the next call is position 0 (which overwrites the accumulation arena; no launch here)."""
+        self.window_position = 0
+
+    def window_loss_value(self):
+        """Mean over the last closed window of what loss_value() reports per call (host float; forces a sync -- logging
+        only).  None without accumulation."""
+        if self._window_loss is None:
+            return None
+        p = (self._window_loss[1] / self.accum_steps).tolist()
+        a, b = self.alpha, self.beta
+        mi = a * (-b * p[1] + b * p[2] + p[3] - p[4] + p[5] - p[6]) if self.use_mi else 0.0
+        return p[0] + mi
+
+    def accum_state_dict(self):
+        """The 'grad_accum' checkpoint entry: {'steps': N, 'position': k} and, inside a window (k > 0), the accumulation
+        arena and the open window's loss sum on the host (synchronises)."""
+        sd = {'steps': self.accum_steps, 'position': self.window_position}
+        if self.window_position > 0:
+            sd['arena'] = self.accum.detach().cpu().clone()
+            sd['loss_sum'] = self._window_loss[0].detach().cpu().clone()
+        return sd
+
+    def load_accum_state_dict(self, sd):
+        """The inverse, into a Trainer with the same accum_steps (ValueError otherwise)."""
+        if int(sd['steps']) != self.accum_steps:
+            raise ValueError('the checkpoint was written with accum_steps=%d, this Trainer has accum_steps=%d' %
+                             (int(sd['steps']), self.accum_steps))
+        k = int(sd['position'])
+        if not 0 <= k < self.accum_steps:
+            raise ValueError('window position %d outside a window of %d micro-batches' % (k, self.accum_steps))
+        if k > 0:
+            self.accum.copy_(sd['arena'])
+            self._window_loss[0].copy_(sd['loss_sum'])
+        self.window_position = k
+
+    def _accum_eager_step(self, kf_x, sup_x, target, weight):
+        closing = self.window_position == self.accum_steps - 1
+        outs = self._forward_backward(kf_x, sup_x, target, weight)
+        if not closing:
+            self._accumulate()
+        elif self.ddp:
+            self._exchange_window()
+            self._ddp_tail()
+        else:
+            self._close_window()
+        self._window_call_done(closing)
+        return outs
+
     def _eager_step(self, kf_x, sup_x, target, weight):
+        if self.accum_steps > 1:
+            return self._accum_eager_step(kf_x, sup_x, target, weight)
         if self.ddp:
             outs = self._forward_backward(kf_x, sup_x, target, weight, on_bucket=self.reducer.allreduce)
             self.reducer.wait()
@@ -1101,6 +1226,8 @@ class Trainer:
 
     def _capture_plan(self, kf_x, sup_x, target, weight):
         st = {'kf': kf_x.clone(), 'sup': sup_x.clone(), 'target': target.clone(), 'weight': weight.clone()}
+        if self.accum_steps > 1:
+            return self._capture_accum_plan(st)
         # warm-up on a side stream (allocator + pack caches).  The warm-up steps must not count as training steps: the
         # parameters, Adam state and module buffers (BN running statistics, batch counters) are restored afterwards, so
         # the first step() of a graph-mode Trainer is exactly one optimisation step, like the eager one.
@@ -1149,6 +1276,56 @@ class Trainer:
             outs, plan = self._capture_overlap(st)
         entry = (plan, st, outs, self._hyper_version())
         return entry
+
+    def _capture_accum_plan(self, st):
+        """accum_steps > 1: ONE graph of forward + loss + backward for this batch shape, replayed at every window position (the
+        accumulating launches and the exchange follow the replay, uncaptured), and the shape-independent tail
+        (_capture_tail), captured the first time any shape is.  The warm-up runs the gradient computation alone: it never
+        touches the accumulation arena, the window position or the window loss sum, so a shape first seen in the middle of
+        a window (the smaller last batch of an epoch) leaves the open window as it was; module buffers (BN running
+        statistics, batch counters) are restored, and the gradient arena is rewritten by the replay that follows."""
+        bufs = [(b, b.clone()) for b in self.model.buffers()]
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'])
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        for b, src in bufs:
+            b.copy_(src)
+        torch.cuda.synchronize(self.dev)
+        # (thread_local: RCCL's watchdog thread may query events while this thread captures)
+        kw = {'capture_error_mode': 'thread_local'} if self.ddp else {}
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, **kw):
+            outs = self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'])
+        if self._tail is None or self._tail[1] != self._hyper_version():
+            self._tail = (self._capture_tail(kw), self._hyper_version())
+        return ([('graph', g)], st, outs, self._hyper_version())
+
+    def _capture_tail(self, kw):
+        """The graph a window's last call replays behind its backward pass (and, data parallel, behind the exchange): the
+        closing pass, coefficient, scale update and optimizers.  Its one warm-up run is rolled back (parameters, optimizer
+        state, scaler and clip vectors, overflow flag and count); it only reads the accumulation arena."""
+        tail = self._ddp_tail if self.ddp else self._close_window
+        snap = [t.clone() for t in self._opt_tensors()]
+        ovf = None if self.overflow is None else self.overflow.clone()
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            tail()
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        for dst, src in zip(self._opt_tensors(), snap):
+            dst.copy_(src)
+        if ovf is not None:
+            self.overflow.copy_(ovf)
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, **kw):
+            tail()
+        return g
 
     def _capture_overlap(self, st):
         """Data-parallel plan with graph replay AND overlap: the launch sequence of forward + backward is captured into
@@ -1205,7 +1382,8 @@ class Trainer:
     def step(self, kf_x, sup_x, target, weight):
         """-> (final_hm, kf_bb_hm, ...) of this step; self.loss_parts holds [mse*W, mi_1..mi_6] on device, self.acc
         the PCK rows.  Graph mode keeps one captured plan per batch shape: the DataLoader of the reference has no
-        drop_last, so the last batch of an epoch is usually smaller (datasets/zoo/build.py:32-50)."""
+        drop_last, so the last batch of an epoch is usually smaller (datasets/zoo/build.py:32-50).  With accum_steps = N > 1
+        a call is one micro-batch; the N-th of a window updates the parameters (class docstring)."""
         weight = weight.reshape(weight.shape[0], -1).float().contiguous()
         target = target.float().contiguous()
         if not (kf_x.shape[0] == sup_x.shape[0] == target.shape[0] == weight.shape[0]):
@@ -1222,6 +1400,17 @@ class Trainer:
         st['sup'].copy_(sup_x, non_blocking=True)
         st['target'].copy_(target, non_blocking=True)
         st['weight'].copy_(weight, non_blocking=True)
+        if self.accum_steps > 1:
+            closing = self.window_position == self.accum_steps - 1
+            plan[0][1].replay()
+            if not closing:
+                self._accumulate()
+            else:
+                if self.ddp:
+                    self._exchange_window()
+                self._tail[0].replay()
+            self._window_call_done(closing)
+            return outs
         for kind, obj in plan:
             if kind == 'graph':
                 obj.replay()

@@ -298,6 +298,10 @@ int fami_sgd_f32(float* p, const float* g, float* buf, long n, const float* stat
  *   fixed contiguous chunk per workgroup, no atomics: bitwise reproducible for a given (g, n, alignment of g)).
  * fami_unscale_check_sumsq_f32: fami_unscale_check_f32 -- g *= f * (fdev ? fdev[0] : 1), *flag raised on inf / NaN --
  *   that also leaves the sum of squares of the unscaled values in partials (may be NULL).
+ * fami_accum_unscale_check_sumsq_f32: the pass that closes a gradient-accumulation window, g[i] = rn(rn(acc[i] + g[i]) * mul)
+ *   with mul formed as above; acc is only read; flag (may be NULL: no check) is raised on inf / NaN in what was written;
+ *   partials (may be NULL) is bit for bit what fami_sumsq_f32 returns on the g this pass leaves.  One launch instead of
+ *   fami_axpby_f32(acc, g, g, 1, 1) + fami_unscale_check_sumsq_f32, with the same result in the arena, the slab and the flag.
  * fami_clip_coef_f32: clip (device float[2]) = {total_norm, coef}; the partials are summed in double in a fixed order,
  *   coef = min(1, max_norm_dev[0] / (total_norm + 1e-6f)).  A non-finite norm raises flag[0] (coef = 0), so the checked
  *   prep kernels skip and count the step like an fp16 overflow.  That differs from torch on purpose: clip_grad_norm_'s
@@ -311,6 +315,8 @@ int fami_sumsq_parts(void);
 int fami_sumsq_f32(const float* g, long n, float* partials, fami_stream_t stream);
 int fami_unscale_check_sumsq_f32(float* g, long n, float f, const float* fdev, unsigned* flag, float* partials,
                                  fami_stream_t stream);
+int fami_accum_unscale_check_sumsq_f32(float* g, const float* acc, long n, float f, const float* fdev, unsigned* flag,
+                                       float* partials, fami_stream_t stream);
 int fami_clip_coef_f32(const float* partials, int nparts, const float* max_norm_dev, float* clip, unsigned* flag,
                        fami_stream_t stream);
 int fami_adam_scaled_f32(float* p, const float* g, float* m, float* v, long n, const float* state4, float beta1,
