@@ -28,6 +28,15 @@ micro-batches in the open window and, when k > 0, ``'arena'`` (the accumulation 
 open window's seven loss parts), so a run saved inside a window continues bit for bit.  `resume` restores the entry into
 a Trainer with the same accum_steps and raises ValueError on any other; a checkpoint without the entry starts an
 accumulating Trainer at position 0.  Trainers without accumulation write today's keys exactly.
+
+A Trainer with a moving average of the weights (ema_decay) adds ``'ema'``: ``{'decay', 'warmup', 'updates', 'params': {name:
+host fp32 tensor}}`` with `name` the ``state_dict`` key of each trainable parameter (Trainer.ema_state_dict), so
+``{**ckpt['state_dict'], **ckpt['ema']['params']}`` is a state_dict of the averaged model -- for a model of this repository
+or of the reference.  BatchNorm buffers are not averaged: that dict takes them from ``'state_dict'``.  `resume` restores the
+entry into an EMA Trainer; a parameter name or shape that does not match raises ValueError before anything is loaded.  An
+EMA Trainer resuming a file without the entry restarts its average from the loaded weights (reset_ema: `resume` copies into
+the parameters in place, so the average taken at construction would be stale).  A Trainer without an EMA ignores the entry
+and writes exactly the keys above.
 """
 import os
 import os.path as osp
@@ -215,10 +224,12 @@ def load_optimizer_state_dicts(trainer, sds):
 def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
     """`optimizer`: a train.Trainer (flat Adam / SGD, one state dict per learning-rate group) or any torch optimizer /
     list of them (reference signature)."""
+    opts = optimizer if isinstance(optimizer, list) else [optimizer]
+    if any(getattr(o, '_ema_swapped', False) for o in opts):
+        raise RuntimeError('save_checkpoint inside ema_weights(): the model holds the averaged weights')
     os.makedirs(save_folder, exist_ok=True)
     path = osp.join(save_folder, 'epoch_{}_state.pth'.format(epoch))
     sd = {k: v.detach().cpu() for k, v in _strip_module(model.state_dict()).items()}
-    opts = optimizer if isinstance(optimizer, list) else [optimizer]
     osd = []
     for o in opts:
         osd.extend(optimizer_state_dicts(o) if hasattr(o, 'table') else [o.state_dict()])
@@ -229,6 +240,9 @@ def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
     acc = [o for o in opts if getattr(o, 'accum_steps', 1) > 1]
     if acc:
         ckpt['grad_accum'] = acc[0].accum_state_dict()
+    ema = [o for o in opts if getattr(o, 'ema', None) is not None]
+    if ema:
+        ckpt['ema'] = ema[0].ema_state_dict()
     torch.save(ckpt, path)
     return path
 
@@ -242,6 +256,10 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
             if hasattr(o, 'table') and int(ckpt['grad_accum']['steps']) != getattr(o, 'accum_steps', 1):
                 raise ValueError('the checkpoint was written with accum_steps=%d, this Trainer has accum_steps=%d' %
                                  (int(ckpt['grad_accum']['steps']), getattr(o, 'accum_steps', 1)))
+    if 'ema' in ckpt:                 # likewise: names and shapes are checked before the model is touched
+        for o in opts:
+            if getattr(o, 'ema', None) is not None:
+                o.check_ema_state_dict(ckpt['ema'])
     sd = _strip_module(ckpt['state_dict'])
     sd = {(k[7:] if k.startswith('preact.') else k): v for k, v in sd.items()}
     with torch.no_grad():
@@ -270,4 +288,10 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
                 o.load_accum_state_dict(ckpt['grad_accum'])
             else:
                 o.reset_window()
+    for o in opts:
+        if getattr(o, 'ema', None) is not None:
+            if 'ema' in ckpt:
+                o.load_ema_state_dict(ckpt['ema'])
+            else:
+                o.reset_ema()          # the parameters were just overwritten in place: the average restarts from them
     return model, optimizer, begin_epoch

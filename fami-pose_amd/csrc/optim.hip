@@ -13,6 +13,11 @@
 // run), alone or fused into the unscale-and-check pass; clip_coef_kernel turns the slab into {total_norm, coef}
 // (torch.nn.utils.clip_grad_norm_, norm_type 2); the *_scaled optimizer entry points multiply the gradient by a device
 // scalar on load instead of rewriting the arena; loss_scale_update_kernel is torch.amp.GradScaler's update rule.
+//
+// The exponential moving average of the parameter arena, device-resident: ema_prep_kernel keeps {updates, decay_t, 1 - decay_t,
+// apply} in a device vector and reads the optimizer's "this step was applied" scalar, so a skipped step leaves the average alone
+// without a host read-back and a captured hipGraph keeps replaying; ema_update_kernel is one pass over both arenas (12 bytes per
+// element); swap_kernel exchanges two arenas in place (the averaged weights into the model and out again).
 #include "common.h"
 
 // state = {step, lr, apply}
@@ -254,6 +259,145 @@ __global__ void loss_scale_update_kernel(float* __restrict__ scaler, const unsig
   }
 }
 
+// ---- the exponential moving average of a parameter arena -----------------------------------------------------------------
+// st = {updates, decay_t, w = 1 - decay_t, apply}.  gate (optional): the scalar the optimizer's prep leaves -- state[2] of
+// adam_prep_kernel (the first bias correction, 0 on a skipped step) and of sgd_prep_kernel (apply).  A skipped step only
+// clears `apply`: the update count, and with it the warm-up schedule, does not advance.  warmup: the usual
+// min(decay, (1 + t) / (10 + t)) ramp, t the update being made (1, 2, ...).
+__global__ void ema_prep_kernel(float* st, const float* gate, float decay, int warmup) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+#pragma clang fp contract(off)
+    if (gate && gate[0] == 0.f) {
+      st[3] = 0.f;
+      return;
+    }
+    const float t = st[0] + 1.f;
+    const float d = warmup ? fminf(decay, (1.f + t) / (10.f + t)) : decay;
+    st[0] = t;
+    st[1] = d;
+    st[2] = 1.f - d;
+    st[3] = 1.f;
+  }
+}
+
+// rn(e + rn(w * rn(p - e))): three roundings, no fused multiply-add -- three fp32 torch operations give the same bits
+__device__ __forceinline__ float ema_elem(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float s = w * d;
+  return e + s;
+}
+
+// the second array of a two-arena pass: 16-byte accesses where it shares the first one's alignment (BVEC), four scalar
+// ones per vector where it does not (sumsq_vec's AVEC split).  NT: a non-temporal load, for an arena this pass reads once --
+// measured on the W48 arenas, the update pass with cold caches: 165 -> 140 us (the store side gains nothing from the hint)
+template <bool BVEC, bool NT>
+__device__ __forceinline__ f32x4 ld4_as(const float* b) {
+  if (BVEC) return NT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(b)) : ld4(b);
+  f32x4 v;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) v[t] = NT ? __builtin_nontemporal_load(b + t) : b[t];
+  return v;
+}
+template <bool BVEC>
+__device__ __forceinline__ void st4_as(float* b, f32x4 v) {
+  if (BVEC) {
+    st4(b, v);
+    return;
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) b[t] = v[t];
+}
+
+// The work layout of both passes is the first array's.  head: its elements in front of the first 16-byte boundary (sumsq_head).
+// The aligned body is cut into tiles of TWO_U x 256 consecutive vectors (16 KB of each arena); a chip-sized grid strides the
+// tiles, every lane with TWO_U vectors of each arena in flight, 256 vectors apart.  (Measured against a plain grid-stride loop,
+// against the same loop with four vectors a whole grid apart in flight, and against sumsq_kernel's one-chunk-per-workgroup layout:
+// the tiles are the fastest, the vectors-a-grid-apart form the slowest, 12 % behind.)  The workgroup that meets the last, partial
+// tile walks it one vector per lane; workgroup 0 takes the <= 3 + 3 scalar head / tail elements, one per lane.
+constexpr int TWO_U = 4;
+static inline int two_arena_grid(long n) { return fami_ew_grid((n / 4 + TWO_U - 1) / TWO_U); }
+
+template <bool PVEC>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, long head,
+                                                         const float* __restrict__ st) {
+  if (st[3] == 0.f) return;      // skipped step (see ema_prep_kernel)
+  const float w = st[2];
+  const long n4 = (n - head) >> 2, tail = head + n4 * 4;
+  float* __restrict__ eb = ema + head;
+  const float* __restrict__ pb = p + head;
+  const long tile = (long)TWO_U * 256, stride = (long)gridDim.x * tile;
+  long base = blockIdx.x * tile;
+  for (; base + tile <= n4; base += stride) {
+    const long i = base + threadIdx.x;
+    f32x4 e[TWO_U], q[TWO_U];
+#pragma unroll
+    for (int u = 0; u < TWO_U; ++u) {
+      e[u] = ld4(eb + (i + u * 256) * 4);
+      q[u] = ld4_as<PVEC, true>(pb + (i + u * 256) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < TWO_U; ++u) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) e[u][t] = ema_elem(e[u][t], q[u][t], w);
+      st4(eb + (i + u * 256) * 4, e[u]);
+    }
+  }
+  if (base < n4) {               // the last, partial tile: [base, n4)
+    for (long i = base + threadIdx.x; i < n4; i += 256) {
+      f32x4 e = ld4(eb + i * 4);
+      const f32x4 q = ld4_as<PVEC, true>(pb + i * 4);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) e[t] = ema_elem(e[t], q[t], w);
+      st4(eb + i * 4, e);
+    }
+  }
+  const long nrest = head + (n - tail);          // <= 6: [0, head) and [tail, n)
+  if (blockIdx.x == 0 && threadIdx.x < nrest) {
+    const long j = threadIdx.x < head ? threadIdx.x : tail + (threadIdx.x - head);
+    ema[j] = ema_elem(ema[j], p[j], w);
+  }
+}
+
+// a <-> b in one pass, no temporary: every lane holds what it is about to overwrite in registers
+template <bool BVEC>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n, long head) {
+  const long n4 = (n - head) >> 2, tail = head + n4 * 4;
+  float* __restrict__ ab = a + head;
+  float* __restrict__ bb = b + head;
+  const long tile = (long)TWO_U * 256, stride = (long)gridDim.x * tile;
+  long base = blockIdx.x * tile;
+  for (; base + tile <= n4; base += stride) {
+    const long i = base + threadIdx.x;
+    f32x4 x[TWO_U], y[TWO_U];
+#pragma unroll
+    for (int u = 0; u < TWO_U; ++u) {
+      x[u] = ld4(ab + (i + u * 256) * 4);
+      y[u] = ld4_as<BVEC, false>(bb + (i + u * 256) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < TWO_U; ++u) {
+      st4(ab + (i + u * 256) * 4, y[u]);
+      st4_as<BVEC>(bb + (i + u * 256) * 4, x[u]);
+    }
+  }
+  if (base < n4) {
+    for (long i = base + threadIdx.x; i < n4; i += 256) {
+      const f32x4 x = ld4(ab + i * 4);
+      const f32x4 y = ld4_as<BVEC, false>(bb + i * 4);
+      st4(ab + i * 4, y);
+      st4_as<BVEC>(bb + i * 4, x);
+    }
+  }
+  const long nrest = head + (n - tail);
+  if (blockIdx.x == 0 && threadIdx.x < nrest) {
+    const long j = threadIdx.x < head ? threadIdx.x : tail + (threadIdx.x - head);
+    const float x = a[j], y = b[j];
+    a[j] = y;
+    b[j] = x;
+  }
+}
+
 extern "C" {
 
 // state (device float[3]) = {step, lr, apply}; prep increments step
@@ -365,6 +509,49 @@ int fami_loss_scale_update_f32(float* scaler, const unsigned* flag, float growth
                "fami_loss_scale_update_f32", "bad argument");
   hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, s, scaler, flag, growth, backoff, interval);
   FAMI_CHECK_LAUNCH("fami_loss_scale_update_f32");
+  return FAMI_OK;
+}
+
+// ---- exponential moving average of the parameters, arena swap
+// st (device float[4]) = {updates, decay_t, 1 - decay_t, apply}; gate (device float, may be null): 0 = the optimizer skipped this step
+int fami_ema_prep_f32(float* st, const float* gate, float decay, int warmup, hipStream_t s) {
+  FAMI_REQUIRE(st && decay > 0.f && decay < 1.f, "fami_ema_prep_f32", "bad argument");
+  hipLaunchKernelGGL(ema_prep_kernel, dim3(1), dim3(64), 0, s, st, gate, decay, warmup);
+  FAMI_CHECK_LAUNCH("fami_ema_prep_f32");
+  return FAMI_OK;
+}
+// two 4-byte aligned arrays of n floats that do not overlap; *bvec: the second shares the first one's 16-byte alignment
+static bool two_arenas(const float* a, const float* b, long n, bool* bvec) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  if (!a || !b || n <= 0 || ((x | y) & 3) != 0) return false;
+  if (!(x + (uintptr_t)n * 4 <= y || y + (uintptr_t)n * 4 <= x)) return false;
+  *bvec = (x & 15) == (y & 15);
+  return true;
+}
+// ema = ema + st[2] * (p - ema), each operation rounded once; nothing is written when st[3] == 0; p is only read
+int fami_ema_update_f32(float* ema, const float* p, long n, const float* st, hipStream_t s) {
+  bool pvec = false;
+  FAMI_REQUIRE(st && two_arenas(ema, p, n, &pvec), "fami_ema_update_f32", "bad argument");
+  const long head = sumsq_head(ema, n);
+  const dim3 grid(two_arena_grid(n));     // a chip-sized grid (<= 2048 workgroups) strides the tiles
+  if (pvec)
+    hipLaunchKernelGGL(ema_update_kernel<true>, grid, dim3(256), 0, s, ema, p, n, head, st);
+  else
+    hipLaunchKernelGGL(ema_update_kernel<false>, grid, dim3(256), 0, s, ema, p, n, head, st);
+  FAMI_CHECK_LAUNCH("fami_ema_update_f32");
+  return FAMI_OK;
+}
+// a <-> b, bit for bit (no arithmetic touches the values), in place
+int fami_swap_f32(float* a, float* b, long n, hipStream_t s) {
+  bool bvec = false;
+  FAMI_REQUIRE(two_arenas(a, b, n, &bvec), "fami_swap_f32", "bad argument");
+  const long head = sumsq_head(a, n);
+  const dim3 grid(two_arena_grid(n));
+  if (bvec)
+    hipLaunchKernelGGL(swap_kernel<true>, grid, dim3(256), 0, s, a, b, n, head);
+  else
+    hipLaunchKernelGGL(swap_kernel<false>, grid, dim3(256), 0, s, a, b, n, head);
+  FAMI_CHECK_LAUNCH("fami_swap_f32");
   return FAMI_OK;
 }
 

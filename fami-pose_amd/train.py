@@ -22,6 +22,8 @@ zero_grad / backward / Adam step) -- the reference loop itself is not importable
   With world_size > 1 the backward is cut into one graph per bucket so the
   collectives run between graph launches on RCCL's stream.
 """
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -193,6 +195,12 @@ def _check_gmul(t, like):
     if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == 1 and t.device == like.device):
         raise ValueError('the gradient multiplier is one fp32 element on the device of the parameters')
     return t
+
+
+def _check_ema_decay(v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < 1.0:
+        raise ValueError('ema_decay is None or a number in (0, 1), not %r' % (v,))
+    return float(v)
 
 
 def _check_sgd(lr, momentum, dampening, weight_decay, nesterov):
@@ -629,18 +637,38 @@ class Trainer:
     backward pass is deliberately not kept.  The in-backward optimizer split is off.  None and 1: no arena, the launch
     sequence above launch for launch.  Windows always hold N micro-batches and may span epochs (reset_window() drops an
     open one); set_lr / set_max_grad_norm inside a window act at its update.
+
+    ema_decay = d in (0, 1): an exponential moving average of the weights, ema = ema + (1 - d_t) * (param - ema), kept on the
+    device in a second fp32 arena `ema` with the parameter arena's layout (it starts as a copy of it, taken after the
+    data-parallel broadcast).  Two launches directly behind the optimizers, wherever a step ends -- so inside every
+    captured graph that holds them, and once per window under accumulation: fami_ema_prep_f32 advances
+    `ema_state` = {updates, d_t, 1 - d_t, apply} and fami_ema_update_f32 makes one pass over both arenas.  The prep reads
+    the base group's "this step was applied" scalar (opt.state[2]; that group is stepped last and records a skip), so a
+    step skipped for an fp16 overflow or a non-finite norm leaves the average and its update count as they were, with no
+    host read-back.  ema_warmup=True: d_t = min(d, (1 + t) / (10 + t)) at update t, so a short run is not dominated by its
+    initial weights.  d and the warm-up switch are kernel arguments: set_ema_decay re-captures.  Data-parallel ranks
+    exchange nothing for the average: equal parameters give equal averages.  BatchNorm running statistics and batch
+    counters are NOT averaged -- they are running averages already -- so the averaged weights are used with the live
+    buffers.  ema_weights() puts the average into the model (and takes it out again) by exchanging the two arenas in
+    place; ema_state_dict() is the checkpoint entry.  None (default): no arena, none of these launches.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
-                 weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None):
+                 weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None,
+                 ema_decay=None, ema_warmup=False):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
         from a reference config.  max_grad_norm / loss_scale='dynamic' / scaler: see the class docstring (the reference
         configuration has no such keys: from_cfg takes them as keyword arguments).  accum_steps: micro-batches per update
-        (class docstring; None = 1)."""
+        (class docstring; None = 1).  ema_decay / ema_warmup: the moving average of the weights (class docstring; None =
+        none)."""
+        if ema_decay is None and ema_warmup:
+            raise ValueError('ema_warmup=True needs an ema_decay')
+        self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         if accum_steps is not None and (isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1):
             raise ValueError('accum_steps is None or an integer >= 1, not %r' % (accum_steps,))
         self.accum_steps = 1 if accum_steps is None else accum_steps
@@ -765,6 +793,14 @@ class Trainer:
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
             self.broadcast_parameters()
+        # the moving average of the weights: a second parameter arena and {updates, decay_t, 1 - decay_t, apply}
+        self.ema = self.ema_state = None
+        self._ema_version = 0
+        self._ema_swapped = False       # inside ema_weights(): `flat` holds the average, `ema` the raw weights
+        if self.ema_decay is not None:
+            self.ema = self.flat.detach().clone()
+            self.ema_state = torch.zeros(4, device=self.dev)
+            self._set_ema_updates(0)
 
     @classmethod
     def from_cfg(cls, cfg, model, **trainer_kw):
@@ -1006,9 +1042,11 @@ class Trainer:
     def _opt_step(self):
         if self._adam_done:
             self._adam_done = False
+            self._ema_step()
             return
         self._unscale()
         self._step_optimizers()
+        self._ema_step()
 
     def _step_optimizers(self):
         """every group's step (prep + its runs); one group: exactly FlatAdam.step / FlatSGD.step"""
@@ -1021,9 +1059,10 @@ class Trainer:
         self.opt.step(self.overflow)
 
     def _opt_tensors(self):
-        """the parameter arena and every optimizer's device state (shared arenas once), with the loss-scaler vector and the
-        clip vector where they exist: what a capture's warm-up steps must not leave changed"""
-        out, seen = [self.flat] + [t for t in (self.scaler_state, self.clip) if t is not None], set()
+        """the parameter arena and every optimizer's device state (shared arenas once), with the loss-scaler vector, the
+        clip vector and the moving average with its state vector where they exist: what a capture's warm-up steps must not
+        leave changed"""
+        out, seen = [self.flat] + [t for t in (self.scaler_state, self.clip, self.ema, self.ema_state) if t is not None], set()
         for o in self.optimizers:
             for t in o.tensors():
                 if id(t) not in seen:
@@ -1032,7 +1071,7 @@ class Trainer:
         return out
 
     def _hyper_version(self):
-        return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version,)
+        return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version, self._ema_version)
 
     def _unscale(self):
         """gradient arena *= 1 / (world * loss_scale): the data-parallel mean and the static loss scale in one pass.
@@ -1111,6 +1150,113 @@ class Trainer:
         scale = float(sd['scale'])
         self.scaler_state.copy_(torch.tensor([scale, 1.0 / scale, float(sd['_growth_tracker'])]))
 
+    # ------------------------------------------------------------------ moving average of the weights (ema_decay)
+    def _ema_step(self):
+        """behind the optimizers, wherever a step ends: the scalars (gated by the base group's applied / skipped scalar),
+        then the one pass over both arenas"""
+        if self.ema is None:
+            return
+        s = _stream(self.dev)
+        self._lc('fami_ema_prep_f32', _p(self.ema_state), _p(self.opt.state[2:3]), self.ema_decay, int(self.ema_warmup), s)
+        self._lc('fami_ema_update_f32', _p(self.ema), _p(self.flat), self.flat.numel(), _p(self.ema_state), s)
+
+    def _require_ema(self):
+        if getattr(self, 'ema', None) is None:
+            raise ValueError('this Trainer was built without ema_decay')
+        if getattr(self, '_ema_swapped', False):
+            raise RuntimeError('inside ema_weights(): the two arenas are exchanged')
+
+    def _set_ema_updates(self, t):
+        """ema_state after `t` applied updates, in the kernel's own fp32 arithmetic (fami_ema_prep_f32)"""
+        d = torch.tensor(self.ema_decay, dtype=torch.float32)
+        if self.ema_warmup and t > 0:
+            tt = torch.tensor(float(t), dtype=torch.float32)
+            d = torch.minimum(d, (1.0 + tt) / (10.0 + tt))
+        self.ema_state.copy_(torch.stack([torch.tensor(float(t)), d, 1.0 - d, torch.tensor(1.0 if t > 0 else 0.0)]))
+
+    def set_ema_decay(self, v, warmup=None):
+        """A new decay (and, optionally, warm-up switch).  Both are kernel arguments of the captured plan: a change
+        re-captures on the next step(), like set_hyper of the optimizers."""
+        self._require_ema()
+        new = (_check_ema_decay(v), self.ema_warmup if warmup is None else bool(warmup))
+        if new != (self.ema_decay, self.ema_warmup):
+            self.ema_decay, self.ema_warmup = new
+            self._ema_version += 1
+
+    def ema_updates(self):
+        """Updates the average has received: applied optimizer steps since construction / reset_ema() (host int; forces
+        a sync -- logging only)."""
+        return None if self.ema is None else int(self.ema_state[0].item())
+
+    def ema_decay_value(self):
+        """The decay of the last update -- below ema_decay while the warm-up ramp is active (host float; forces a sync --
+        logging only)."""
+        return None if self.ema is None else float(self.ema_state[1].item())
+
+    def reset_ema(self):
+        """Restart the average from the current weights: ema = flat, 0 updates (in place: captured plans keep replaying)."""
+        self._require_ema()
+        with torch.no_grad():
+            self.ema.copy_(self.flat)
+        self._set_ema_updates(0)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Context manager: inside it every trainable parameter of `model` reads its averaged value -- model(...) under
+        torch.no_grad(), evaluate.predict / evaluate_loop and model.state_dict() all see the average, together with the
+        LIVE BatchNorm buffers (class docstring).  Entry exchanges the parameter arena and `ema` in place
+        (fami_swap_f32: one pass, no third arena), exit exchanges them back: both are then bitwise what they were.
+        step(), save_checkpoint, the ema_* state methods and a nested ema_weights() raise RuntimeError inside."""
+        self._require_ema()
+        n, s = self.flat.numel(), _stream(self.dev)
+        self._lc('fami_swap_f32', _p(self.flat), _p(self.ema), n, s)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._lc('fami_swap_f32', _p(self.flat), _p(self.ema), n, _stream(self.dev))
+            self._ema_swapped = False
+
+    def _ema_rows(self):
+        """[(state_dict key, parameter, offset, elements)] of the arena, in table order"""
+        names = {id(p): k for k, p in self.model.named_parameters()}
+        return [(names[id(p)][7:] if names[id(p)].startswith('module.') else names[id(p)], p, off, n)
+                for p, off, n in self.table]
+
+    def ema_state_dict(self):
+        """The 'ema' checkpoint entry: {'decay', 'warmup', 'updates', 'params': {state_dict key of each trainable parameter:
+        host fp32 tensor}} (synchronises).  {**model.state_dict(), **entry['params']} is a state_dict of the averaged model."""
+        self._require_ema()
+        params = {k: self.ema[off:off + n].view(p.shape).detach().cpu().clone() for k, p, off, n in self._ema_rows()}
+        return {'decay': float(self.ema_decay), 'warmup': bool(self.ema_warmup), 'updates': int(self.ema_state[0].item()),
+                'params': params}
+
+    def check_ema_state_dict(self, sd):
+        """ValueError unless the entry names exactly this Trainer's trainable parameters, with their shapes; loads nothing."""
+        self._require_ema()
+        rows = self._ema_rows()
+        params = sd['params']
+        missing = [k for k, _, _, _ in rows if k not in params]
+        extra = sorted(set(params) - {k for k, _, _, _ in rows})
+        if missing or extra:
+            raise ValueError("'ema' entry mismatch: missing %s unexpected %s" % (missing[:5], extra[:5]))
+        for k, p, _, _ in rows:
+            if tuple(params[k].shape) != tuple(p.shape):
+                raise ValueError("'ema' entry %s has shape %s, the parameter %s" % (k, tuple(params[k].shape), tuple(p.shape)))
+        _check_ema_decay(sd['decay'])
+        if int(sd['updates']) < 0:
+            raise ValueError("'ema' entry with %d updates" % int(sd['updates']))
+
+    def load_ema_state_dict(self, sd):
+        """The inverse of ema_state_dict (checked first: a refused entry loads nothing).  Decay and warm-up switch are taken
+        from the entry; where they differ from this Trainer's, a captured plan re-captures."""
+        self.check_ema_state_dict(sd)
+        self.set_ema_decay(sd['decay'], sd.get('warmup', False))
+        with torch.no_grad():
+            for k, p, off, n in self._ema_rows():
+                self.ema[off:off + n].copy_(sd['params'][k].reshape(-1).to(torch.float32))
+        self._set_ema_updates(int(sd['updates']))
+
     # ------------------------------------------------------------------ gradient accumulation (accum_steps > 1)
     def _accumulate(self):
         """window position k < N - 1, behind the backward pass: accum = grad (k = 0) or accum = accum + grad"""
@@ -1127,6 +1273,7 @@ class Trainer:
                  _p(self._partials) if self.clip is not None else None, s)
         self._coef_and_scale_update(s)
         self._step_optimizers()
+        self._ema_step()
 
     def _exchange_window(self):
         """data parallel, a window's last call: grad = accum + grad, then every bucket's all-reduce (outside any graph)"""
@@ -1139,6 +1286,7 @@ class Trainer:
         """... and behind the exchange: the existing unscale path (1 / (world * N * loss scale)) and the optimizers"""
         self._unscale()
         self._step_optimizers()
+        self._ema_step()
 
     def _window_call_done(self, closing):
         """the loss parts of this call into the window sum (one 7-element launch; row 0: the open window, row 1: the last
@@ -1271,6 +1419,7 @@ class Trainer:
             with torch.cuda.graph(g2, pool=pool, capture_error_mode='thread_local'):
                 self._unscale()
                 self._step_optimizers()
+                self._ema_step()
             plan.append(('graph', g2))
         else:
             outs, plan = self._capture_overlap(st)
@@ -1372,6 +1521,7 @@ class Trainer:
             try:
                 self._unscale()
                 self._step_optimizers()
+                self._ema_step()
             finally:
                 g2.capture_end()
             plan.append(('graph', g2))
@@ -1384,6 +1534,8 @@ class Trainer:
         the PCK rows.  Graph mode keeps one captured plan per batch shape: the DataLoader of the reference has no
         drop_last, so the last batch of an epoch is usually smaller (datasets/zoo/build.py:32-50).  With accum_steps = N > 1
         a call is one micro-batch; the N-th of a window updates the parameters (class docstring)."""
+        if self._ema_swapped:
+            raise RuntimeError('step() inside ema_weights(): the parameter arena holds the averaged weights')
         weight = weight.reshape(weight.shape[0], -1).float().contiguous()
         target = target.float().contiguous()
         if not (kf_x.shape[0] == sup_x.shape[0] == target.shape[0] == weight.shape[0]):

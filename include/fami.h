@@ -325,6 +325,20 @@ int fami_sgd_scaled_f32(float* p, const float* g, float* buf, long n, const floa
                         float dampening, float weight_decay, int nesterov, const float* gmul, fami_stream_t stream);
 int fami_loss_scale_update_f32(float* scaler, const unsigned* flag, float growth, float backoff, int interval,
                                fami_stream_t stream);
+/* Exponential moving average (EMA) of a flat fp32 parameter arena, device-resident: no host sync, and a captured hipGraph
+ * keeps replaying while steps are applied or skipped.
+ * fami_ema_prep_f32: one thread.  st4 (device float[4]) = {updates, decay_t, w, apply}.  gate (device float, may be NULL):
+ *   the optimizer's "this step was applied" scalar -- state[2] of fami_adam_prep_* / fami_sgd_prep_*.  gate[0] == 0:
+ *   apply = 0 and nothing else changes.  Otherwise t = updates + 1, updates = t, decay_t = warmup ? min(decay,
+ *   (1 + t) / (10 + t)) : decay, w = 1 - decay_t (one fp32 subtraction), apply = 1.  decay must lie in (0, 1).
+ * fami_ema_update_f32: returns at once when st4[3] == 0; otherwise ema[i] = rn(ema[i] + rn(w * rn(p[i] - ema[i]))) with
+ *   w = st4[2] -- three separately rounded fp32 operations, no fused multiply-add.  p is only read.  12 bytes of traffic
+ *   per element.
+ * fami_swap_f32: exchanges the contents of a and b bit for bit in one pass, with no temporary.
+ * Both passes accept any 4-byte aligned sub-ranges of arenas; the two arrays must not overlap. */
+int fami_ema_prep_f32(float* st4, const float* gate, float decay, int warmup, fami_stream_t stream);
+int fami_ema_update_f32(float* ema, const float* p, long n, const float* st4, fami_stream_t stream);
+int fami_swap_f32(float* a, float* b, long n, fami_stream_t stream);
 
 /* ---- temporal alignment ----------------------------------------------------------------------
  * fami_shift_bilinear_*: kornia.geometry.warp_affine(src, [[1,0,tx],[0,1,ty]], dsize) at
