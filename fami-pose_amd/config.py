@@ -44,4 +44,7 @@ def default_cfg(width=48, num_joints=17, freeze_backbone=False, name='Alignment_
         'TRAIN': {'ROT_FACTOR': 45, 'SCALE_FACTOR': 0.35, 'LR': 1e-3, 'LR_STEP': [8, 12, 16], 'LR_FACTOR': 0.1,
                   'OPTIMIZER': 'adam'},
         'LOSS': {'HEATMAP_MSE': {'USE': True, 'WEIGHT': 1.0}},
+        # flip testing (evaluate.flip_test_options); the reference's defaults, posetimation/config/mppe_config.py:322-346
+        'VAL': {'FLIP_VAL': False, 'SHIFT_HEATMAP': False},
+        'TEST': {'FLIP_TEST': False, 'SHIFT_HEATMAP': False},
     })

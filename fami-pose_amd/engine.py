@@ -14,6 +14,7 @@ write fp32 in either mode; parameters, BatchNorm statistics, weight gradients, t
 dense layers ([M,K] tensors) and everything at the NCHW boundary are always fp32.
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -113,10 +114,12 @@ class _RoutedQueries:
     they depend on the routing state, so the route is bound before the raw call, as it is before every launch."""
 
     def __init__(self, L, eng):
-        self._L, self._eng = L, eng
+        # weak: the engine owns this object.  A strong reference closed a cycle, and every buffer of a forward stayed allocated
+        # until Python's cycle collector happened to run (9.7 GiB per W48 inference call of 4 clips, several calls deep)
+        self._L, self._eng = L, weakref.ref(eng)
 
     def __getattr__(self, name):
-        fn, L, eng = getattr(self._L.cdll, name), self._L, self._eng
+        fn, L, eng = getattr(self._L.cdll, name), self._L, self._eng()
 
         def query(*args):
             L.bind(eng.route)

@@ -4,6 +4,15 @@
   (engine/core/functions/alignment_mi_function_term6_1.py:256-276): `model(kf, sup) -> (pred, kf_bb)` under
   `torch.no_grad()`, then `get_final_preds(pred, center, scale)` -- with the decode on device, so only [B,J,2]
   coordinates and [B,J,1] confidences leave the GPU instead of two full heatmap stacks.
+* `mirror_cat` / `flip_merge` / `flip_perm` -- flip testing, the protocol every HRNet-family number is reported with
+  (the reference declares VAL.FLIP_VAL, TEST.FLIP_TEST and the two SHIFT_HEATMAP switches,
+  posetimation/config/mppe_config.py:322-346, and ships `flip_back`, datasets/process/pose_process.py:29-42, but its
+  released eval function never calls it): the clip and its horizontal mirror go through ONE forward as a doubled batch,
+  the mirrored half's heatmaps are mirrored back with the left/right joint channels swapped, optionally shifted by one
+  column, and averaged with the plain half -- one HIP launch per input in front of the forward and one per merged head
+  behind it (csrc/flip.hip), nothing extra on the bus.  `predict(..., flip=True)` and `evaluate_loop(..., flip=True)` use it; `flip_test_options(cfg, phase)` reads the
+  switches.  The doubled batch doubles the activation memory of the forward: halve VAL.BATCH_SIZE_PER_GPU /
+  TEST.BATCH_SIZE_PER_GPU where that does not fit (there is no two-pass mode).
 * `EvalAccumulator` + `evaluate_loop` -- the loop around it (:222-328): per-batch PCK of both heatmap outputs (on
   device), `all_preds` / `all_bb` / `all_boxes` / `filenames_map` accumulation exactly as the reference lays them out.
 * `write_posetrack_results` -- the PoseTrack JSON writer of
@@ -26,7 +35,10 @@ import os.path as osp
 import numpy as np
 import torch
 
-from .loss import get_final_preds
+from ._lib import lib
+from .data import FLIP_PAIRS
+from .loss import _need_cuda, _p, _stream, get_final_preds
+from .zoo.registry import TEST_PHASE, VAL_PHASE
 
 COCO_JOINT = ['nose', 'left_eye', 'right_eye', 'left_ear', 'right_ear', 'left_shoulder', 'right_shoulder',
               'left_elbow', 'right_elbow', 'left_wrist', 'right_wrist', 'left_hip', 'right_hip', 'left_knee',
@@ -36,10 +48,98 @@ POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_k
                    'head_top']
 
 
+# ---------------------------------------------------------------------------------------- flip testing
+def flip_perm(num_joints, pairs=FLIP_PAIRS):
+    """-> list of J ints: perm[a] = b and perm[b] = a for every (a, b) of `pairs`, identity elsewhere (the channel
+    exchange of flip_back, pose_process.py:37-40, as one gather)."""
+    J = int(num_joints)
+    perm = list(range(J))
+    seen = set()
+    for a, b in pairs:
+        a, b = int(a), int(b)
+        if not (0 <= a < J and 0 <= b < J):
+            raise ValueError('flip pair (%d, %d) outside [0, %d)' % (a, b, J))
+        if a == b:
+            raise ValueError('flip pair (%d, %d) pairs a joint with itself' % (a, b))
+        if a in seen or b in seen:
+            raise ValueError('flip pair (%d, %d): a joint occurs twice' % (a, b))
+        seen.update((a, b))
+        perm[a], perm[b] = b, a
+    return perm
+
+
+_PERM_CACHE = {}
+
+
+def _perm_on(dev, J, pairs):
+    """flip_perm(J, pairs) as a device int32 tensor; one upload per (device, J, pairs)."""
+    key = (str(dev), J, tuple((int(a), int(b)) for a, b in pairs))
+    t = _PERM_CACHE.get(key)
+    if t is None:
+        t = _PERM_CACHE[key] = torch.tensor(flip_perm(J, key[2]), dtype=torch.int32, device=dev)
+    return t
+
+
+def mirror_cat(x):
+    """x [B,C,H,W] (device) -> [2B,C,H,W] fp32: x, then x mirrored along W -- the doubled batch of a flip-test forward,
+    one launch, values copied bit for bit."""
+    _need_cuda(x)
+    if x.dim() != 4:
+        raise ValueError('mirror_cat expects [B,C,H,W], got %s' % (tuple(x.shape),))
+    x = x.float().contiguous()
+    B, C, H, W = x.shape
+    out = torch.empty(2 * B, C, H, W, device=x.device)
+    lib().call('fami_mirror_cat_f32', _p(x), _p(out), B * C * H, W, _stream(x))
+    return out
+
+
+def flip_merge(hm2, pairs=FLIP_PAIRS, shift=False):
+    """hm2 [2B,J,H,W] (device): heatmaps of a clip batch, then of its mirror -> [B,J,H,W] =
+    (hm2[:B] + flip_back(hm2[B:], pairs)) * 0.5; with `shift` the mirrored-back half moves one column to the right first
+    (HRNet's SHIFT_HEATMAP: flipped[..., 1:] = flipped[..., :-1], column 0 keeps its value)."""
+    _need_cuda(hm2)
+    if hm2.dim() != 4 or hm2.shape[0] % 2:
+        raise ValueError('flip_merge expects [2B,J,H,W], got %s' % (tuple(hm2.shape),))
+    hm2 = hm2.float().contiguous()
+    B, J, H, W = hm2.shape[0] // 2, hm2.shape[1], hm2.shape[2], hm2.shape[3]
+    perm = _perm_on(hm2.device, J, pairs)
+    out = torch.empty(B, J, H, W, device=hm2.device)
+    lib().call('fami_flip_merge_f32', _p(hm2), _p(perm), _p(out), B, J, H, W, 1 if shift else 0, _stream(hm2))
+    return out
+
+
+def flip_test_options(cfg, phase):
+    """-> {'flip': bool, 'shift_heatmap': bool} for `predict` / `evaluate_loop` from the reference's switches:
+    VAL.FLIP_VAL / VAL.SHIFT_HEATMAP in the validation phase, TEST.FLIP_TEST / TEST.SHIFT_HEATMAP in the test phase
+    (mppe_config.py:322,329,340,346); False where the node or the key is absent."""
+    if phase == VAL_PHASE:
+        node, key = 'VAL', 'FLIP_VAL'
+    elif phase == TEST_PHASE:
+        node, key = 'TEST', 'FLIP_TEST'
+    else:
+        raise ValueError('flip testing is an evaluation option: phase %r has none' % (phase,))
+    sub = cfg.get(node) if hasattr(cfg, 'get') else None
+    sub = sub if hasattr(sub, 'get') else {}
+    return {'flip': bool(sub.get(key, False)), 'shift_heatmap': bool(sub.get('SHIFT_HEATMAP', False))}
+
+
+def _flip_forward(model, kf_x, sup_x):
+    """ONE forward on the doubled batch [x ; mirror(x)] (the channel-packed supporting frames mirror along W like any
+    other channel).  Needs eval mode: with running statistics BatchNorm does not mix the two halves."""
+    if model.training:
+        raise RuntimeError('flip testing needs model.eval(): batch statistics would mix the clip and its mirror')
+    return model(mirror_cat(kf_x), mirror_cat(sup_x))
+
+
 @torch.no_grad()
-def predict(model, kf_x, sup_x, center, scale):
+def predict(model, kf_x, sup_x, center, scale, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS):
     """-> (preds [B,J,2] image coordinates, maxvals [B,J,1], final_hm [B,J,H/4,W/4]) as device tensors.
-    `model` is a val/test-phase Alignment_V15 (2-tuple forward) or a train-phase one (3-tuple; MI terms ignored)."""
+    `model` is a val/test-phase Alignment_V15 (2-tuple forward) or a train-phase one (3-tuple; MI terms ignored).
+    flip=True: flip testing -- one forward on the doubled batch, final_hm is the merged map and the decode runs on it."""
+    if flip:
+        final_hm = flip_merge(_flip_forward(model, kf_x, sup_x)[0], flip_pairs, shift_heatmap)
+        preds, maxvals = get_final_preds(final_hm, center, scale)
+        return preds, maxvals, final_hm
     out = model(kf_x, sup_x)
     final_hm = out[0]
     preds, maxvals = get_final_preds(final_hm, center, scale)
@@ -92,18 +192,23 @@ class EvalAccumulator:
 
 
 @torch.no_grad()
-def evaluate_loop(model, batches, num_samples, num_joints=17):
+def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS):
     """The reference's validation loop (core fn :256-309) on the HIP path.  `batches` yields
     (kf_x, sup_x, target_heatmaps | None, meta) with meta = {'image': [names], 'center': [B,2], 'scale': [B,2],
-    'score': [B]}; tensors may live on the host (they are moved to the model's device).  -> EvalAccumulator."""
-    from ._lib import lib
+    'score': [B]}; tensors may live on the host (they are moved to the model's device).  -> EvalAccumulator.
+    flip=True: flip testing -- both heads (final_hm, kf_bb_hm) are merged from one doubled-batch forward; decode and
+    PCK run on the merged maps."""
     dev = next(model.parameters()).device
     acc = EvalAccumulator(num_samples, num_joints)
     model.eval()
     for kf_x, sup_x, target, meta in batches:
         kf_x, sup_x = kf_x.to(dev), sup_x.to(dev)
-        out = model(kf_x, sup_x)
-        pred_hm, kf_bb_hm = out[0], out[1]
+        if flip:
+            out = _flip_forward(model, kf_x, sup_x)
+            pred_hm, kf_bb_hm = (flip_merge(o, flip_pairs, shift_heatmap) for o in out[:2])
+        else:
+            out = model(kf_x, sup_x)
+            pred_hm, kf_bb_hm = out[0], out[1]
         center = np.asarray(meta['center'], dtype=np.float32)
         scale = np.asarray(meta['scale'], dtype=np.float32)
         pc, pm = get_final_preds(pred_hm, center, scale)

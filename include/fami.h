@@ -449,6 +449,20 @@ int fami_final_preds_f32(const float* hm, const float* center, const float* scal
 int fami_pck_accuracy_f32(const float* pred_hm, const float* target_hm, float* out, long long* idx_ws, float* max_ws,
                           int B, int J, int H, int W, float thr, fami_stream_t stream);
 
+/* Flip testing (HRNet / DCPose evaluation protocol: the clip and its horizontal mirror in ONE doubled batch, the two
+ * sets of heatmaps merged on the device; csrc/flip.hip).  Boundary tensors are NCHW fp32 in every compute mode.
+ * fami_mirror_cat_f32: out [2*rows][W]: out[r,:] = x[r,:], out[rows+r, w] = x[r, W-1-w].  x [B,C,H,W] contiguous with
+ *   rows = B*C*H gives [x ; mirror_W(x)].  A pure copy: every bit pattern survives.  x and out must not overlap.
+ * fami_flip_merge_f32: hm2 [2B,J,H,W] (plain outputs, then the outputs of the mirrored inputs), perm device int[J] with
+ *   every entry in [0, J): out[b,j,y,x] = (hm2[b,j,y,x] + hm2[B+b, perm[j], y, xs]) * 0.5f, xs = W-1-x, or with shift
+ *   min(W-x, W-1) -- flip_back (datasets/process/pose_process.py:29-42), HRNet's flipped[..., 1:] = flipped[..., :-1]
+ *   (column 0 keeps its value), then one fp32 add and one fp32 multiply.  out must not overlap hm2.
+ * Both use 16-byte accesses when W % 4 == 0 and the bases are 16-byte aligned, and a scalar form for any W and any
+ * 4-byte aligned pointers. */
+int fami_mirror_cat_f32(const float* x, float* out, long long rows, int W, fami_stream_t stream);
+int fami_flip_merge_f32(const float* hm2, const int* perm, float* out, int B, int J, int H, int W, int shift,
+                        fami_stream_t stream);
+
 /* ---- input pipeline on the device -------------------------------------------------------------
  * cv2.warpAffine(frame, trans, (Wd, Hd), flags=INTER_LINEAR) on the F 8-bit HWC frames of one clip (one transform
  * for key + supporting frames, datasets/zoo/posetrack/PoseTrack_Alignment.py:421-427; flip = source mirrored in x
