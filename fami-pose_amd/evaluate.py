@@ -13,6 +13,12 @@
   behind it (csrc/flip.hip), nothing extra on the bus.  `predict(..., flip=True)` and `evaluate_loop(..., flip=True)` use it; `flip_test_options(cfg, phase)` reads the
   switches.  The doubled batch doubles the activation memory of the forward: halve VAL.BATCH_SIZE_PER_GPU /
   TEST.BATCH_SIZE_PER_GPU where that does not fit (there is no two-pass mode).
+* `decode='dark'` on `predict` / `evaluate_loop` -- the distribution-aware decode the reference ships and exports
+  (`dark_get_final_preds`, datasets/process/heatmaps_process.py:84-143; datasets/process/__init__.py:14) and that DARK-trained
+  weights are meant to be read with: a `blur_kernel` x `blur_kernel` Gaussian blur of every map, log, one Newton step at the
+  argmax -- one HIP launch per head (csrc/decode.hip, `loss.dark_get_final_preds`) in place of the quarter-pixel shift; with
+  flip=True it runs on the merged maps.  The reference has no cfg switch for it, so there is none here; PCK stays on the
+  argmax.  The default decode='standard' is `get_final_preds` as before.
 * `EvalAccumulator` + `evaluate_loop` -- the loop around it (:222-328): per-batch PCK of both heatmap outputs (on
   device), `all_preds` / `all_bb` / `all_boxes` / `filenames_map` accumulation exactly as the reference lays them out.
 * `write_posetrack_results` -- the PoseTrack JSON writer of
@@ -37,7 +43,7 @@ import torch
 
 from ._lib import lib
 from .data import FLIP_PAIRS
-from .loss import _need_cuda, _p, _stream, get_final_preds
+from .loss import _need_cuda, _p, _stream, check_blur_kernel, dark_get_final_preds, get_final_preds
 from .zoo.registry import TEST_PHASE, VAL_PHASE
 
 COCO_JOINT = ['nose', 'left_eye', 'right_eye', 'left_ear', 'right_ear', 'left_shoulder', 'right_shoulder',
@@ -131,18 +137,32 @@ def _flip_forward(model, kf_x, sup_x):
     return model(mirror_cat(kf_x), mirror_cat(sup_x))
 
 
+def _decoder(decode, blur_kernel):
+    """-> f(heatmaps, center, scale) for decode = 'standard' (get_final_preds: quarter-pixel shift) or 'dark'
+    (dark_get_final_preds with a blur_kernel x blur_kernel Gaussian); ValueError for anything else, before any device work."""
+    if decode == 'standard':
+        return get_final_preds
+    if decode == 'dark':
+        k = check_blur_kernel(blur_kernel)
+        return lambda hm, center, scale: dark_get_final_preds(hm, center, scale, k)
+    raise ValueError("decode must be 'standard' or 'dark', got %r" % (decode,))
+
+
 @torch.no_grad()
-def predict(model, kf_x, sup_x, center, scale, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS):
+def predict(model, kf_x, sup_x, center, scale, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS, decode='standard',
+            blur_kernel=11):
     """-> (preds [B,J,2] image coordinates, maxvals [B,J,1], final_hm [B,J,H/4,W/4]) as device tensors.
     `model` is a val/test-phase Alignment_V15 (2-tuple forward) or a train-phase one (3-tuple; MI terms ignored).
-    flip=True: flip testing -- one forward on the doubled batch, final_hm is the merged map and the decode runs on it."""
+    flip=True: flip testing -- one forward on the doubled batch, final_hm is the merged map and the decode runs on it.
+    decode='dark': the distribution-aware decode (blur_kernel: odd, 9..17) instead of the quarter-pixel shift."""
+    final_preds = _decoder(decode, blur_kernel)
     if flip:
         final_hm = flip_merge(_flip_forward(model, kf_x, sup_x)[0], flip_pairs, shift_heatmap)
-        preds, maxvals = get_final_preds(final_hm, center, scale)
+        preds, maxvals = final_preds(final_hm, center, scale)
         return preds, maxvals, final_hm
     out = model(kf_x, sup_x)
     final_hm = out[0]
-    preds, maxvals = get_final_preds(final_hm, center, scale)
+    preds, maxvals = final_preds(final_hm, center, scale)
     return preds, maxvals, final_hm
 
 
@@ -192,12 +212,15 @@ class EvalAccumulator:
 
 
 @torch.no_grad()
-def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS):
+def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS,
+                  decode='standard', blur_kernel=11):
     """The reference's validation loop (core fn :256-309) on the HIP path.  `batches` yields
     (kf_x, sup_x, target_heatmaps | None, meta) with meta = {'image': [names], 'center': [B,2], 'scale': [B,2],
     'score': [B]}; tensors may live on the host (they are moved to the model's device).  -> EvalAccumulator.
     flip=True: flip testing -- both heads (final_hm, kf_bb_hm) are merged from one doubled-batch forward; decode and
-    PCK run on the merged maps."""
+    PCK run on the merged maps.  decode='dark': both heads are decoded with dark_get_final_preds (blur_kernel: odd, 9..17);
+    PCK stays on the argmax."""
+    final_preds = _decoder(decode, blur_kernel)
     dev = next(model.parameters()).device
     acc = EvalAccumulator(num_samples, num_joints)
     model.eval()
@@ -211,8 +234,8 @@ def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_
             pred_hm, kf_bb_hm = out[0], out[1]
         center = np.asarray(meta['center'], dtype=np.float32)
         scale = np.asarray(meta['scale'], dtype=np.float32)
-        pc, pm = get_final_preds(pred_hm, center, scale)
-        bc, bm = get_final_preds(kf_bb_hm, center, scale)
+        pc, pm = final_preds(pred_hm, center, scale)
+        bc, bm = final_preds(kf_bb_hm, center, scale)
         if target is not None:
             B, J, H, W = pred_hm.shape
             target = target.to(dev).float().contiguous()

@@ -115,6 +115,58 @@ def get_final_preds(batch_heatmaps, center, scale):
     return preds, mx.unsqueeze(-1)
 
 
+def check_blur_kernel(k):
+    """-> int(k), or ValueError: the DARK decode accepts an odd Gaussian kernel size with 9 <= k <= 17.  (OpenCV uses fixed
+    tables instead of the formula for k = 3, 5, 7, and nothing available here can pin them.)"""
+    if isinstance(k, bool) or int(k) != k or int(k) % 2 == 0 or not 9 <= int(k) <= 17:
+        raise ValueError('blur_kernel must be an odd integer with 9 <= k <= 17, got %r' % (k,))
+    return int(k)
+
+
+def gaussian_taps(k):
+    """The k taps of cv2.GaussianBlur(., (k, k), 0) as float32: sigma = 0.3 ((k - 1) / 2 - 1) + 0.8 (2.0 for k = 11),
+    exp(-x^2 / (2 sigma^2)) normalised to sum 1 in float64, then rounded."""
+    k = check_blur_kernel(k)
+    sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) * 0.5
+    t = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return (t / t.sum()).astype(np.float32)
+
+
+_TAPS_CACHE = {}
+
+
+def _taps_on(dev, k):
+    """gaussian_taps(k) as a device tensor; one upload per (device, k)."""
+    key = (str(dev), k)
+    t = _TAPS_CACHE.get(key)
+    if t is None:
+        t = _TAPS_CACHE[key] = torch.from_numpy(gaussian_taps(k)).to(dev)
+    return t
+
+
+def dark_get_final_preds(batch_heatmaps, center, scale, blur_kernel=11):
+    """On-device dark_get_final_preds (datasets/process/heatmaps_process.py:84-143), the distribution-aware decode: argmax
+    of the unblurred map, a blur_kernel x blur_kernel Gaussian blur rescaled to the original maximum, log, one Newton step
+    at the peak, inverse affine -- one launch (csrc/decode.hip).  Same conventions as get_final_preds: heatmaps [B,J,H,W]
+    (device), center / scale [B,2] -> (preds [B,J,2] image coordinates, maxvals [B,J,1]) as device tensors."""
+    k = check_blur_kernel(blur_kernel)
+    _need_cuda(batch_heatmaps)
+    B, J, H, W = batch_heatmaps.shape
+    need, limit = lib().cdll.fami_dark_preds_lds_bytes(H, W, k), lib().cdll.fami_dark_preds_lds_limit()     # host arithmetic
+    if need > limit:
+        raise ValueError('dark_get_final_preds: a %dx%d map at blur_kernel %d needs %d bytes of LDS (the padded map and its '
+                         'row pass, 4 (H (W + k - 1) + (H + k - 1) W)); the limit is %d' % (H, W, k, need, limit))
+    dev = batch_heatmaps.device
+    c = torch.as_tensor(center, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
+    sc = torch.as_tensor(scale, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
+    preds = torch.empty(B, J, 2, device=dev)
+    mx = torch.empty(B, J, device=dev)
+    lib().call('fami_dark_preds_f32', _p(batch_heatmaps.float().contiguous()), _p(c), _p(sc), _p(_taps_on(dev, k)), k,
+               _p(preds), _p(mx), B, J, H, W, _stream(batch_heatmaps))
+    return preds, mx.unsqueeze(-1)
+
+
 def accuracy(output, target, thr=0.5):
     """PCK on heatmap argmax (evaluate.py:39-75).  -> (acc[J+1], avg_acc, cnt, pred[B,J,2] ndarray)."""
     pred, _ = get_max_preds(output)

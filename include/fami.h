@@ -441,6 +441,23 @@ int fami_argmax2d_f32(const float* hm, long long* idx, float* maxval, int R, int
  * preds [B,J,2]; maxvals [B,J]; idx_ws: B*J int64 scratch */
 int fami_final_preds_f32(const float* hm, const float* center, const float* scale, float* preds, float* maxvals,
                          long long* idx_ws, int B, int J, int H, int W, fami_stream_t stream);
+/* dark_get_final_preds (datasets/process/heatmaps_process.py:84-143; csrc/decode.hip): the distribution-aware decode.
+ * Per map, in fp32 and in this order: get_max_preds on the unblurred map (maxvals and the integer coordinates are those
+ * of fami_final_preds_f32 bit for bit); a k x k separable Gaussian blur with zero padding, rescaled by
+ * origin_max / max(blurred); log(max(., 1e-10)); one Newton step from the 5-point gradient and Hessian at the integer
+ * peak where 1 < px < W-2, 1 < py < H-2 and the determinant is not 0; transform_preds for rot 0.  Where the rescale
+ * ratio is not finite (blurred maximum exactly 0; NaN coordinates in the reference) the step is skipped.
+ * hm [B,J,H,W]; center, scale [B,2]; taps: DEVICE float[k], the fp64 kernel exp(-x^2 / (2 sigma^2)) normalised to sum 1
+ * and rounded to fp32 (OpenCV: sigma = 0.3 ((k-1)/2 - 1) + 0.8; symmetric: only taps[0 .. (k-1)/2] are read and each
+ * mirror pair of samples is added before it is scaled), k odd with 9 <= k <= 17 (else -1); preds [B,J,2];
+ * maxvals [B,J].  One launch, one workgroup per map, no workspace and no host read-back.  The map and its row pass live
+ * in LDS: fami_dark_preds_lds_bytes(H, W, k) = 4 (H (W + k - 1) + (H + k - 1) W) bytes (-1 for a k or size that is no
+ * argument) must not exceed fami_dark_preds_lds_limit(), else -2 before any launch (128x96 at k = 17: 112640 of
+ * 163584).  Any W: no alignment is assumed. */
+int fami_dark_preds_f32(const float* hm, const float* center, const float* scale, const float* taps, int k, float* preds,
+                        float* maxvals, int B, int J, int H, int W, fami_stream_t stream);
+long fami_dark_preds_lds_bytes(int H, int W, int k);
+long fami_dark_preds_lds_limit(void);
 
 /* PCK accuracy on heatmap argmax, engine/core/utils/evaluate.py:39-75 (`accuracy`, called twice per training step at
  * engine/core/functions/alignment_mi_function_term6_1.py:159-163 after D2H copies of four heatmap stacks): here
