@@ -36,7 +36,54 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-class FlatAdam:
+class _FlatOptimizer:
+    """What FlatAdam and FlatSGD share: the arena runs, the learning rate (host copy and the device scalar state[1]), the
+    gradient multiplier, and a step as "the scalars, then one launch per run".  A subclass supplies `_prep(flag, s)` (the
+    step's scalars; flag: the device u32 of the checked step, None: unchecked) and `_launch(lo, hi, s)`."""
+
+    gmul = None
+
+    def __init__(self, flat_param, lr, runs):
+        self.p = flat_param
+        self.runs = [(0, flat_param.numel())] if runs is None else [(int(a), int(b)) for a, b in runs]
+        self.lr = float(lr)
+        # the undecayed rate an LR schedule scales (torch stores it as param_groups[0]['initial_lr'] the first time a
+        # scheduler is attached; checkpoints carry it so a resumed MultiStepLR does not decay an already decayed rate)
+        self.initial_lr = float(lr)
+        self.hyper_version = 0
+
+    def set_grad_multiplier(self, t):
+        """t: device float tensor [1] read by every later update (None: back to the unscaled update).  A graph-mode
+        Trainer bakes the choice into its captured plan: it sets it once, at construction."""
+        self.gmul = _check_gmul(t, self.p)
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self.state[1] = self.lr
+
+    def step(self, flag=None):
+        """flag: device u32 raised by fami_unscale_check_f32 on non-finite gradients -> the step is skipped."""
+        s = _stream(self.p.device)
+        self._prep(flag, s)
+        for lo, hi in self.runs:
+            self._launch(lo, hi, s)
+
+    def prep(self, s=None):
+        """the step's scalars alone (step count, bias corrections): a step split into ranges prepares once, up front"""
+        self._prep(None, _stream(self.p.device) if s is None else s)
+
+    def apply(self, lo, hi, s=None):
+        """the update of arena[lo:hi] (restricted to this optimizer's runs) with the prepared scalars"""
+        s = _stream(self.p.device) if s is None else s
+        for a, b in _clip(self.runs, lo, hi):
+            self._launch(a, b, s)
+
+    def _scaled(self, name):
+        """-> (entry point, trailing arguments): `name`, or its _scaled variant with the multiplier pointer appended"""
+        return (name + '_f32', ()) if self.gmul is None else (name + '_scaled_f32', (_p(self.gmul),))
+
+
+class FlatAdam(_FlatOptimizer):
     """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8, weight_decay=0) on one flat fp32 arena
     (posetimation/optimizer/optimizer.py:66-68 builds the reference's).  The step count, the learning rate and the two
     bias corrections live in a device vector, so an LR schedule needs no re-capture of a hipGraph; betas / eps /
@@ -49,37 +96,21 @@ class FlatAdam:
     fami_clip_coef_f32; the gradient arena itself is not rewritten.  None: exactly the launches of the plain update."""
 
     kind = 'adam'
-    gmul = None
 
     def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, runs=None, share=None):
-        self.p = flat_param
+        super().__init__(flat_param, lr, runs)
         if share is None:
             self.grad = torch.zeros_like(flat_param)
             self.m = torch.zeros_like(flat_param)
             self.v = torch.zeros_like(flat_param)
         else:
             self.grad, self.m, self.v = share.grad, share.m, share.v
-        self.runs = [(0, flat_param.numel())] if runs is None else [(int(a), int(b)) for a, b in runs]
         self.betas, self.eps, self.wd = tuple(betas), eps, weight_decay
-        self.lr = float(lr)
-        # the undecayed rate an LR schedule scales (torch stores it as param_groups[0]['initial_lr'] the first time a
-        # scheduler is attached; checkpoints carry it so a resumed MultiStepLR does not decay an already decayed rate)
-        self.initial_lr = float(lr)
-        self.hyper_version = 0
         self.state = torch.tensor([0.0, lr, 1.0, 1.0], device=flat_param.device)   # step, lr, bc1, bc2
-
-    def set_grad_multiplier(self, t):
-        """t: device float tensor [1] read by every later update (None: back to the unscaled update).  A graph-mode
-        Trainer bakes the choice into its captured plan: it sets it once, at construction."""
-        self.gmul = _check_gmul(t, self.p)
 
     def tensors(self):
         """the device state a step mutates besides the parameters (a graph capture's warm-up restores it)"""
         return [self.m, self.v, self.state]
-
-    def set_lr(self, lr):
-        self.lr = float(lr)
-        self.state[1] = self.lr
 
     def set_hyper(self, betas=None, eps=None, weight_decay=None):
         new = (tuple(betas) if betas is not None else self.betas, self.eps if eps is None else eps,
@@ -88,36 +119,19 @@ class FlatAdam:
             self.betas, self.eps, self.wd = new
             self.hyper_version += 1
 
-    def step(self, flag=None):
-        """flag: device u32 raised by fami_unscale_check_f32 on non-finite gradients -> the step is skipped."""
-        s = _stream(self.p.device)
+    def _prep(self, flag, s):
         if flag is None:
             lib().call('fami_adam_prep_f32', _p(self.state), self.betas[0], self.betas[1], s)
         else:
             lib().call('fami_adam_prep_checked_f32', _p(self.state), self.betas[0], self.betas[1], _p(flag), s)
-        for lo, hi in self.runs:
-            self._launch(lo, hi, s)
-
-    def prep(self, s=None):
-        """the step's scalars alone (step count, bias corrections): a step split into ranges prepares once, up front"""
-        lib().call('fami_adam_prep_f32', _p(self.state), self.betas[0], self.betas[1], _stream(self.p.device) if s is None else s)
-
-    def apply(self, lo, hi, s=None):
-        """the update of arena[lo:hi] (restricted to this optimizer's runs) with the prepared scalars"""
-        s = _stream(self.p.device) if s is None else s
-        for a, b in _clip(self.runs, lo, hi):
-            self._launch(a, b, s)
 
     def _launch(self, lo, hi, s):
-        if self.gmul is not None:
-            lib().call('fami_adam_scaled_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]),
-                       hi - lo, _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, _p(self.gmul), s)
-            return
-        lib().call('fami_adam_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]), hi - lo,
-                   _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, s)
+        name, gmul = self._scaled('fami_adam')
+        lib().call(name, _p(self.p[lo:hi]), _p(self.grad[lo:hi]), _p(self.m[lo:hi]), _p(self.v[lo:hi]), hi - lo,
+                   _p(self.state), self.betas[0], self.betas[1], self.eps, self.wd, *gmul, s)
 
 
-class FlatSGD:
+class FlatSGD(_FlatOptimizer):
     """torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) on one flat fp32 arena: TRAIN.OPTIMIZER 'sgd'
     (posetimation/optimizer/optimizer.py:58-64; MOMENTUM 0.9 / WD 1e-4 / NESTEROV False in posetimation/config/
     defaults.py:137-140).  The protocol of FlatAdam: the step count (it selects the momentum buffer's first-step rule),
@@ -126,32 +140,20 @@ class FlatSGD:
     momentum, as torch's does.  gmul / set_grad_multiplier: as FlatAdam's."""
 
     kind = 'sgd'
-    gmul = None
 
     def __init__(self, flat_param, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, runs=None,
                  share=None):
         _check_sgd(lr, momentum, dampening, weight_decay, nesterov)
-        self.p = flat_param
+        super().__init__(flat_param, lr, runs)
         self.grad = torch.zeros_like(flat_param) if share is None else share.grad
         self.momentum, self.dampening, self.wd, self.nesterov = float(momentum), float(dampening), float(weight_decay), bool(nesterov)
         self.buf = None
         if self.momentum != 0.0:
             self.buf = share.buf if share is not None and share.buf is not None else torch.zeros_like(flat_param)
-        self.runs = [(0, flat_param.numel())] if runs is None else [(int(a), int(b)) for a, b in runs]
-        self.lr = float(lr)
-        self.initial_lr = float(lr)
-        self.hyper_version = 0
         self.state = torch.tensor([0.0, lr, 1.0], device=flat_param.device)        # step, lr, apply
-
-    def set_grad_multiplier(self, t):
-        self.gmul = _check_gmul(t, self.p)
 
     def tensors(self):
         return ([] if self.buf is None else [self.buf]) + [self.state]
-
-    def set_lr(self, lr):
-        self.lr = float(lr)
-        self.state[1] = self.lr
 
     def set_hyper(self, momentum=None, dampening=None, weight_decay=None, nesterov=None):
         new = (self.momentum if momentum is None else float(momentum), self.dampening if dampening is None else float(dampening),
@@ -163,32 +165,16 @@ class FlatSGD:
                 self.buf = torch.zeros_like(self.p)
             self.hyper_version += 1
 
-    def step(self, flag=None):
-        """flag: device u32 raised by fami_unscale_check_f32 on non-finite gradients -> the step is skipped."""
-        s = _stream(self.p.device)
+    def _prep(self, flag, s):
         if flag is None:
             lib().call('fami_sgd_prep_f32', _p(self.state), s)
         else:
             lib().call('fami_sgd_prep_checked_f32', _p(self.state), _p(flag), s)
-        for lo, hi in self.runs:
-            self._launch(lo, hi, s)
-
-    def prep(self, s=None):
-        lib().call('fami_sgd_prep_f32', _p(self.state), _stream(self.p.device) if s is None else s)
-
-    def apply(self, lo, hi, s=None):
-        s = _stream(self.p.device) if s is None else s
-        for a, b in _clip(self.runs, lo, hi):
-            self._launch(a, b, s)
 
     def _launch(self, lo, hi, s):
-        buf = None if self.momentum == 0.0 else _p(self.buf[lo:hi])
-        if self.gmul is not None:
-            lib().call('fami_sgd_scaled_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), buf, hi - lo, _p(self.state),
-                       self.momentum, self.dampening, self.wd, int(self.nesterov), _p(self.gmul), s)
-            return
-        lib().call('fami_sgd_f32', _p(self.p[lo:hi]), _p(self.grad[lo:hi]), buf, hi - lo, _p(self.state), self.momentum,
-                   self.dampening, self.wd, int(self.nesterov), s)
+        name, gmul = self._scaled('fami_sgd')
+        lib().call(name, _p(self.p[lo:hi]), _p(self.grad[lo:hi]), None if self.momentum == 0.0 else _p(self.buf[lo:hi]),
+                   hi - lo, _p(self.state), self.momentum, self.dampening, self.wd, int(self.nesterov), *gmul, s)
 
 
 def _check_gmul(t, like):
@@ -741,7 +727,6 @@ class Trainer:
             self.accum = torch.zeros_like(self.grad)
             self._window_loss = torch.zeros(2, 7, device=self.dev)
         self._adam_split = self._find_adam_split(model)
-        self._adam_done = False
         self.views = {id(p): self.grad[o:o + n].view(p.shape) for p, o, n in self.table}
         # merged parameters (engine.CatParam): adjacent in the arena by construction -- one gradient view spanning the parts
         self.cats = []
@@ -862,9 +847,9 @@ class Trainer:
 
     # ------------------------------------------------------------------ the step (eager launch sequence)
     def _forward_backward(self, kf_x, sup_x, target, weight, on_bucket=None, fused_opt=False):
-        """Enqueue forward, loss and backward of one batch.  fused_opt (set only by _eager_step / _capture_plan): the Adam update
-        may be enqueued from INSIDE the backward pass in two parts (_find_adam_split) -- the call then mutates the parameters and
-        sets `_adam_done` for the `_opt_step` that must follow.  Direct callers (tools, tests) get a pure gradient computation."""
+        """Enqueue forward, loss and backward of one batch.  fused_opt (set only by _single_step): the Adam update may be enqueued
+        from INSIDE the backward pass in two parts (_find_adam_split) -- the call then mutates the parameters, and _single_step
+        enqueues only the moving average behind it.  Direct callers (tools, tests) get a pure gradient computation."""
         model = self.model
         eng = Engine(self.dev, grad_views=self.views, dtype=self.act_dtype,
                      deterministic=getattr(model, 'deterministic', None), route=self.route)
@@ -873,7 +858,7 @@ class Trainer:
         if on_bucket is not None:
             eng.persist_lanes = False       # bucket hooks fire between forked regions: keep a join per module
         early = {'ev': None}
-        split = self._adam_split if (fused_opt and on_bucket is None and not self.ddp) else None
+        split = self._backward_split() if (fused_opt and on_bucket is None) else None
         if split is not None:
             # Adam in two parts (see _find_adam_split): the scalars now, everything but the stem stretch when backward reaches the
             # stage-2 boundary (side lane), the stem stretch behind the backward pass
@@ -1002,7 +987,6 @@ class Trainer:
                     o.apply(0, self.flat.numel(), eng.stream)
             if early['ev'] is not None:
                 eng.wait_main(early['ev'])
-            self._adam_done = True
         self.conv_flops = eng.conv_flops        # nn.Conv2d FLOPs of one step (forward + both gradients; reporting)
         if on_bucket is not None:
             self._flushing = True
@@ -1039,12 +1023,13 @@ class Trainer:
         lo, hi = off[id(hr.conv1.weight)], min(off[id(p)] for p in first)
         return (lo, hi) if 0 <= lo < hi else None
 
-    def _opt_step(self):
-        if self._adam_done:
-            self._adam_done = False
-            self._ema_step()
-            return
-        self._unscale()
+    def _update(self, fold=False):
+        """Everything between "the gradient arena holds this step's raw gradients" and the end of the step -- wherever a step
+        ends, eager or inside a capture: the one pass over the gradient arena (or none), the clip coefficient and the
+        loss-scale update, every group's optimizer step, the moving average.  fold: the accumulation arena is added inside
+        the pass (the single-process call that closes a window)."""
+        self._grad_pass(fold)
+        self._coef_and_scale_update(_stream(self.dev))
         self._step_optimizers()
         self._ema_step()
 
@@ -1057,6 +1042,11 @@ class Trainer:
                 flag[0].copy_(self.overflow[0])
             o.step(flag)
         self.opt.step(self.overflow)
+
+    def _backward_split(self):
+        """the arena range a _forward_backward(fused_opt=True) without bucket hooks splits the optimizers around
+        (_find_adam_split), None where it enqueues none: the one condition both it and _single_step behind it go by"""
+        return None if self.ddp else self._adam_split
 
     def _opt_tensors(self):
         """the parameter arena and every optimizer's device state (shared arenas once), with the loss-scaler vector, the
@@ -1073,30 +1063,32 @@ class Trainer:
     def _hyper_version(self):
         return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version, self._ema_version)
 
-    def _unscale(self):
-        """gradient arena *= 1 / (world * loss_scale): the data-parallel mean and the static loss scale in one pass.
-        With gradient clipping and / or a dynamic loss scale: the same pass reads 1 / scale from the device and leaves
-        the sum of squares of what it wrote (the standalone read-only reduction when there is nothing to multiply), then
-        the clip coefficient, then the scale update -- which must see the overflow flag before the optimizers' checked
-        prep clears it, once per step."""
-        if self.clip is not None or self.dynamic_scale:
-            return self._unscale_norm_update()
-        f = 1.0 / ((self.world if self.ddp else 1) * self.accum_steps * self.loss_scale)
-        if self.overflow is not None:
-            # static loss scaling (fp16): the same pass also looks for inf / NaN; Adam then skips the step
-            self._lc('fami_unscale_check_f32', _p(self.grad), self.grad.numel(), f, _p(self.overflow), _stream(self.dev))
-        elif f != 1.0:
-            self._lc('fami_axpby_f32', _p(self.grad), None, _p(self.grad), self.grad.numel(), f, 0.0, _stream(self.dev))
+    def _grad_factor(self):
+        """the host factor of the gradient pass, 1 / (world * accum_steps * loss_scale): the data-parallel mean, the mean over
+        a window's micro-batches and the static loss scale (a dynamic one is read from the device: 1 here)"""
+        return 1.0 / ((self.world if self.ddp else 1) * self.accum_steps * (1.0 if self.dynamic_scale else self.loss_scale))
 
-    def _unscale_norm_update(self):
-        s, n = _stream(self.dev), self.grad.numel()
-        f = 1.0 / ((self.world if self.ddp else 1) * self.accum_steps * (1.0 if self.dynamic_scale else self.loss_scale))
-        if self.dynamic_scale or f != 1.0:
-            self._lc('fami_unscale_check_sumsq_f32', _p(self.grad), n, f, _p(self.scaler_state[1:2]) if self.dynamic_scale else None,
-                     _p(self.overflow), _p(self._partials), s)
-        else:
-            self._lc('fami_sumsq_f32', _p(self.grad), n, _p(self._partials), s)
-        self._coef_and_scale_update(s)
+    def _grad_pass(self, fold):
+        """The one pass over the gradient arena in front of the optimizers, chosen by: guarded (an overflow flag exists),
+        clipping, dynamic scale, fold.  grad = (grad [+ accum]) * factor [* the device's 1 / scale], with the inf / NaN check
+        where the trainer is guarded and the sum of squares of what was written where it clips (a null flag / slab pointer
+        switches either off); the read-only reduction when clipping has nothing to multiply; no launch when there is
+        nothing to do.  The clip coefficient and the scale update behind it (_coef_and_scale_update) must see the overflow
+        flag before the optimizers' checked prep clears it, once per step."""
+        s, n, f = _stream(self.dev), self.grad.numel(), self._grad_factor()
+        inv = _p(self.scaler_state[1:2]) if self.dynamic_scale else None
+        flag, slab = _p(self.overflow), _p(self._partials)            # (null: unguarded / not clipping)
+        if fold:
+            self._lc('fami_accum_unscale_check_sumsq_f32', _p(self.grad), _p(self.accum), n, f, inv, flag, slab, s)
+        elif self.dynamic_scale or (self.clip is not None and f != 1.0):
+            self._lc('fami_unscale_check_sumsq_f32', _p(self.grad), n, f, inv, flag, slab, s)
+        elif self.clip is not None:
+            self._lc('fami_sumsq_f32', _p(self.grad), n, slab, s)
+        elif self.overflow is not None:
+            # static loss scaling (fp16): the same pass also looks for inf / NaN; Adam then skips the step
+            self._lc('fami_unscale_check_f32', _p(self.grad), n, f, flag, s)
+        elif f != 1.0:
+            self._lc('fami_axpby_f32', _p(self.grad), None, _p(self.grad), n, f, 0.0, s)
 
     def _coef_and_scale_update(self, s):
         """the clip coefficient from the slab, then the loss-scale update: both read the overflow flag the pass in front of them
@@ -1263,30 +1255,12 @@ class Trainer:
         self._lc('fami_axpby_f32', _p(self.grad), _p(self.accum) if self.window_position else None, _p(self.accum),
                  self.grad.numel(), 1.0, 1.0, _stream(self.dev))
 
-    def _close_window(self):
-        """the tail of a window's last call, single process: grad = (accum + grad) / (N * loss scale) with the check and the
-        slab in the same pass, then what _unscale_norm_update and _step_optimizers enqueue"""
-        s = _stream(self.dev)
-        f = 1.0 / (self.accum_steps * (1.0 if self.dynamic_scale else self.loss_scale))
-        self._lc('fami_accum_unscale_check_sumsq_f32', _p(self.grad), _p(self.accum), self.grad.numel(), f,
-                 _p(self.scaler_state[1:2]) if self.dynamic_scale else None, _p(self.overflow),
-                 _p(self._partials) if self.clip is not None else None, s)
-        self._coef_and_scale_update(s)
-        self._step_optimizers()
-        self._ema_step()
-
     def _exchange_window(self):
         """data parallel, a window's last call: grad = accum + grad, then every bucket's all-reduce (outside any graph)"""
         self._lc('fami_axpby_f32', _p(self.accum), _p(self.grad), _p(self.grad), self.grad.numel(), 1.0, 1.0, _stream(self.dev))
         for lo, hi in self.reducer.ranges():
             self.reducer.allreduce(lo, hi)
         self.reducer.wait()
-
-    def _ddp_tail(self):
-        """... and behind the exchange: the existing unscale path (1 / (world * N * loss scale)) and the optimizers"""
-        self._unscale()
-        self._step_optimizers()
-        self._ema_step()
 
     def _window_call_done(self, closing):
         """the loss parts of this call into the window sum (one 7-element launch; row 0: the open window, row 1: the last
@@ -1305,10 +1279,7 @@ class Trainer:
         only).  None without accumulation."""
         if self._window_loss is None:
             return None
-        p = (self._window_loss[1] / self.accum_steps).tolist()
-        a, b = self.alpha, self.beta
-        mi = a * (-b * p[1] + b * p[2] + p[3] - p[4] + p[5] - p[6]) if self.use_mi else 0.0
-        return p[0] + mi
+        return self._total_loss((self._window_loss[1] / self.accum_steps).tolist())
 
     def accum_state_dict(self):
         """The 'grad_accum' checkpoint entry: {'steps': N, 'position': k} and, inside a window (k > 0), the accumulation
@@ -1337,23 +1308,32 @@ class Trainer:
         outs = self._forward_backward(kf_x, sup_x, target, weight)
         if not closing:
             self._accumulate()
-        elif self.ddp:
-            self._exchange_window()
-            self._ddp_tail()
         else:
-            self._close_window()
+            if self.ddp:
+                self._exchange_window()
+            self._update(fold=not self.ddp)      # (behind the exchange the arena already is the window's sum)
         self._window_call_done(closing)
+        return outs
+
+    def _single_step(self, kf_x, sup_x, target, weight):
+        """A whole step of a single process without accumulation (eager, or inside the one captured graph).  With an
+        in-backward optimizer split the gradient pass (none: the split is off wherever one is needed) and the optimizers
+        were enqueued inside the backward pass: the moving average is what remains of the update."""
+        outs = self._forward_backward(kf_x, sup_x, target, weight, fused_opt=True)
+        if self._backward_split() is not None:
+            self._ema_step()
+        else:
+            self._update()
         return outs
 
     def _eager_step(self, kf_x, sup_x, target, weight):
         if self.accum_steps > 1:
             return self._accum_eager_step(kf_x, sup_x, target, weight)
-        if self.ddp:
-            outs = self._forward_backward(kf_x, sup_x, target, weight, on_bucket=self.reducer.allreduce)
-            self.reducer.wait()
-        else:
-            outs = self._forward_backward(kf_x, sup_x, target, weight, fused_opt=True)
-        self._opt_step()
+        if not self.ddp:
+            return self._single_step(kf_x, sup_x, target, weight)
+        outs = self._forward_backward(kf_x, sup_x, target, weight, on_bucket=self.reducer.allreduce)
+        self.reducer.wait()
+        self._update()
         return outs
 
     # ------------------------------------------------------------------ hipGraph capture / replay
@@ -1372,37 +1352,42 @@ class Trainer:
             if was:
                 gc.enable()
 
+    def _warm_up(self, run, times, state, buffers):
+        """`times` runs of `run` on a side stream before a capture (allocator + pack caches), rolled back.  state: the
+        parameters, every optimizer's device state and the scaler / clip / moving-average tensors (_opt_tensors) and the
+        overflow vector {raised, skipped steps} are restored; buffers: the module buffers are."""
+        keep = []
+        if state:
+            keep += self._opt_tensors() + ([] if self.overflow is None else [self.overflow])
+        if buffers:
+            keep += list(self.model.buffers())
+        snap = [t.clone() for t in keep]
+        side = torch.cuda.Stream(self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            for _ in range(times):
+                run()
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        for dst, src in zip(keep, snap):
+            dst.copy_(src)
+        torch.cuda.synchronize(self.dev)
+
     def _capture_plan(self, kf_x, sup_x, target, weight):
         st = {'kf': kf_x.clone(), 'sup': sup_x.clone(), 'target': target.clone(), 'weight': weight.clone()}
         if self.accum_steps > 1:
             return self._capture_accum_plan(st)
-        # warm-up on a side stream (allocator + pack caches).  The warm-up steps must not count as training steps: the
-        # parameters, Adam state and module buffers (BN running statistics, batch counters) are restored afterwards, so
-        # the first step() of a graph-mode Trainer is exactly one optimisation step, like the eager one.
-        snap = [t.clone() for t in self._opt_tensors()]
-        ovf = None if self.overflow is None else self.overflow.clone()     # {raised, skipped steps}: warm-up steps do not count
-        bufs = [(b, b.clone()) for b in self.model.buffers()]
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._eager_step(st['kf'], st['sup'], st['target'], st['weight'])
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for dst, src in zip(self._opt_tensors(), snap):
-            dst.copy_(src)
-        for b, src in bufs:
-            b.copy_(src)
-        if ovf is not None:
-            self.overflow.copy_(ovf)
-        torch.cuda.synchronize(self.dev)
+        batch = (st['kf'], st['sup'], st['target'], st['weight'])
+        # The warm-up steps must not count as training steps: the parameters, Adam state and module buffers (BN running
+        # statistics, batch counters) are restored afterwards, so the first step() of a graph-mode Trainer is exactly one
+        # optimisation step, like the eager one.
+        self._warm_up(lambda: self._eager_step(*batch), 2, state=True, buffers=True)
         if not self.ddp:
             g = torch.cuda.CUDAGraph()
             # (round 6 probe: capturing on a high-priority stream -- lane 0 is the step's critical path -- changes nothing:
             #  bf16 18.75 vs 18.70 ms, f32 44.78 vs 44.78, profiles/r06/ab_lane0_high_priority_*.txt)
             with torch.cuda.graph(g):
-                outs = self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'], fused_opt=True)
-                self._opt_step()
+                outs = self._single_step(*batch)
             plan = [('graph', g)]
         elif self.ddp_plan == 'serial':
             # graph 1 = forward + backward, then the bucketed all-reduce of the flat gradient arena (RCCL, outside any
@@ -1411,15 +1396,13 @@ class Trainer:
             g1 = torch.cuda.CUDAGraph()
             # thread_local: RCCL's watchdog thread may query events while this thread captures
             with torch.cuda.graph(g1, pool=pool, capture_error_mode='thread_local'):
-                outs = self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'])
+                outs = self._forward_backward(*batch)
             plan = [('graph', g1)]
             plan += [('allreduce', r) for r in self.reducer.ranges()]
             plan.append(('wait', None))
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, pool=pool, capture_error_mode='thread_local'):
-                self._unscale()
-                self._step_optimizers()
-                self._ema_step()
+                self._update()
             plan.append(('graph', g2))
         else:
             outs, plan = self._capture_overlap(st)
@@ -1433,22 +1416,13 @@ class Trainer:
         touches the accumulation arena, the window position or the window loss sum, so a shape first seen in the middle of
         a window (the smaller last batch of an epoch) leaves the open window as it was; module buffers (BN running
         statistics, batch counters) are restored, and the gradient arena is rewritten by the replay that follows."""
-        bufs = [(b, b.clone()) for b in self.model.buffers()]
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'])
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for b, src in bufs:
-            b.copy_(src)
-        torch.cuda.synchronize(self.dev)
+        batch = (st['kf'], st['sup'], st['target'], st['weight'])
+        self._warm_up(lambda: self._forward_backward(*batch), 2, state=False, buffers=True)
         # (thread_local: RCCL's watchdog thread may query events while this thread captures)
         kw = {'capture_error_mode': 'thread_local'} if self.ddp else {}
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, **kw):
-            outs = self._forward_backward(st['kf'], st['sup'], st['target'], st['weight'])
+            outs = self._forward_backward(*batch)
         if self._tail is None or self._tail[1] != self._hyper_version():
             self._tail = (self._capture_tail(kw), self._hyper_version())
         return ([('graph', g)], st, outs, self._hyper_version())
@@ -1457,23 +1431,10 @@ class Trainer:
         """The graph a window's last call replays behind its backward pass (and, data parallel, behind the exchange): the
         closing pass, coefficient, scale update and optimizers.  Its one warm-up run is rolled back (parameters, optimizer
         state, scaler and clip vectors, overflow flag and count); it only reads the accumulation arena."""
-        tail = self._ddp_tail if self.ddp else self._close_window
-        snap = [t.clone() for t in self._opt_tensors()]
-        ovf = None if self.overflow is None else self.overflow.clone()
-        side = torch.cuda.Stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            tail()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for dst, src in zip(self._opt_tensors(), snap):
-            dst.copy_(src)
-        if ovf is not None:
-            self.overflow.copy_(ovf)
-        torch.cuda.synchronize(self.dev)
+        self._warm_up(lambda: self._update(fold=not self.ddp), 1, state=True, buffers=False)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, **kw):
-            tail()
+            self._update(fold=not self.ddp)
         return g
 
     def _capture_overlap(self, st):
@@ -1519,9 +1480,7 @@ class Trainer:
             g2 = torch.cuda.CUDAGraph()
             g2.capture_begin(pool=pool, capture_error_mode='thread_local')
             try:
-                self._unscale()
-                self._step_optimizers()
-                self._ema_step()
+                self._update()
             finally:
                 g2.capture_end()
             plan.append(('graph', g2))
@@ -1581,7 +1540,10 @@ class Trainer:
 
     def loss_value(self):
         """Total loss of the last step (host float; forces a sync -- logging only)."""
-        p = self.loss_parts.tolist()
+        return self._total_loss(self.loss_parts.tolist())
+
+    def _total_loss(self, p):
+        """[mse * W, mi_1..mi_6] -> the loss the reference optimises (core fn :119-148)"""
         a, b = self.alpha, self.beta
         mi = a * (-b * p[1] + b * p[2] + p[3] - p[4] + p[5] - p[6]) if self.use_mi else 0.0
         return p[0] + mi
