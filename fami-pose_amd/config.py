@@ -42,7 +42,9 @@ def default_cfg(width=48, num_joints=17, freeze_backbone=False, name='Alignment_
                            'NUM_CHANNELS': [w, 2 * w, 4 * w, 8 * w], 'FUSE_METHOD': 'SUM'}}},
         'DATASET': {'BBOX_ENLARGE_FACTOR': 1.25},
         'TRAIN': {'ROT_FACTOR': 45, 'SCALE_FACTOR': 0.35, 'LR': 1e-3, 'LR_STEP': [8, 12, 16], 'LR_FACTOR': 0.1,
-                  'OPTIMIZER': 'adam'},
+                  'OPTIMIZER': 'adam',
+                  # augmentation draws (data.draw_augmentation), Base_PoseTrack17.yaml:99-101
+                  'FLIP': True, 'NUM_JOINTS_HALF_BODY': 8, 'PROB_HALF_BODY': 0.3},
         'LOSS': {'HEATMAP_MSE': {'USE': True, 'WEIGHT': 1.0}},
         # flip testing (evaluate.flip_test_options); the reference's defaults, posetimation/config/mppe_config.py:322-346
         'VAL': {'FLIP_VAL': False, 'SHIFT_HEATMAP': False},

@@ -491,6 +491,32 @@ int fami_warp_normalize_u8(const unsigned char* src, float* out, int F, int Hs, 
                            long out_stride, double m00, double m01, double m02, double m10, double m11, double m12,
                            int flip, int swap_rb, float mean0, float mean1, float mean2, float std0, float std1,
                            float std2, fami_stream_t stream);
+/* The same crop for every frame of every clip of a BATCH in one launch: the B x (1 + supporting) cv2.warpAffine calls
+ * and transforms of one minibatch (PoseTrack_Alignment.py:416-428 per sample; in evaluation many person boxes cropped
+ * from the same five frames, :380-443).  Per pixel it is fami_warp_normalize_u8's arithmetic, expression for
+ * expression (one shared device function): the output is bit for bit what B pairs of per-clip calls write.
+ * table: DEVICE memory the caller owns, fami_warp_batch_table_bytes(B, F) bytes (-1 for B <= 0 or F <= 0), 8-byte
+ *   aligned: first B fami_warp_clip_t records, then B*F source pointers `const unsigned char*`, pointer [b*F + f] = frame
+ *   f of clip b ([Hs][Ws][3] 8-bit HWC, contiguous), the key frame at f = 0.  Pointers are per (clip, frame): clips may
+ *   name the same frame, and the frames of a clip need not be adjacent.  All frames of a clip share the clip's Hs, Ws;
+ *   clips may differ.  The table is in memory, not in the arguments, because B*F pointers outgrow the kernel-argument
+ *   block at evaluation batch sizes; a workgroup reads its clip's record through a uniform index, once.
+ * key [B,3,Hd,Wd], sup [B,3(F-1),Hd,Wd] fp32: frame 0 of clip b -> key[b], frame f >= 1 -> channels 3(f-1)..3f-1 of
+ *   sup[b]; sup may be null when F == 1.  swap_rb, mean, std: for the whole batch.
+ * Checked here (-1, no launch): null table / key, null sup with F > 1, B <= 0 (or > 65535, the grid's y extent), F <= 0,
+ * Hd*Wd >= 2^31, a zero std.  The records live in device memory and are NOT checked: the caller guarantees
+ * 0 < Hs, Ws < 32768 and non-null frames (fami_pose_amd.data.ClipBatcher does).  Grid: pixels x clips, one thread per
+ * output pixel of all F frames; the library allocates nothing. */
+typedef struct fami_warp_clip_t {
+  double m[6];  /* inverse map (dst -> src) of the clip, row-major 2x3: fami_warp_normalize_u8's m00..m12 */
+  int flip;     /* source mirrored in x first */
+  int Hs, Ws;   /* size of every source frame of the clip */
+  int reserved; /* 0 (pads the record to 64 bytes) */
+} fami_warp_clip_t;
+long fami_warp_batch_table_bytes(int B, int F);
+int fami_warp_normalize_batch_u8(const void* table, float* key, float* sup, int B, int F, int Hd, int Wd, int swap_rb,
+                                 float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                 fami_stream_t stream);
 
 
 /* ======================================================================================================
