@@ -17,7 +17,8 @@ _os.environ.setdefault('HIP_FORCE_DEV_KERNARG', '1')
 from .config import CfgNode, default_cfg
 from .zoo import (MODEL_REGISTRY, CORE_FUNCTION_REGISTRY, DATASET_REGISTRY, TRAIN_PHASE, VAL_PHASE, TEST_PHASE,
                   build_model, get_model_hyperparameter, Alignment_V15, HRNet, HRNetPlus)
+from .train import freeze_batchnorm
 
 __all__ = ['CfgNode', 'default_cfg', 'MODEL_REGISTRY', 'CORE_FUNCTION_REGISTRY', 'DATASET_REGISTRY', 'TRAIN_PHASE',
            'VAL_PHASE', 'TEST_PHASE', 'build_model', 'get_model_hyperparameter', 'Alignment_V15', 'HRNet',
-           'HRNetPlus']
+           'HRNetPlus', 'freeze_batchnorm']

@@ -37,6 +37,11 @@ entry into an EMA Trainer; a parameter name or shape that does not match raises 
 EMA Trainer resuming a file without the entry restarts its average from the loaded weights (reset_ema: `resume` copies into
 the parameters in place, so the average taken at construction would be stale).  A Trainer without an EMA ignores the entry
 and writes exactly the keys above.
+
+A Trainer with frozen BatchNorm statistics (frozen_bn / train.freeze_batchnorm; the flags live on the model's modules) adds
+``'frozen_bn'``: the list of the frozen modules' names in ``named_modules()`` order.  `resume` into a model whose frozen set
+differs -- none included -- raises ValueError naming both sets, before anything is loaded.  A file without the entry says nothing about the set (pretrained
+weights, a run that trained the statistics) and loads into any Trainer.  Without the option the keys are unchanged.
 """
 import os
 import os.path as osp
@@ -243,6 +248,10 @@ def save_checkpoint(epoch, save_folder, model, optimizer, **kwargs):
     ema = [o for o in opts if getattr(o, 'ema', None) is not None]
     if ema:
         ckpt['ema'] = ema[0].ema_state_dict()
+    from .train import frozen_batchnorm_names
+    frozen = [k[7:] if k.startswith('module.') else k for k in frozen_batchnorm_names(model)]
+    if frozen:
+        ckpt['frozen_bn'] = frozen
     torch.save(ckpt, path)
     return path
 
@@ -260,6 +269,12 @@ def resume(model, optimizer, checkpoint_file, **kwargs):
         for o in opts:
             if getattr(o, 'ema', None) is not None:
                 o.check_ema_state_dict(ckpt['ema'])
+    if 'frozen_bn' in ckpt:           # likewise: a run with another frozen set is another run
+        from .train import frozen_batchnorm_names
+        own = [k[7:] if k.startswith('module.') else k for k in frozen_batchnorm_names(model)]
+        if list(ckpt['frozen_bn']) != own:
+            raise ValueError('the checkpoint was written with frozen_bn=%r, this model has frozen_bn=%r' %
+                             (list(ckpt['frozen_bn']), own))
     sd = _strip_module(ckpt['state_dict'])
     sd = {(k[7:] if k.startswith('preact.') else k): v for k, v in sd.items()}
     with torch.no_grad():

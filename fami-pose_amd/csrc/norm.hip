@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
   }
 }
 
-// coef[0][c] = mean(dz), coef[1][c] = mean(dz*xhat); dgamma/dbeta optional
+// coef[0][c] = mean(dz), coef[1][c] = mean(dz*xhat) (coef optional); dgamma/dbeta optional
 __global__ void bn_bwd_finalize_kernel(const float* __restrict__ partial, int G, long P, int C, float* coef,
                                        float* dgamma, float* dbeta, int accumulate) {
   __shared__ double sm4[4];
@@ -292,8 +292,10 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ partial, int G,
   s = block_sum_d(s, sm4);
   q = block_sum_d(q, sm4);
   if (threadIdx.x != 0) return;
-  coef[c] = (float)(s / (double)P);
-  coef[C + c] = (float)(q / (double)P);
+  if (coef) {  // null: the frozen-statistics backward has no batch terms and wants the two parameter sums only
+    coef[c] = (float)(s / (double)P);
+    coef[C + c] = (float)(q / (double)P);
+  }
   if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
   if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
 }
@@ -337,6 +339,100 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
       if (acc_dres) r += ld4(dres + o);
       st4(dres + o, r);
     }
+  }
+}
+
+// ---- backward with FROZEN statistics (eval-mode BatchNorm, Engine.bn_batch_stats false): mean / invstd are constants, not
+// functions of x, so the batch terms of the train-mode backward vanish and ONE pass does it:
+//   dz = relu ? dy*(y>0) : dy ; dx (=|+=) dz*gamma*invstd ; dres (=|+=) dz
+// SUMS: the workgroup also leaves partial[g][0][c] = sum dz, partial[g][1][c] = sum dz*xhat for bn_bwd_finalize_kernel
+// (fixed order, fp64: run-to-run bitwise).  Without SUMS (gamma / beta frozen too) x and mean are never read: dy (+ y) in,
+// dx out.  BN_U rows per thread in flight; rows past the end re-read row p (a cache hit), contribute an exact 0 to the sums
+// and store nothing.
+template <typename T, bool SUMS>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                          const T* __restrict__ y, const float* __restrict__ mean,
+                                                          const float* __restrict__ invstd,
+                                                          const float* __restrict__ gamma, float* __restrict__ partial,
+                                                          T* dx, T* dres, long P, int C, int relu, int acc_dx,
+                                                          int acc_dres) {
+  extern __shared__ float sm[];  // SUMS: [rows][2][C]
+  const ColMap m = col_map(C);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+  if (m.active) {
+    f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is, gi;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int c = m.cv * 4 + t;
+      is[t] = invstd[c];
+      gi[t] = gamma[c] * is[t];
+      if (SUMS) mu[t] = mean[c];
+    }
+    const long step = (long)gridDim.x * m.rows;
+    for (long p = (long)blockIdx.x * m.rows + m.prow; p < P; p += BN_U * step) {
+      f32x4 g[BN_U], yy[BN_U], xx[BN_U], dd[BN_U], rr[BN_U];
+      long o[BN_U];
+#pragma unroll
+      for (int u = 0; u < BN_U; ++u) {
+        const long pu = p + u * step;
+        o[u] = (pu < P ? pu : p) * C + m.cv * 4;
+        g[u] = ld4(dy + o[u]);
+      }
+      if (relu) {
+#pragma unroll
+        for (int u = 0; u < BN_U; ++u) yy[u] = ld4(y + o[u]);
+      }
+      if (SUMS) {
+#pragma unroll
+        for (int u = 0; u < BN_U; ++u) xx[u] = ld4(x + o[u]);
+      }
+      if (acc_dx) {
+#pragma unroll
+        for (int u = 0; u < BN_U; ++u) dd[u] = ld4(dx + o[u]);
+      }
+      if (dres && acc_dres) {
+#pragma unroll
+        for (int u = 0; u < BN_U; ++u) rr[u] = ld4(dres + o[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < BN_U; ++u) {
+        if (relu) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) g[u][t] = yy[u][t] > 0.f ? g[u][t] : 0.f;
+        }
+        const bool in = p + u * step < P;
+        if (SUMS) {
+          const f32x4 gz = in ? g[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+          s += gz;
+          q += gz * ((xx[u] - mu) * is);
+        }
+        if (in) {
+          f32x4 d = g[u] * gi;
+          if (acc_dx) d += dd[u];
+          st4(dx + o[u], d);
+          if (dres) {
+            f32x4 r = g[u];
+            if (acc_dres) r += rr[u];
+            st4(dres + o[u], r);
+          }
+        }
+      }
+    }
+    if (SUMS) {
+      float* d = sm + (long)m.prow * 2 * C;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        d[m.cv * 4 + t] = s[t];
+        d[C + m.cv * 4 + t] = q[t];
+      }
+    }
+  }
+  if (!SUMS) return;
+  __syncthreads();
+  for (int e = threadIdx.x; e < 2 * C; e += 256) {
+    float tot = 0.f;
+    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
+    partial[(long)blockIdx.x * 2 * C + e] = tot;
   }
 }
 
@@ -891,6 +987,37 @@ static int bn_bwd_impl(const T* dy, const T* x, const T* y, const float* mean, c
   return FAMI_OK;
 }
 
+// frozen-statistics backward: one data pass (+ a channel-sized finalize when dgamma / dbeta are wanted)
+template <typename T>
+static int bn_eval_bwd_impl(const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
+                            const float* gamma, T* dx, float* dgamma, float* dbeta, T* dres, long P, int C, int relu,
+                            int acc_dx, int acc_param, int acc_dres, float* ws, hipStream_t s, const char* nm) {
+  FAMI_REQUIRE(dy && invstd && gamma && dx, nm, "null pointer");
+  FAMI_REQUIRE(!relu || y, nm, "relu needs y");
+  if (!bn_shape_ok(P, C)) {
+    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
+    return FAMI_ESHAPE;
+  }
+  const int rows = 256 / (C >> 2);
+  if (!dgamma && !dbeta) {  // gamma / beta frozen too: no sums, no workspace, no second launch; x and mean are not read
+    long g = (P + (long)rows * BN_U - 1) / ((long)rows * BN_U);
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL((bn_eval_bwd_kernel<T, false>), dim3((int)g), dim3(256), 0, s, dy, x, y, mean, invstd, gamma,
+                       (float*)nullptr, dx, dres, P, C, relu, acc_dx, acc_dres);
+    FAMI_CHECK_LAUNCH(nm);
+    return FAMI_OK;
+  }
+  FAMI_REQUIRE(x && mean && ws, nm, "parameter sums need x, mean and ws");
+  const int G = bn_grid(P, C);  // <= BN_MAXG partial rows: the whole of fami_bn_workspace(C)
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, true>), dim3(G), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, dy, x, y,
+                     mean, invstd, gamma, ws, dx, dres, P, C, relu, acc_dx, acc_dres);
+  FAMI_CHECK_LAUNCH(nm);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, ws, G, P, C, (float*)nullptr, dgamma, dbeta,
+                     acc_param);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+
 // train-mode BatchNorm forward in one call: statistics (+ running-stat update) and apply (+ residual, + ReLU).
 // Small tensors take the single-launch kernel, large ones the three-launch path.
 template <typename T>
@@ -1085,6 +1212,14 @@ int fami_bn_running_update_batch_f32(const long* ptrs, const float* meta, int n,
                         int acc_dx, int acc_param, int acc_dres, float* ws, hipStream_t s) {                           \
     return bn_bwd_impl<T>(dy, x, y, mean, invstd, gamma, dx, dgamma, dbeta, dres, P, C, relu, acc_dx, acc_param,       \
                           acc_dres, ws, s, "fami_bn_bwd_" #sfx);                                                       \
+  }                                                                                                                    \
+  /* the same with mean / invstd FROZEN (eval-mode statistics): dx (=|+=) dz*gamma*invstd, dgamma (=|+=) sum dz*xhat, */ \
+  /* dbeta (=|+=) sum dz, in one data pass; dgamma and dbeta both null: no sums, ws / x / mean unused                 */ \
+  int fami_bn_eval_bwd_##sfx(const T* dy, const T* x, const T* y, const float* mean, const float* invstd,              \
+                             const float* gamma, T* dx, float* dgamma, float* dbeta, T* dres, long P, int C, int relu, \
+                             int acc_dx, int acc_param, int acc_dres, float* ws, hipStream_t s) {                      \
+    return bn_eval_bwd_impl<T>(dy, x, y, mean, invstd, gamma, dx, dgamma, dbeta, dres, P, C, relu, acc_dx, acc_param,  \
+                               acc_dres, ws, s, "fami_bn_eval_bwd_" #sfx);                                             \
   }                                                                                                                    \
   /* train-mode forward, statistics + apply in one call (one launch for P <= 16384 pixels) */                         \
   int fami_bn_train_fwd_##sfx(const T* x, const T* residual, T* y, const float* gamma, const float* beta,              \

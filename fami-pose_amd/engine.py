@@ -959,6 +959,13 @@ class Engine:
             self.record_bwd(bwd, [weight, bias], (x,))
         return out
 
+    @staticmethod
+    def bn_batch_stats(bn):
+        """Does this BatchNorm normalise with the statistics of the batch (and update its running statistics)?  The one
+        predicate every BatchNorm path asks: eval mode and `frozen_stats` (train.freeze_batchnorm) both say no -- the
+        eval-mode forward, no train-only fusion, no running-statistics update, the one-pass backward fami_bn_eval_bwd_*."""
+        return bn.training and not getattr(bn, 'frozen_stats', False)
+
     def bn_fusable(self, P, C):
         """Can the statistics passes of a train-mode BatchNorm over [P, C] run in a convolution epilogue?"""
         return C % 4 == 0 and 4 <= C <= 1024 and not self.Q.fami_bn_is_small(P, C)
@@ -980,7 +987,7 @@ class Engine:
         st, pd, dl = conv.stride[0], conv.padding[0], conv.dilation[0]
         Ho = (H + 2 * pd - dl * (kh - 1) - 1) // st + 1
         Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
-        if (bn.training and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
+        if (self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
                 and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)):
             slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
             z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
@@ -1000,16 +1007,16 @@ class Engine:
         Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
         P = N * Ho * Wo
         okq = self.Q.fami_conv2d_xbn_ok if self.half else self.Q.fami_conv2d_xbn_ok_f32
-        ok = (self.use_xbn and self.bn2 and self.defer_reduce and bn.training and self.fuse_bn_fwd
+        ok = (self.use_xbn and self.bn2 and self.defer_reduce and self.bn_batch_stats(bn) and self.fuse_bn_fwd
               and self.defer_bn is None and bn.running_mean is not None and self.bn_fusable(P, Co)
               and tuple(nxt.weight.shape[1:]) == (Co, 3, 3) and nxt.stride[0] == 1 and nxt.padding[0] == 1
               and nxt.dilation[0] == 1 and okq(N, Ho, Wo, Co, nxt.weight.shape[0]))
         if not ok:
-            if self.abl_bn1 and bn.training and self.fuse_bn_fwd and self.bn_fusable(P, Co):
+            if self.abl_bn1 and self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(P, Co):
                 return self._abl_bn1(x, conv, bn, st, pd, dl, Co)
             # 16-bit storage (round 6): the normalised tensor IS written, but by `nxt`'s own launch (Engine.conv takes the pending
             # apply pass: fami_conv2d_fwd_bnin_*) -- where conv's epilogue takes the statistics and the weight-resident kernel takes nxt
-            if (self.bn_in and bn.training and self.fuse_bn_fwd and self.bn_fusable(P, Co)
+            if (self.bn_in and self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(P, Co)
                     and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)
                     and tuple(nxt.weight.shape[1:]) == (Co, 3, 3) and nxt.stride[0] == 1 and nxt.padding[0] == 1
                     and nxt.dilation[0] == 1 and self.Q.fami_conv2d_fwd_bnin_ok(N, Ho, Wo, Co, nxt.weight.shape[0])):
@@ -1068,7 +1075,8 @@ class Engine:
         mean, invstd = self.empty(C), self.empty(C)
         y = self.like(x.data)
         pending = None
-        if bn.training:
+        training = self.bn_batch_stats(bn)
+        if training:
             deferred = self.defer_bn is not None and bn.running_mean is not None
             if not deferred:
                 self._lane_guard(('running statistics', id(bn)))
@@ -1109,7 +1117,6 @@ class Engine:
         out = T(y, rg)
         out.pending = pending
         if rg:
-            training = bn.training
             # ReLU mask in backward: from y when a residual was added, else recomputed from x (one tensor read less)
             rmode = (1 if residual is not None else 2) if relu else 0
             rec = None
@@ -1128,8 +1135,6 @@ class Engine:
                     if x.requires_grad:
                         x.grad = out.grad
                     return
-                if not training:
-                    raise NotImplementedError("backward through eval-mode BatchNorm is outside the training hot path")
                 gx, accx = self.gbuf(x) if x.requires_grad else (self.act(*shp), 0)
                 gg = gb = None
                 accp = 0
@@ -1139,7 +1144,12 @@ class Engine:
                 gr, accr = (None, 0)
                 if residual is not None and residual.requires_grad:
                     gr, accr = self.gbuf(residual)
-                if rec is not None and rec['pre_bwd'] is not None:
+                if not training:
+                    # frozen statistics: no batch terms, one pass; the mask comes from the stored y
+                    self.acall('fami_bn_eval_bwd', _p(out.grad), _p(x.data), _p(y), _p(mean), _p(invstd),
+                               _p(bn.weight.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, int(relu), accx, accp, accr,
+                               _p(self.ws(self.Q.fami_bn_workspace(C)) if need_p else None))
+                elif rec is not None and rec['pre_bwd'] is not None:
                     # out.grad holds dz (mask applied) and the slot rows the two sums: fami_conv2d_dgrad_bnstats_*
                     self.acall('fami_bn_bwd_apply_slots', _p(out.grad), _p(x.data), _p(mean), _p(invstd),
                                _p(bn.weight.data), _p(bn.bias.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, accx, accp,
@@ -1165,7 +1175,7 @@ class Engine:
         st, pd, dl = conv.stride[0], conv.padding[0], conv.dilation[0]
         Ho = (H + 2 * pd - dl * (kh - 1) - 1) // st + 1
         Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
-        if (bn.training and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
+        if (self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
                 and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)):
             slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
             z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
@@ -1181,7 +1191,7 @@ class Engine:
         if bn is not None:
             Pk = x.data.numel() // C
             mean, invstd = self.empty(C), self.empty(C)
-            if bn.training:
+            if self.bn_batch_stats(bn):
                 self._lane_guard(('running statistics', id(bn)))
                 mom = 0.1 if bn.momentum is None else bn.momentum
                 if pre is not None:
@@ -1193,10 +1203,12 @@ class Engine:
                                _p(bn.running_var), float(mom), float(bn.eps), _p(ws))
                 self.bn_trained.append(bn)
             else:
+                assert pre is None
                 self.call('fami_bn_eval_stats_f32', _p(bn.running_mean), _p(bn.running_var), _p(mean), _p(invstd),
                           C, float(bn.eps))
             h['stats'] = (mean, invstd)
         need_p = bn is not None and self.rq(bn.weight)
+        training = bn is not None and self.bn_batch_stats(bn)
         if self.record and (x.requires_grad or need_p):
             def bwd():
                 out = h['out']
@@ -1209,8 +1221,6 @@ class Engine:
                         g, acc = self.gbuf(x)
                         self.acall('fami_relu_bwd', _p(dy), _p(y), _p(g), y.numel(), acc)
                     return
-                if not bn.training:
-                    raise NotImplementedError("backward through eval-mode BatchNorm")
                 Pk = x.data.numel() // C
                 gx, accx = self.gbuf(x) if x.requires_grad else (self.like(x.data), 0)
                 gg = gb = None
@@ -1219,6 +1229,18 @@ class Engine:
                     gg, accp = self.pgrad(bn.weight)
                     gb, _ = self.pgrad(bn.bias)
                 st = h['stats']
+                if not training:
+                    # frozen statistics: one pass (fami_bn_eval_bwd_*), after the pooled ReLU backward for an upsampled term
+                    ws = self.ws(self.Q.fami_bn_workspace(C)) if need_p else None
+                    if shift == 0:
+                        self.acall('fami_bn_eval_bwd', _p(dy), _p(x.data), _p(y), _p(st[0]), _p(st[1]),
+                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 1, accx, accp, 0, _p(ws))
+                    else:
+                        low = self.like(x.data)
+                        self.acall('fami_pool_relu_bwd', _p(dy), _p(y), _p(low), N, H >> shift, W >> shift, C, shift, 1)
+                        self.acall('fami_bn_eval_bwd', _p(low), _p(x.data), None, _p(st[0]), _p(st[1]),
+                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 0, accx, accp, 0, _p(ws))
+                    return
                 # two-launch form (statistics into fp64 slot rows, finalize folded into the apply pass) where the BatchNorm is
                 # large enough for it -- the three-launch form's one-workgroup finalize sat between the two passes of all 53
                 # fuse-term BatchNorms of a step (5 us each)

@@ -254,6 +254,48 @@ class MultiStepLR:
         self.opt.set_lr(self.get_last_lr()[0])
 
 
+def frozen_batchnorm_names(model):
+    """Names (named_modules() order) of the BatchNorm2d modules whose statistics are frozen (freeze_batchnorm)."""
+    return [n for n, m in model.named_modules()
+            if isinstance(m, torch.nn.BatchNorm2d) and getattr(m, 'frozen_stats', False)]
+
+
+def freeze_batchnorm(model, scope):
+    """Freeze the statistics of BatchNorm2d modules of `model` (`norm_eval` / FrozenBatchNorm of other toolboxes): a frozen
+    BatchNorm normalises with its running statistics in train mode too, leaves them and num_batches_tracked untouched,
+    still propagates gradients and still trains gamma / beta (set requires_grad = False on those to fix them as well).
+    scope: 'all'; 'backbone' (module names under `hrnet.`); a tuple of module-name prefixes (or one prefix that is
+    neither word); None clears the flag everywhere.  The modules in scope get `frozen_stats = True`, every other
+    BatchNorm2d loses the flag: the call states the whole set.  -> the frozen names in named_modules() order.  A
+    prefix that matches no BatchNorm2d raises ValueError (nothing is changed then).  The flag is a plain attribute:
+    model.train() / model.eval() do not touch it and state_dict() does not carry it.  The reference has no such switch:
+    its MODEL.FREEZE_HRNET_WEIGHTS stops the weights and lets the statistics follow every batch."""
+    bns = [(n, m) for n, m in model.named_modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    if scope is None:
+        prefixes = ()
+    elif scope == 'all':
+        prefixes = ('',)
+    elif scope == 'backbone':
+        prefixes = ('hrnet.',)
+    elif isinstance(scope, str):
+        prefixes = (scope,)
+    else:
+        prefixes = tuple(scope)
+        if not prefixes or not all(isinstance(q, str) for q in prefixes):
+            raise ValueError("scope is None, 'all', 'backbone' or a tuple of module-name prefixes, not %r" % (scope,))
+    for q in prefixes:
+        if not any(n.startswith(q) for n, _ in bns):
+            raise ValueError('no BatchNorm2d module name starts with %r' % (q,))
+    names = []
+    for n, m in bns:
+        if any(n.startswith(q) for q in prefixes):
+            m.frozen_stats = True
+            names.append(n)
+        elif 'frozen_stats' in m.__dict__:
+            del m.frozen_stats
+    return names
+
+
 def flatten_parameters(model):
     """Move every trainable parameter into one flat arena (views keep names/shapes). -> (flat, [(param, off, n)])"""
     ps = [p for p in model.parameters() if p.requires_grad]
@@ -637,20 +679,31 @@ class Trainer:
     counters are NOT averaged -- they are running averages already -- so the averaged weights are used with the live
     buffers.  ema_weights() puts the average into the model (and takes it out again) by exchanging the two arenas in
     place; ema_state_dict() is the checkpoint entry.  None (default): no arena, none of these launches.
+
+    frozen_bn = 'all' | 'backbone' | prefixes: BatchNorm with frozen statistics (freeze_batchnorm) -- those modules normalise
+    with their running statistics (the eval-mode forward: fami_bn_eval_stats_f32 + fami_bn_apply_*), leave them and their
+    batch counters untouched and run the one-pass backward fami_bn_eval_bwd_*; gamma / beta keep training unless the caller
+    set requires_grad = False on them.  No train-only BatchNorm fusion is taken for a frozen module.  The set of frozen
+    modules keys the captured plans next to the optimizer hyper-parameters: a later freeze_batchnorm call re-captures.
+    The reference has no such switch, so there is no config key; None (default) leaves every launch as it is.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
                  weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, frozen_bn=None):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
         from a reference config.  max_grad_norm / loss_scale='dynamic' / scaler: see the class docstring (the reference
         configuration has no such keys: from_cfg takes them as keyword arguments).  accum_steps: micro-batches per update
         (class docstring; None = 1).  ema_decay / ema_warmup: the moving average of the weights (class docstring; None =
-        none)."""
+        none).  frozen_bn: None, 'all', 'backbone' or module-name prefixes -- freeze_batchnorm(model, frozen_bn) before
+        anything is captured (class docstring; None leaves the model's flags as they are)."""
+        if frozen_bn is not None:
+            freeze_batchnorm(model, frozen_bn)
+        self._bn_modules = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
         if ema_decay is None and ema_warmup:
             raise ValueError('ema_warmup=True needs an ema_decay')
         self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay)
@@ -1060,8 +1113,17 @@ class Trainer:
                     out.append(t)
         return out
 
+    def _frozen_key(self):
+        """which BatchNorm modules have frozen statistics right now: part of what keys a captured plan"""
+        return tuple(k for k, m in enumerate(self._bn_modules) if getattr(m, 'frozen_stats', False))
+
+    def frozen_bn_names(self):
+        """-> the names of the model's BatchNorm modules with frozen statistics (the 'frozen_bn' checkpoint entry)"""
+        return frozen_batchnorm_names(self.model)
+
     def _hyper_version(self):
-        return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version, self._ema_version)
+        return tuple(o.hyper_version for o in self.optimizers) + (self._scaler_version, self._ema_version,
+                                                                  self._frozen_key())
 
     def _grad_factor(self):
         """the host factor of the gradient pass, 1 / (world * accum_steps * loss_scale): the data-parallel mean, the mean over

@@ -166,6 +166,14 @@ int fami_bn_apply_f32(const float* x, const float* mean, const float* invstd, co
 int fami_bn_bwd_f32(const float* dy, const float* x, const float* y, const float* mean, const float* invstd,
                     const float* gamma, float* dx, float* dgamma, float* dbeta, float* dres, long P, int C, int relu,
                     int acc_dx, int acc_param, int acc_dres, float* ws, fami_stream_t stream);
+/* Backward with FROZEN statistics (eval-mode BatchNorm: mean / invstd are constants): dz = relu ? dy*(y>0) : dy;
+ * dx (=|+=) dz*gamma*invstd; dres (=|+=) dz; dbeta (=|+=) sum dz; dgamma (=|+=) sum dz*(x-mean)*invstd.  One data pass,
+ * plus a channel-sized fixed-order fp64 finalize when dgamma / dbeta are given (ws: fami_bn_workspace(C)); run-to-run
+ * bitwise.  dgamma and dbeta both NULL: no sums, one launch, x / mean / ws are not read. */
+int fami_bn_eval_bwd_f32(const float* dy, const float* x, const float* y, const float* mean,
+                     const float* invstd, const float* gamma, float* dx, float* dgamma, float* dbeta,
+                     float* dres, long P, int C, int relu, int acc_dx, int acc_param, int acc_dres, float* ws,
+                     fami_stream_t stream);
 /* Two-launch forms of the two calls above (fami_bn_{stats,finalize,apply,bwd}; the finalize launch is folded
  * into the apply pass): the statistics pass adds its partial sums into fp64 slot rows, every workgroup of the apply pass
  * folds them in its prologue.  `slots`: fami_bn_slots_bytes(C) bytes, ZERO on entry (the caller clears one arena per
@@ -596,6 +604,10 @@ int fami_bn_bwd_bf16(const fami_bf16_t* dy, const fami_bf16_t* x, const fami_bf1
                      const float* invstd, const float* gamma, fami_bf16_t* dx, float* dgamma, float* dbeta,
                      fami_bf16_t* dres, long P, int C, int relu, int acc_dx, int acc_param, int acc_dres, float* ws,
                      fami_stream_t stream);
+int fami_bn_eval_bwd_bf16(const fami_bf16_t* dy, const fami_bf16_t* x, const fami_bf16_t* y, const float* mean,
+                     const float* invstd, const float* gamma, fami_bf16_t* dx, float* dgamma, float* dbeta,
+                     fami_bf16_t* dres, long P, int C, int relu, int acc_dx, int acc_param, int acc_dres, float* ws,
+                     fami_stream_t stream);
 int fami_channel_sum_bf16(const fami_bf16_t* x, long P, int C, float* out, int accumulate, float* ws,
                           fami_stream_t stream);
 
@@ -722,6 +734,10 @@ int fami_bn_bwd2_f16(const fami_f16_t* dy, const fami_f16_t* x, const fami_f16_t
                      const float* gamma, const float* beta, fami_f16_t* dx, float* dgamma, float* dbeta, fami_f16_t* dres, long P,
                      int C, int relu, int acc_dx, int acc_param, int acc_dres, void* slots, fami_stream_t stream);
 int fami_bn_bwd_f16(const fami_f16_t* dy, const fami_f16_t* x, const fami_f16_t* y, const float* mean,
+                     const float* invstd, const float* gamma, fami_f16_t* dx, float* dgamma, float* dbeta,
+                     fami_f16_t* dres, long P, int C, int relu, int acc_dx, int acc_param, int acc_dres, float* ws,
+                     fami_stream_t stream);
+int fami_bn_eval_bwd_f16(const fami_f16_t* dy, const fami_f16_t* x, const fami_f16_t* y, const float* mean,
                      const float* invstd, const float* gamma, fami_f16_t* dx, float* dgamma, float* dbeta,
                      fami_f16_t* dres, long P, int C, int relu, int acc_dx, int acc_param, int acc_dres, float* ws,
                      fami_stream_t stream);
