@@ -11,9 +11,16 @@
 #include "common.h"
 
 // joints [B,J,2] (x,y in input-image pixels), vis [B,J] -> target [B,J,Hh,Wh], weight [B,J]
+// joint_w (or null): per-joint factors of the stored weight (heatmaps_process.py:200-201); the "> 0.5" test that decides
+// whether a map is drawn stays on the unmultiplied weight (:195-196).
+// SUB: the Gaussian is centred at the real-valued joint position (DARK's encoding) inside the window of the rounded
+// centre; (float)((double)x - joint / stride) is the integer x - mx whenever joint / stride is a non-negative integer, so
+// such a joint gets the quantised map bit for bit.
+template <bool SUB>
 __global__ void gauss_target_kernel(const float* __restrict__ joints, const float* __restrict__ vis,
-                                    float* __restrict__ target, float* __restrict__ weight, int B, int J, int Hh,
-                                    int Wh, double stride_x, double stride_y, int sigma) {
+                                    const float* __restrict__ joint_w, float* __restrict__ target,
+                                    float* __restrict__ weight, int B, int J, int Hh, int Wh, double stride_x,
+                                    double stride_y, int sigma) {
   const long HW = (long)Hh * Wh;
   const long total = (long)B * J * HW;
   const int r = sigma * 3;
@@ -23,19 +30,25 @@ __global__ void gauss_target_kernel(const float* __restrict__ joints, const floa
     const int hw = (int)(i - bj * HW);
     const int y = hw / Wh, x = hw - y * Wh;
     // int(v + 0.5) of the reference truncates toward zero, in double
-    const int mx = (int)((double)joints[bj * 2 + 0] / stride_x + 0.5);
-    const int my = (int)((double)joints[bj * 2 + 1] / stride_y + 0.5);
+    const double cx = (double)joints[bj * 2 + 0] / stride_x, cy = (double)joints[bj * 2 + 1] / stride_y;
+    const int mx = (int)(cx + 0.5);
+    const int my = (int)(cy + 0.5);
     const int x0 = mx - r, y0 = my - r, x1 = mx + r + 1, y1 = my + r + 1;
     float w = vis[bj];
     const bool outside = x0 >= Wh || y0 >= Hh || x1 < 0 || y1 < 0;
     if (outside) w = 0.f;
     float v = 0.f;
     if (!outside && w > 0.5f && x >= x0 && x < x1 && y >= y0 && y < y1) {
-      const int dx = x - mx, dy = y - my;
-      v = expf(-((float)(dx * dx + dy * dy)) / inv);
+      if constexpr (SUB) {
+        const float dx = (float)((double)x - cx), dy = (float)((double)y - cy);
+        v = expf(-(dx * dx + dy * dy) / inv);
+      } else {
+        const int dx = x - mx, dy = y - my;
+        v = expf(-((float)(dx * dx + dy * dy)) / inv);
+      }
     }
     target[i] = v;
-    if (hw == 0) weight[bj] = w;
+    if (hw == 0) weight[bj] = joint_w ? w * joint_w[bj % J] : w;
   }
 }
 
@@ -80,6 +93,41 @@ __global__ void scalar_sum_kernel(const float* __restrict__ rows, int R, double 
   if (lane == 0) sm[wave] = s;
   __syncthreads();
   if (threadIdx.x == 0) out[0] = (float)((sm[0] + sm[1] + sm[2] + sm[3]) * scale);
+}
+// Online hard keypoint mining: one workgroup walks the samples.  Per sample the J row sums go to LDS, joint j counts the
+// joints ranked before it -- larger first, equal values by lower index, NaN above every number (torch.topk's order) -- and is
+// selected when fewer than k are.  sel_w[b,j] = w[b,j] (1 without w) if selected else 0;
+// loss[0] = scale * sum over the selected row sums, in fp64: per thread in (b, j) order, then lanes, then waves.
+__global__ __launch_bounds__(256) void ohkm_select_kernel(const float* __restrict__ rows, const float* __restrict__ w,
+                                                          float* __restrict__ sel_w, float* __restrict__ loss, int B,
+                                                          int J, int k, double scale) {
+  extern __shared__ float row[];      // J floats
+  __shared__ double sm[4];
+  double s = 0.0;
+  for (int b = 0; b < B; ++b) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < J; j += 256) row[j] = rows[(long)b * J + j];
+    __syncthreads();
+    for (int j = threadIdx.x; j < J; j += 256) {
+      const float vj = row[j];
+      const bool nj = vj != vj;
+      int before = 0;
+      for (int i = 0; i < J; ++i) {
+        const float vi = row[i];
+        const bool ni = vi != vi;
+        const bool first = ni != nj ? ni : ((ni || vi == vj) ? i < j : vi > vj);
+        before += first ? 1 : 0;
+      }
+      const bool sel = before < k;
+      sel_w[(long)b * J + j] = sel ? (w ? w[(long)b * J + j] : 1.f) : 0.f;
+      if (sel) s += (double)vj;
+    }
+  }
+  s = wave_sum_d(s);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) sm[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[0] = (float)((sm[0] + sm[1] + sm[2] + sm[3]) * scale);
 }
 // dpred = g * 2 w^2 (pred - gt) * scale
 __global__ void wmse_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -329,6 +377,8 @@ __global__ __launch_bounds__(256) void pck_kernel(const long long* __restrict__ 
   }
 }
 
+#define OHKM_MAX_J 15360      // 60 KiB of the 64 KiB a workgroup may ask for without an opt-in
+
 extern "C" {
 
 // joints [B,J,2] px, vis [B,J] -> target [B,J,Hh,Wh] (NCHW), weight [B,J]
@@ -336,9 +386,24 @@ int fami_gauss_target_f32(const float* joints, const float* vis, float* target, 
                           int Wh, int img_h, int img_w, int sigma, hipStream_t s) {
   FAMI_REQUIRE(joints && vis && target && weight && B > 0 && J > 0 && Hh > 0 && Wh > 0 && sigma > 0,
                "fami_gauss_target_f32", "bad argument");
-  hipLaunchKernelGGL(gauss_target_kernel, dim3(fami_ew_grid((long)B * J * Hh * Wh)), dim3(256), 0, s, joints, vis,
-                     target, weight, B, J, Hh, Wh, (double)img_w / (double)Wh, (double)img_h / (double)Hh, sigma);
+  hipLaunchKernelGGL(gauss_target_kernel<false>, dim3(fami_ew_grid((long)B * J * Hh * Wh)), dim3(256), 0, s, joints, vis,
+                     (const float*)nullptr, target, weight, B, J, Hh, Wh, (double)img_w / (double)Wh,
+                     (double)img_h / (double)Hh, sigma);
   FAMI_CHECK_LAUNCH("fami_gauss_target_f32");
+  return FAMI_OK;
+}
+// ... with joint_w [J] (device, or null): weight[b,j] *= joint_w[j]; subpixel != 0: the Gaussian centred at the real-valued
+// joint position, window and weight those of the rounded centre.  (null, 0) writes what fami_gauss_target_f32 writes.
+int fami_gauss_target_ex_f32(const float* joints, const float* vis, const float* joint_w, float* target, float* weight,
+                             int B, int J, int Hh, int Wh, int img_h, int img_w, int sigma, int subpixel,
+                             hipStream_t s) {
+  FAMI_REQUIRE(joints && vis && target && weight && B > 0 && J > 0 && Hh > 0 && Wh > 0 && sigma > 0,
+               "fami_gauss_target_ex_f32", "bad argument");
+  const dim3 grid(fami_ew_grid((long)B * J * Hh * Wh));
+  const double sx = (double)img_w / (double)Wh, sy = (double)img_h / (double)Hh;
+  if (subpixel) hipLaunchKernelGGL(gauss_target_kernel<true>, grid, dim3(256), 0, s, joints, vis, joint_w, target, weight, B, J, Hh, Wh, sx, sy, sigma);
+  else hipLaunchKernelGGL(gauss_target_kernel<false>, grid, dim3(256), 0, s, joints, vis, joint_w, target, weight, B, J, Hh, Wh, sx, sy, sigma);
+  FAMI_CHECK_LAUNCH("fami_gauss_target_ex_f32");
   return FAMI_OK;
 }
 
@@ -361,6 +426,21 @@ int fami_wmse_bwd_f32(const float* pred, const float* gt, const float* w, float*
   return FAMI_OK;
 }
 
+// OHKM: per sample only the k joints with the largest row sums count.  pred/gt [B*J,L], w [B*J] or null ->
+// sel_w [B*J] = w (1 without w) on the selected joints, 0 elsewhere; loss[0] = scale * sum of the selected row sums.
+// ws >= B*J floats.  The gradient is fami_wmse_bwd_f32 with sel_w in place of w (the selection factor is 0 or 1).
+int fami_ohkm_fwd_f32(const float* pred, const float* gt, const float* w, float* loss, float* sel_w, int B, int J, int L,
+                      int k, double scale, float* ws, hipStream_t s) {
+  FAMI_REQUIRE(pred && gt && loss && sel_w && ws && B > 0 && J > 0 && L > 0 && (long)B * J <= 0x7fffffffL,
+               "fami_ohkm_fwd_f32", "bad argument");
+  FAMI_REQUIRE(k >= 1 && k <= J, "fami_ohkm_fwd_f32", "bad argument (1 <= k <= J)");
+  FAMI_REQUIRE(J <= OHKM_MAX_J, "fami_ohkm_fwd_f32", "bad argument (the J row sums of a sample live in LDS: J <= 15360)");
+  hipLaunchKernelGGL(wmse_rows_kernel, dim3(B * J), dim3(256), 0, s, pred, gt, w, ws, L);
+  FAMI_CHECK_LAUNCH("fami_ohkm_fwd_f32/rows");
+  hipLaunchKernelGGL(ohkm_select_kernel, dim3(1), dim3(256), (size_t)J * sizeof(float), s, ws, w, sel_w, loss, B, J, k, scale);
+  FAMI_CHECK_LAUNCH("fami_ohkm_fwd_f32/select");
+  return FAMI_OK;
+}
 // value[0] = mean over R*L of t*(log t - a), a = softmax(A/T) rows, t = softmax(Bt/T) rows.
 // stats [R,5] saved for the backward; ws >= R floats.
 int fami_softmax_kl_fwd_f32(const float* A, const float* Bt, float* value, float* stats, int R, int L,

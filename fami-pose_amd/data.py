@@ -17,6 +17,7 @@ from ._lib import lib
 MEAN = (0.485, 0.456, 0.406)      # datasets/transforms/build.py:13-14 (RGB)
 STD = (0.229, 0.224, 0.225)
 FLIP_PAIRS = ((3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))   # PoseTrack_Alignment.py:40
+JOINTS_WEIGHT = (1., 1., 1., 1., 1., 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5)    # PoseTrack_Alignment.py:41-43
 UPPER_BODY_IDS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10)                            # PoseTrack_Alignment.py:44
 PIXEL_STD = 200                                                                # datasets/zoo/base.py:27
 

@@ -64,18 +64,103 @@ class JointMSELoss(nn.Module):
         return _WMSE.apply(output.float().contiguous(), target.float().contiguous(), w, scale)
 
 
-def generate_heatmaps(joints, joints_vis, sigma, image_size, heatmap_size):
+class _OHKM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, w, k, scale):
+        B, J = pred.shape[:2]
+        L = pred[0, 0].numel()
+        out = torch.empty(1, device=pred.device)
+        sel_w = torch.empty(B * J, device=pred.device)
+        ws = torch.empty(B * J, device=pred.device)
+        lib().call('fami_ohkm_fwd_f32', _p(pred), _p(gt), _p(w), _p(out), _p(sel_w), B, J, L, k, float(scale), _p(ws),
+                   _stream(pred))
+        ctx.save_for_backward(pred, gt, sel_w)
+        ctx.scale = scale
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, gt, sel_w = ctx.saved_tensors
+        R, L = pred.shape[0] * pred.shape[1], pred[0, 0].numel()
+        d = torch.empty_like(pred)
+        lib().call('fami_wmse_bwd_f32', _p(pred), _p(gt), _p(sel_w), _p(d), R, L, float(ctx.scale),
+                   _p(g.reshape(1).contiguous()), 0, _stream(pred))
+        return d, None, None, None, None
+
+
+def check_ohkm_topk(k, num_joints=None):
+    """-> int(k), or ValueError: an integer (not a bool) with 1 <= k (<= num_joints where that is known)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (num_joints is not None and k > num_joints):
+        raise ValueError('OHKM topk is an integer with 1 <= topk <= the number of joints%s, not %r' %
+                         ('' if num_joints is None else ' (%d)' % num_joints, k))
+    return int(k)
+
+
+class JointOHKMMSELoss(nn.Module):
+    """Online hard keypoint mining (the HRNet family's JointsOHKMMSELoss): per sample only the `topk` joints with the largest
+    loss count, (1/B) sum_b (1/k) sum_{j in top-k of b} mean_p (w_bj (pred - gt))^2.  The selection runs on the device
+    (fami_ohkm_fwd_f32: larger first, equal losses by lower joint index, NaN first) and carries no gradient; the backward
+    pass is JointMSELoss's with the weights of the unselected joints zeroed.  HRNet's factor 0.5 is deliberately NOT
+    here: topk = J is then exactly this project's JointMSELoss, and a caller who wants HRNet's value puts the 0.5 into
+    the weight of the term (the Trainer's mse_weight)."""
+
+    def __init__(self, topk=8, use_target_weight=True):
+        super().__init__()
+        self.topk = check_ohkm_topk(topk)
+        self.use_target_weight = use_target_weight
+
+    def forward(self, output, target, target_weight):
+        _need_cuda(output)
+        B, J = output.shape[:2]
+        k = check_ohkm_topk(self.topk, J)
+        L = output[0, 0].numel()
+        w = target_weight.reshape(B * J).float().contiguous() if self.use_target_weight else None
+        return _OHKM.apply(output.float().contiguous(), target.float().contiguous(), w, k, 1.0 / (B * L * k))
+
+
+ENCODINGS = ('quantised', 'subpixel')
+
+
+def check_target_options(encoding, joint_weights, num_joints=None):
+    """-> (subpixel flag, joint weights as a tuple of floats or None), or ValueError -- host arithmetic only."""
+    if encoding not in ENCODINGS:
+        raise ValueError("encoding is 'quantised' or 'subpixel', not %r" % (encoding,))
+    if joint_weights is not None:
+        jw = joint_weights.detach().cpu().reshape(-1).tolist() if torch.is_tensor(joint_weights) else \
+            [float(v) for v in np.asarray(joint_weights, dtype=np.float64).reshape(-1)]
+        if not jw or (num_joints is not None and len(jw) != num_joints):
+            raise ValueError('joint_weights holds %d values for %s joints' %
+                             (len(jw), 'no' if num_joints is None else num_joints))
+        joint_weights = tuple(jw)
+    return encoding == 'subpixel', joint_weights
+
+
+def generate_heatmaps(joints, joints_vis, sigma, image_size, heatmap_size, encoding='quantised', joint_weights=None):
     """joints [B,J,2|3] (pixels, device), joints_vis [B,J] or [B,J,3] -> target [B,J,Hh,Wh], weight [B,J,1].
-    image_size / heatmap_size are (w, h) as in the reference."""
-    _need_cuda(joints)
+    image_size / heatmap_size are (w, h) as in the reference.
+    joint_weights: J factors (sequence or tensor) of the returned weights, the reference's USE_DIFFERENT_JOINTS_WEIGHT
+    (heatmaps_process.py:200-201; data.JOINTS_WEIGHT is PoseTrack's vector); whether a map is drawn still follows the
+    unmultiplied weight.
+    encoding='subpixel': the Gaussian is centred at the real-valued position joint / stride instead of the rounded one --
+    the encoding the DARK decode (dark_get_final_preds) assumes.  Window and weight stay those of the rounded centre, so
+    the two encodings differ only in the values inside the window, and a joint at a non-negative integer position gets
+    the same bits under both.  At exactly half a pixel the sub-pixel map has two equal maxima and its first one is the
+    LOWER pixel, where the quantised centre is the upper one."""
     B, J = joints.shape[:2]
+    sub, jw = check_target_options(encoding, joint_weights, J)
+    _need_cuda(joints)
     xy = joints[..., :2].float().contiguous()
     vis = (joints_vis[..., 0] if joints_vis.dim() == 3 else joints_vis).float().contiguous()
     Wh, Hh = int(heatmap_size[0]), int(heatmap_size[1])
     target = torch.empty(B, J, Hh, Wh, device=joints.device)
     weight = torch.empty(B, J, device=joints.device)
-    lib().call('fami_gauss_target_f32', _p(xy), _p(vis), _p(target), _p(weight), B, J, Hh, Wh, int(image_size[1]),
-               int(image_size[0]), int(sigma), _stream(joints))
+    if not sub and jw is None:
+        lib().call('fami_gauss_target_f32', _p(xy), _p(vis), _p(target), _p(weight), B, J, Hh, Wh, int(image_size[1]),
+                   int(image_size[0]), int(sigma), _stream(joints))
+    else:
+        jw = None if jw is None else torch.tensor(jw, dtype=torch.float32, device=joints.device)
+        lib().call('fami_gauss_target_ex_f32', _p(xy), _p(vis), _p(jw), _p(target), _p(weight), B, J, Hh, Wh,
+                   int(image_size[1]), int(image_size[0]), int(sigma), int(sub), _stream(joints))
     return target, weight.reshape(B, J, 1)
 
 

@@ -686,13 +686,29 @@ class Trainer:
     set requires_grad = False on them.  No train-only BatchNorm fusion is taken for a frozen module.  The set of frozen
     modules keys the captured plans next to the optimizer hyper-parameters: a later freeze_batchnorm call re-captures.
     The reference has no such switch, so there is no config key; None (default) leaves every launch as it is.
+
+    The supervision (the target, loss and seed launches between the forward and the backward pass) has three options, all
+    fixed at construction like mse_weight and baked into the captured plans; the defaults leave the three launches
+    fami_gauss_target_f32 / fami_wmse_fwd_f32 / fami_wmse_bwd_f32 as they are.
+    joint_weights (needs targets_from_joints): J factors of the target weights, the reference's
+    LOSS.USE_DIFFERENT_JOINTS_WEIGHT (heatmaps_process.py:200-201; from_cfg reads the key and passes data.JOINTS_WEIGHT).
+    target_encoding='subpixel' (needs targets_from_joints): Gaussians centred at the real-valued joint position, the
+    encoding the DARK decode assumes (loss.generate_heatmaps); both go through fami_gauss_target_ex_f32.  The PCK rows take
+    the argmax of the target map: for a joint at exactly half a pixel the sub-pixel map's first maximum is the lower
+    pixel where the quantised one has the upper.
+    ohkm_topk = k (either kind of target): online hard keypoint mining, loss.JointOHKMMSELoss -- fami_ohkm_fwd_f32 in
+    place of fami_wmse_fwd_f32 ranks the J row losses of each sample on the device and writes the selected weights;
+    loss_parts[0] = mse_weight * (1/B) sum_b (1/k) sum_{top-k} mean_p (w (pred - gt))^2, and the seeds are
+    fami_wmse_bwd_f32 on the selected weights with mse_weight / (B L k).  k = J is the default loss.  PCK and the MI
+    terms are untouched.  ohkm_selection() is the last step's selection.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
                  process_group=None, use_graph=True, targets_from_joints=False, sigma=3, force_ddp=False,
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
                  weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None,
-                 ema_decay=None, ema_warmup=False, frozen_bn=None):
+                 ema_decay=None, ema_warmup=False, frozen_bn=None, target_encoding='quantised', joint_weights=None,
+                 ohkm_topk=None):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
@@ -700,7 +716,15 @@ class Trainer:
         configuration has no such keys: from_cfg takes them as keyword arguments).  accum_steps: micro-batches per update
         (class docstring; None = 1).  ema_decay / ema_warmup: the moving average of the weights (class docstring; None =
         none).  frozen_bn: None, 'all', 'backbone' or module-name prefixes -- freeze_batchnorm(model, frozen_bn) before
-        anything is captured (class docstring; None leaves the model's flags as they are)."""
+        anything is captured (class docstring; None leaves the model's flags as they are).  target_encoding / joint_weights
+        / ohkm_topk: the options of the supervision (class docstring; no config key but joint_weights')."""
+        from .loss import check_ohkm_topk, check_target_options
+        num_joints = getattr(model, 'num_joints', None)
+        self.subpixel, self.joint_weights = check_target_options(target_encoding, joint_weights, num_joints)
+        if (self.subpixel or self.joint_weights is not None) and not targets_from_joints:
+            raise ValueError("target_encoding='subpixel' and joint_weights act where the Trainer makes the targets: they need "
+                             "targets_from_joints=True (precomputed targets: loss.generate_heatmaps takes both)")
+        self.ohkm_topk = None if ohkm_topk is None else check_ohkm_topk(ohkm_topk, num_joints)
         if frozen_bn is not None:
             freeze_batchnorm(model, frozen_bn)
         self._bn_modules = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
@@ -827,6 +851,10 @@ class Trainer:
         self.pck = pck
         self.acc = None           # [2, J+3] device floats of the last step: PCK of final_hm / kf_bb_hm (see accuracy())
         self._cache = {}          # batch shapes -> (plan, static inputs, static outputs, optimizer hyper version)
+        self._joint_w = (None if self.joint_weights is None else
+                         torch.tensor(self.joint_weights, dtype=torch.float32, device=self.dev))
+        self._sel_w = {}          # OHKM: (B, J) -> selected weights [B*J], written by that batch shape's launches
+        self._sel_key = None      # ... and the shape of the last step
         if hasattr(model, '_ensure_nbt'):
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
@@ -845,6 +873,12 @@ class Trainer:
         """A Trainer with the optimizer the reference's build_optimizer makes of `cfg` (optimizer_kwargs); `trainer_kw`
         takes the other Trainer arguments and wins over the config."""
         kw = optimizer_kwargs(cfg)
+        if cfg.get('LOSS', {}).get('USE_DIFFERENT_JOINTS_WEIGHT', False):      # datasets/zoo/base.py:46, mppe_config.py:240
+            from .data import JOINTS_WEIGHT
+            if 'joint_weights' not in trainer_kw and cfg['MODEL']['NUM_JOINTS'] != len(JOINTS_WEIGHT):
+                raise ValueError('LOSS.USE_DIFFERENT_JOINTS_WEIGHT: the only vector at hand is PoseTrack\'s for %d joints, the '
+                                 'model has %d -- pass joint_weights=' % (len(JOINTS_WEIGHT), cfg['MODEL']['NUM_JOINTS']))
+            kw['joint_weights'] = JOINTS_WEIGHT
         kw.update(trainer_kw)
         return cls(model, **kw)
 
@@ -976,19 +1010,36 @@ class Trainer:
             Hh, Wh = kf_x.shape[2] // 4, kf_x.shape[3] // 4
             target = eng.empty(B, J, Hh, Wh)
             weight = eng.empty(B, J)
-            eng.call('fami_gauss_target_f32', _p(joints), _p(vis), _p(target), _p(weight), B, J, Hh, Wh,
-                     kf_x.shape[2], kf_x.shape[3], self.sigma)
+            if self.subpixel or self._joint_w is not None:
+                if self._joint_w is not None and self._joint_w.numel() != J:
+                    raise ValueError('joint_weights holds %d values, the batch has %d joints' % (self._joint_w.numel(), J))
+                eng.call('fami_gauss_target_ex_f32', _p(joints), _p(vis), _p(self._joint_w), _p(target), _p(weight), B, J,
+                         Hh, Wh, kf_x.shape[2], kf_x.shape[3], self.sigma, int(self.subpixel))
+            else:
+                eng.call('fami_gauss_target_f32', _p(joints), _p(vis), _p(target), _p(weight), B, J, Hh, Wh,
+                         kf_x.shape[2], kf_x.shape[3], self.sigma)
         outs, _ = model._body(eng, kf_x, sup_x)
         model._advance_bn_counters(eng)
         aux = eng.aux
         final_nchw = outs[0]
         B, J, Hh, Wh = final_nchw.shape
         L = Hh * Wh
-        scale = self.mse_weight / (B * L * J)
+        scale = self.mse_weight / (B * L * (J if self.ohkm_topk is None else self.ohkm_topk))
         w = weight.reshape(B * J)
         ws = eng.ws(B * J * 4)
-        eng.call('fami_wmse_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]), B * J, L,
-                 float(scale), _p(ws))
+        if self.ohkm_topk is None:
+            eng.call('fami_wmse_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]), B * J, L,
+                     float(scale), _p(ws))
+        else:
+            # the selection between the loss rows and the seeds, on the device: the seeds below read the selected weights
+            if self.ohkm_topk > J:
+                raise ValueError('ohkm_topk = %d, the model has %d joints' % (self.ohkm_topk, J))
+            self._sel_key = (B, J)
+            if self._sel_key not in self._sel_w:
+                self._sel_w[self._sel_key] = torch.zeros(B * J, device=self.dev)
+            eng.call('fami_ohkm_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]),
+                     _p(self._sel_w[self._sel_key]), B, J, L, self.ohkm_topk, float(scale), _p(ws))
+            w = self._sel_w[self._sel_key]
         if self.pck:
             # accuracy(pred_heatmaps, target) and accuracy(kf_bb_heatmaps, target), core fn :159-163, without the four
             # device-to-host heatmap copies
@@ -1051,6 +1102,14 @@ class Trainer:
 
     _flushing = False
     conv_flops = 0
+
+    def ohkm_selection(self):
+        """OHKM: the joints the last step's loss counted, a device bool tensor [B,J] (None without ohkm_topk or before the
+        first step): the selected weights are non-zero there.  A joint of weight 0 that fills one of the k places -- a
+        sample with fewer than k visible joints -- adds nothing to loss or gradient and reads False."""
+        if self._sel_key is None:
+            return None
+        return (self._sel_w[self._sel_key] != 0).reshape(self._sel_key)
 
     def skipped_steps(self):
         """Optimizer steps skipped so far because the loss-scaled gradients held inf / NaN (fp16 mode; synchronises).
@@ -1562,6 +1621,8 @@ class Trainer:
         if not (kf_x.shape[0] == sup_x.shape[0] == target.shape[0] == weight.shape[0]):
             raise ValueError('batch sizes differ: kf %s sup %s target %s weight %s' %
                              (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape)))
+        if self.ohkm_topk is not None:
+            self._sel_key = (target.shape[0], target.shape[1])       # (a replay does not pass through _forward_backward)
         if not self.use_graph:
             return self._eager_step(kf_x, sup_x, target, weight)
         key = (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape))

@@ -434,8 +434,18 @@ int fami_linear_bwd_f32(const float* dy, const float* x, const float* w, float* 
  * fami_argmax2d      : datasets/process/heatmaps_process.py:16-44 (get_max_preds) */
 int fami_gauss_target_f32(const float* joints_xy, const float* vis, float* target, float* weight, int B, int J,
                           int Hh, int Wh, int img_h, int img_w, int sigma, fami_stream_t stream);
+/* joint_w: DEVICE float[J] or NULL (weight[b,j] *= joint_w[j]); subpixel != 0: Gaussian centred at the real-valued joint
+ * position inside the rounded centre's window.  (NULL, 0) writes what fami_gauss_target_f32 writes. */
+int fami_gauss_target_ex_f32(const float* joints_xy, const float* vis, const float* joint_w, float* target,
+                             float* weight, int B, int J, int Hh, int Wh, int img_h, int img_w, int sigma, int subpixel,
+                             fami_stream_t stream);
 int fami_wmse_fwd_f32(const float* pred, const float* gt, const float* w, float* loss, int R, int L, double scale,
                       float* ws, fami_stream_t stream);
+/* online hard keypoint mining: per sample the k joints with the largest row sums (ties: lower index; NaN first);
+ * sel_w [B*J] = w (1 if NULL) where selected, else 0; loss = scale * their sum (fp64, fixed order); ws: B*J floats;
+ * 1 <= k <= J or -1.  Gradient: fami_wmse_bwd_f32 with sel_w as w. */
+int fami_ohkm_fwd_f32(const float* pred, const float* gt, const float* w, float* loss, float* sel_w, int B, int J, int L,
+                      int k, double scale, float* ws, fami_stream_t stream);
 int fami_wmse_bwd_f32(const float* pred, const float* gt, const float* w, float* dpred, int R, int L, float scale,
                       const float* gdev, int accumulate, fami_stream_t stream);
 int fami_softmax_kl_fwd_f32(const float* A, const float* Bt, float* value, float* stats, int R, int L,
