@@ -18,7 +18,8 @@ from .config import CfgNode, default_cfg
 from .zoo import (MODEL_REGISTRY, CORE_FUNCTION_REGISTRY, DATASET_REGISTRY, TRAIN_PHASE, VAL_PHASE, TEST_PHASE,
                   build_model, get_model_hyperparameter, Alignment_V15, HRNet, HRNetPlus)
 from .train import freeze_batchnorm
+from .evaluate import COCO_SIGMAS, pose_nms, pose_nms_options
 
 __all__ = ['CfgNode', 'default_cfg', 'MODEL_REGISTRY', 'CORE_FUNCTION_REGISTRY', 'DATASET_REGISTRY', 'TRAIN_PHASE',
            'VAL_PHASE', 'TEST_PHASE', 'build_model', 'get_model_hyperparameter', 'Alignment_V15', 'HRNet',
-           'HRNetPlus', 'freeze_batchnorm']
+           'HRNetPlus', 'freeze_batchnorm', 'COCO_SIGMAS', 'pose_nms', 'pose_nms_options']

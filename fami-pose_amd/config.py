@@ -47,6 +47,7 @@ def default_cfg(width=48, num_joints=17, freeze_backbone=False, name='Alignment_
                   'FLIP': True, 'NUM_JOINTS_HALF_BODY': 8, 'PROB_HALF_BODY': 0.3},
         'LOSS': {'HEATMAP_MSE': {'USE': True, 'WEIGHT': 1.0}},
         # flip testing (evaluate.flip_test_options); the reference's defaults, posetimation/config/mppe_config.py:322-346
-        'VAL': {'FLIP_VAL': False, 'SHIFT_HEATMAP': False},
-        'TEST': {'FLIP_TEST': False, 'SHIFT_HEATMAP': False},
+        # rescoring and OKS-NMS (evaluate.pose_nms_options); the reference's defaults, mppe_config.py:326-330, 343-347
+        'VAL': {'FLIP_VAL': False, 'SHIFT_HEATMAP': False, 'IN_VIS_THRE': 0.0, 'OKS_THRE': 0.5, 'SOFT_NMS': False},
+        'TEST': {'FLIP_TEST': False, 'SHIFT_HEATMAP': False, 'IN_VIS_THRE': 0.0, 'OKS_THRE': 0.5, 'SOFT_NMS': False},
     })

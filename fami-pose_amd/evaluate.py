@@ -21,6 +21,17 @@
   argmax.  The default decode='standard' is `get_final_preds` as before.
 * `EvalAccumulator` + `evaluate_loop` -- the loop around it (:222-328): per-batch PCK of both heatmap outputs (on
   device), `all_preds` / `all_bb` / `all_boxes` / `filenames_map` accumulation exactly as the reference lays them out.
+* `pose_nms` / `EvalAccumulator.pose_nms` / `pose_nms_options` -- the third step of that protocol, between the loop and
+  the writer: every detection is rescored by its keypoint confidences (box score x mean confidence of the joints above
+  IN_VIS_THRE) and the duplicate poses of one frame are suppressed by object-keypoint-similarity NMS, hard
+  (`oks_nms`) or soft (`soft_oks_nms`).  The reference ships the four functions (datasets/process/nms.py:51-192),
+  declares VAL/TEST.IN_VIS_THRE, OKS_THRE and SOFT_NMS (mppe_config.py:325-330, 342-348), sets them in
+  configs/Alignment/Base_PoseTrack17.yaml and reads them at PoseTrack_Alignment.py:68-72 -- and never uses the values.
+  Here it is one upload, ONE launch for the whole validation set with one workgroup per frame (csrc/nms.hip,
+  `fami_pose_nms_f32`) and one download; `all_boxes` already carries what it needs (column 4 the box area, column 5 the
+  box score).  There is no "run NMS" switch in the reference, so there is none here: the step runs when it is called,
+  and `evaluate_loop`, `predict` and `write_posetrack_results` are unchanged.  Box-IoU NMS (nms.py:9-48, NMS_THRE) is a
+  detector-stage step and stays out.
 * `write_posetrack_results` -- the PoseTrack JSON writer of
   datasets/zoo/posetrack/PoseTrack_Alignment.py:883-1017 (`evaluate` up to the poseval call): COCO->PoseTrack joint
   conversion (datasets/process/structure/keypoints_ord.py:14-73), the annorect structure
@@ -49,6 +60,10 @@ from .zoo.registry import TEST_PHASE, VAL_PHASE
 COCO_JOINT = ['nose', 'left_eye', 'right_eye', 'left_ear', 'right_ear', 'left_shoulder', 'right_shoulder',
               'left_elbow', 'right_elbow', 'left_wrist', 'right_wrist', 'left_hip', 'right_hip', 'left_knee',
               'right_knee', 'left_ankle', 'right_ankle']
+# the per-joint OKS constants of COCO-17, datasets/process/nms.py:66-69 (float64, as the reference holds them)
+COCO_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+NMS_MAX_PER_IMAGE = 256         # csrc/nms.hip: one thread per detection of an image
+NMS_MAX_JOINTS = 32             # ... and one mask bit per joint
 POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_knee', 'left_ankle', 'right_wrist',
                    'right_elbow', 'right_shoulder', 'left_shoulder', 'left_elbow', 'left_wrist', 'neck', 'nose',
                    'head_top']
@@ -210,6 +225,16 @@ class EvalAccumulator:
     def accuracy(self, k=0):
         return self.acc_sum[k] / self.acc_cnt[k] if self.acc_cnt[k] else 0.0
 
+    def pose_nms(self, **kw):
+        """Rescoring and OKS-NMS of everything accumulated so far (module-level `pose_nms`, same keywords) ->
+        (boxes2, filenames_map2): a copy of all_boxes[:idx] with column 5 replaced by the rescored value, and
+        filenames_map with each frame's list reduced to the kept detections in pick order -- the `boxes` and
+        `filenames_map` arguments of `write_posetrack_results`.  The accumulator itself is not modified."""
+        boxes2 = self.all_boxes[:self.idx].copy()
+        scores, keep_map = pose_nms(self.all_preds[:self.idx], boxes2, self.filenames_map, **kw)
+        boxes2[:, 5] = scores
+        return boxes2, keep_map
+
 
 @torch.no_grad()
 def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS,
@@ -252,6 +277,145 @@ def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_
         acc.add(pc.cpu().numpy(), pm.cpu().numpy(), bc.cpu().numpy(), bm.cpu().numpy(), center, scale,
                 np.asarray(meta['score']), list(meta['image']))
     return acc
+
+
+# ---------------------------------------------------------------------------------------- rescoring + OKS-NMS
+def pose_nms_options(cfg, phase):
+    """-> {'in_vis_thre', 'oks_thre', 'soft'} for `pose_nms` from the reference's switches: VAL.IN_VIS_THRE / OKS_THRE /
+    SOFT_NMS in the validation phase, the same keys of TEST in the test phase (mppe_config.py:326-330, 343-347); where
+    the node or a key is absent, the reference's defaults 0.0 / 0.5 / False."""
+    if phase == VAL_PHASE:
+        node = 'VAL'
+    elif phase == TEST_PHASE:
+        node = 'TEST'
+    else:
+        raise ValueError('pose NMS is an evaluation option: phase %r has none' % (phase,))
+    sub = cfg.get(node) if hasattr(cfg, 'get') else None
+    sub = sub if hasattr(sub, 'get') else {}
+    return {'in_vis_thre': float(sub.get('IN_VIS_THRE', 0.0)), 'oks_thre': float(sub.get('OKS_THRE', 0.5)),
+            'soft': bool(sub.get('SOFT_NMS', False))}
+
+
+def _nms_lists(filenames_map, N):
+    """-> (index [n] int32, seg [M+1] int32) of the lists of `filenames_map` in its order; ValueError for a list longer
+    than the kernel's cap, an index outside [0, N), a non-integer index, or an index used twice.  The lists are checked
+    as one array (a validation set has tens of thousands of them); the offending image is looked up only to be named."""
+    lists = [list(v) for v in filenames_map.values()]
+    seg = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(v) for v in lists], out=seg[1:])
+
+    def image_of(pos):
+        return list(filenames_map)[int(np.searchsorted(seg, pos, side='right')) - 1]
+
+    if len(lists) and np.diff(seg).max() > NMS_MAX_PER_IMAGE:
+        m = int(np.diff(seg).argmax())
+        raise ValueError('pose_nms: image %r has %d detections, the limit is %d per image'
+                         % (list(filenames_map)[m], len(lists[m]), NMS_MAX_PER_IMAGE))
+    flat = np.asarray([i for v in lists for i in v])
+    if flat.size == 0:
+        return np.zeros(0, dtype=np.int32), seg.astype(np.int32)
+    if flat.ndim != 1 or flat.dtype.kind not in 'iu':
+        raise ValueError('pose_nms: the lists of filenames_map must hold integer row indices (got %s)' % flat.dtype)
+    bad = np.flatnonzero((flat < 0) | (flat >= N))
+    if bad.size:
+        raise ValueError('pose_nms: image %r lists row %d outside [0, %d)' % (image_of(bad[0]), flat[bad[0]], N))
+    count = np.bincount(flat, minlength=N)
+    if count.max() > 1:
+        raise ValueError('pose_nms: row %d is listed %d times' % (int(count.argmax()), int(count.max())))
+    return flat.astype(np.int32), seg.astype(np.int32)
+
+
+def pose_nms(preds, boxes, filenames_map, in_vis_thre=0.0, oks_thre=0.5, soft=False, max_dets=20, vis_thre=None,
+             sigmas=None, device='cuda'):
+    """Rescoring and OKS-NMS of a whole evaluation set in one launch (csrc/nms.hip; include/fami.h has the arithmetic).
+    preds [N,J,3] (x, y, confidence in image pixels) and boxes [N,6] (column 4 the box area, column 5 the box score) are
+    host arrays as `EvalAccumulator` holds them; filenames_map {image -> [row indices]} groups them into frames.
+    -> (scores [N] float64, keep_map): scores[i] = box score x mean confidence of the joints of i with confidence >
+    in_vis_thre (0 when none passes; also 0 for a row that no image lists), computed in fp64 and rounded to fp32 once;
+    keep_map has the keys of filenames_map in its order, each value the list of kept row indices in pick order
+    (descending score; equal scores: the one listed first).
+    soft=False is the reference's `oks_nms`: a kept pose suppresses every lower-scored one of its frame with OKS >
+    oks_thre.  soft=True is `soft_oks_nms` with the Gaussian `_rescore`: the pose with the highest working score is
+    kept, the others' working scores are multiplied by exp(-OKS^2 / oks_thre), at most max_dets (the reference's default
+    20) per frame; the returned scores stay the rescored values, as the reference returns only indices.
+    vis_thre=None counts all joints in an OKS; with a value, the joints whose confidence in the COMPARED (lower-scored)
+    pose exceeds it -- the picked pose's visibility is not read: the reference's `list(vg > t) and list(vd > t)`
+    evaluates to its second operand, and that is kept here (an empty mask gives OKS 0: nothing is suppressed).
+    sigmas: the per-joint OKS constants, default COCO_SIGMAS for J = 17 (any other J needs its own).
+    The inputs are rounded to fp32 on upload (the pipeline's own values are fp32 already); the arithmetic on them is
+    fp64.  One upload, one launch, one download.  ValueError before any device work for: J != 17 without sigmas, J > 32,
+    non-finite inputs, an image with more than 256 detections, a row index outside [0, N) or used twice, max_dets < 1,
+    oks_thre <= 0 with soft=True."""
+    preds, boxes = np.asarray(preds), np.asarray(boxes)
+    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
+        raise ValueError('pose_nms expects preds [N,J,3] and boxes [N,6], got %s and %s' % (preds.shape, boxes.shape))
+    N, J = preds.shape[:2]
+    if not 1 <= J <= NMS_MAX_JOINTS:
+        raise ValueError('pose_nms: J = %d joints, supported 1 .. %d' % (J, NMS_MAX_JOINTS))
+    if sigmas is None:
+        if J != len(COCO_SIGMAS):
+            raise ValueError('pose_nms: COCO_SIGMAS has %d joints, preds has %d: pass sigmas' % (len(COCO_SIGMAS), J))
+        sigmas = COCO_SIGMAS
+    sig32 = np.asarray(sigmas, dtype=np.float64).reshape(-1).astype(np.float32)
+    if sig32.shape != (J,) or not np.isfinite(sig32).all() or not (sig32 > 0).all():
+        raise ValueError('pose_nms: sigmas must be %d finite positive values' % J)
+    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or max_dets < 1:
+        raise ValueError('pose_nms: max_dets must be an integer >= 1, got %r' % (max_dets,))
+    in_vis_thre, oks_thre = float(in_vis_thre), float(oks_thre)
+    vis = None if vis_thre is None else float(vis_thre)
+    if not (np.isfinite(in_vis_thre) and np.isfinite(oks_thre) and (vis is None or np.isfinite(vis))):
+        raise ValueError('pose_nms: thresholds must be finite')
+    if soft and not oks_thre > 0:
+        raise ValueError('pose_nms: soft mode divides by oks_thre, which must be > 0 (got %r)' % oks_thre)
+    with np.errstate(over='ignore'):
+        k32 = np.ascontiguousarray(preds, dtype=np.float32)
+        a32 = np.ascontiguousarray(boxes[:, 4], dtype=np.float32)
+        b32 = np.ascontiguousarray(boxes[:, 5], dtype=np.float32)
+    if not (np.isfinite(k32).all() and np.isfinite(a32).all() and np.isfinite(b32).all()):
+        raise ValueError('pose_nms: preds, box areas and box scores must be finite (in fp32)')
+    index, seg = _nms_lists(filenames_map, N)
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('pose_nms runs on the HIP path only (device is %s)' % dev)
+    M, n = len(seg) - 1, int(index.size)
+    keys = list(filenames_map.keys())
+    if N == 0 or M == 0:
+        return np.zeros(N, dtype=np.float64), {k: [] for k in keys}
+    if N * J * 3 > 0x7fffffff:
+        raise ValueError('pose_nms: N * J * 3 = %d exceeds 2^31 - 1' % (N * J * 3))
+    # ONE buffer of 4-byte words: the six inputs, then the three outputs with their initial values (score 0 and rank -1
+    # for rows that no image lists) -- one upload; the tail comes back in one download
+    sizes = [N * J * 3, N, N, J, N, M + 1, N, N, M]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    buf = np.zeros(int(off[-1]), dtype=np.int32)
+    fbuf = buf.view(np.float32)
+    fbuf[off[0]:off[1]] = k32.reshape(-1)
+    fbuf[off[1]:off[2]] = a32
+    fbuf[off[2]:off[3]] = b32
+    fbuf[off[3]:off[4]] = sig32
+    buf[off[4]:off[4] + n] = index
+    buf[off[5]:off[6]] = seg
+    buf[off[7]:off[8]] = -1
+    d = torch.from_numpy(buf).to(dev)
+    base = d.data_ptr()
+    p = [base + 4 * int(o) for o in off[:-1]]
+    with torch.cuda.device(dev):
+        lib().call('fami_pose_nms_f32', p[0], p[1], p[2], p[3], p[4], p[5], N, J, M, in_vis_thre, oks_thre,
+                   1 if soft else 0, int(max_dets), 0.0 if vis is None else vis, 0 if vis is None else 1, p[6], p[7], p[8],
+                   torch.cuda.current_stream(dev).cuda_stream)
+    out = d[int(off[6]):].cpu().numpy()
+    scores = out[:N].view(np.float32).astype(np.float64)
+    rank, kept = out[N:2 * N], out[2 * N:]
+    if (kept < 0).any():
+        raise RuntimeError('pose_nms: the kernel refused image %r' % (keys[int(np.argmax(kept < 0))],))
+    # the kept rows of all images, ordered by (image, rank), then cut at the per-image counts
+    r = rank[index]
+    sel = np.flatnonzero(r >= 0)
+    image = np.repeat(np.arange(M), np.diff(seg))[sel]
+    rows = index[sel][np.lexsort((r[sel], image))].tolist()
+    cut = np.concatenate([[0], np.cumsum(kept)]).tolist()
+    keep_map = {key: rows[cut[m]:cut[m + 1]] for m, key in enumerate(keys)}
+    return scores, keep_map
 
 
 # ---------------------------------------------------------------------------------------- PoseTrack JSON writer

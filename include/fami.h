@@ -498,6 +498,34 @@ int fami_mirror_cat_f32(const float* x, float* out, long long rows, int W, fami_
 int fami_flip_merge_f32(const float* hm2, const int* perm, float* out, int B, int J, int H, int W, int shift,
                         fami_stream_t stream);
 
+/* Pose rescoring and OKS-NMS (the third step of the HRNet evaluation protocol; datasets/process/nms.py:51-192 oks_iou,
+ * oks_nms, _rescore, soft_oks_nms, and the rescoring rule behind VAL/TEST.IN_VIS_THRE; csrc/nms.hip).  All pointers are
+ * DEVICE memory, 4-byte aligned.  kpts [N,J,3] fp32 (x, y, confidence per joint, image pixels); area, box_score [N];
+ * sigmas [J]; index [N] and seg [M+1] int: the detections of image m are index[seg[m] .. seg[m+1]) -- rows of kpts in
+ * any order, at most 256 per image, an empty segment is legal.  Per image, in fp64 on the fp32 inputs:
+ *   score[g] = box_score[g] * mean(conf over the joints with conf > in_vis_thre) (mean 0 when none passes), rounded to
+ *     fp32 once; written for every listed detection, kept or not.
+ *   The detections are then picked by descending working score (initially the fp32 score; ties: the lower position in
+ *     the image's list).  OKS(picked, d) = mean over the masked joints of
+ *     exp(-(dx^2 + dy^2) / (2 sigma_j)^2 / ((area_p + area_d) / 2 + 2^-52) / 2), and 0 on an empty mask.  The mask is
+ *     conf_j(d) > vis_thre with use_vis != 0 -- the visibility of the COMPARED detection d only, as the reference's
+ *     `list(vg > t) and list(vd > t)` evaluates -- and all joints with use_vis == 0.
+ *   soft == 0 (oks_nms): a picked detection drops every remaining one with OKS > oks_thre; max_dets is not read.
+ *   soft != 0 (soft_oks_nms, Gaussian): it multiplies every remaining working score by exp(-OKS^2 / oks_thre); at most
+ *     max_dets are picked.  The working scores stay inside the kernel.
+ *   rank[g] = position of g among its image's picks (0 = picked first), -1 = not kept; kept[m] = number picked.
+ * One launch, one workgroup per image, no atomics, no workspace, no host read-back: bitwise reproducible.
+ * Returns -1 before any launch for a null or misaligned pointer, J outside 1 .. 32, N outside 1 .. (2^31 - 1) / (3 J),
+ * M outside 1 .. 2^31 - 2, a NaN threshold, and in soft mode oks_thre <= 0 or max_dets < 1.  index and seg are in
+ * device memory and are not checked here (fami_pose_amd.evaluate.pose_nms does): an image whose segment is longer than
+ * 256, is no sub-range of [0, N] or names a row outside [0, N) gets kept[m] = -1 and rank = -1 for each of its rows that
+ * can be addressed (scores are still written for an over-long segment); nothing outside the three outputs is ever
+ * written and other images are not affected.  A row listed twice has two writers (undefined which wins). */
+int fami_pose_nms_f32(const float* kpts, const float* area, const float* box_score, const float* sigmas,
+                      const int* index, const int* seg, int N, int J, int M, double in_vis_thre, double oks_thre,
+                      int soft, int max_dets, double vis_thre, int use_vis, float* score, int* rank, int* kept,
+                      fami_stream_t stream);
+
 /* ---- input pipeline on the device -------------------------------------------------------------
  * cv2.warpAffine(frame, trans, (Wd, Hd), flags=INTER_LINEAR) on the F 8-bit HWC frames of one clip (one transform
  * for key + supporting frames, datasets/zoo/posetrack/PoseTrack_Alignment.py:421-427; flip = source mirrored in x
