@@ -151,6 +151,13 @@ static inline long bn_slots_bytes(int C) { return (long)BN_NS_MAX * 2 * C * 8 + 
 __host__ __device__ static inline float* bn_slots_pivot(void* slots, int C) {
   return reinterpret_cast<float*>(reinterpret_cast<double*>(slots) + (long)BN_NS_MAX * 2 * C);
 }
+// scale / shift of the normalisation exactly as the two-launch forward applies them (norm.hip bn_apply2_kernel, the XBN /
+// bnin staging of the convolutions): explicit fused multiply-adds.  The ONE copy: the backward passes and the convolution
+// epilogues recompute the ReLU mask (relu == 2) from it and must agree with the forward bit for bit.
+__device__ __forceinline__ void bn_scale_shift(float mean, float invstd, float gamma, float beta, float& sc, float& sf) {
+  sc = invstd * gamma;
+  sf = __builtin_fmaf(-mean, sc, beta);
+}
 
 // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (linear id % 8), each with its own 4 MB L2:
 // with the natural order, neighbouring pixel tiles -- which share their 3x3 halo rows -- sit in 8 different L2s and

@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32(ConvArgs p) {
       } else {
         emu = e->mean[cc];
         eis = e->invstd[cc];
-        epi_scale_shift(emu, eis, e->gamma[cc], e->beta[cc], esc, esf);
+        bn_scale_shift(emu, eis, e->gamma[cc], e->beta[cc], esc, esf);
       }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -1002,7 +1002,7 @@ __global__ __launch_bounds__(256) void conv_igemm_h(ConvArgsH p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a, b;
-          epi_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
+          bn_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
           esc[r] = a;
           esf[r] = b;
         }
@@ -1390,7 +1390,7 @@ __global__ __launch_bounds__(256) void conv3x3_lds_kernel(ConvLdsArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a, b;
-          epi_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
+          bn_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
           esc[r] = a;
           esf[r] = b;
         }

@@ -46,12 +46,6 @@ typedef const EpiBN* EpiPtr;
 __device__ inline EpiPtr epi_late(unsigned) { return nullptr; }
 #endif
 
-// the forward apply pass's scale / shift (norm.hip bn_scale_shift): the recomputed ReLU mask must match it bit for bit
-__device__ __forceinline__ void epi_scale_shift(float mean, float invstd, float gamma, float beta, float& sc, float& sf) {
-  sc = invstd * gamma;
-  sf = __builtin_fmaf(-mean, sc, beta);
-}
-
 // v rounded to storage type H and widened again (what a later pass over the stored tensor would read)
 template <typename H>
 __device__ __forceinline__ f32x4 ld4_round(f32x4 v) {
@@ -81,7 +75,10 @@ static inline XBN xbn_none() {
   x.P = 0; x.momentum = 0.f; x.eps = 0.f; x.C = 0; x.ns = 0; x.on = 0; x.out = nullptr;
   return x;
 }
-// scale / shift of channel c into (sc, sf); forward form also publishes mean / invstd / running statistics when `publish`
+// scale / shift of channel c into (sc, sf); forward form also publishes mean / invstd / running statistics when `publish`.
+// The slot fold, moments and running update below repeat norm.hip's helpers on purpose: calling them from here re-schedules
+// the convolution kernels (one conv3x3_t4_kernel instance 180 -> 181 VGPRs, 14 of 136 conv3x3_t6_kernel instances another
+// SGPR count), so this copy stays.  Only bn_scale_shift (common.h), which the ReLU masks depend on bit for bit, is shared.
 __device__ __forceinline__ void xbn_channel(const XBN& x, int c, bool publish, float& sc, float& sf) {
   float muf, isf;
   if (x.slots) {
@@ -110,7 +107,7 @@ __device__ __forceinline__ void xbn_channel(const XBN& x, int c, bool publish, f
     muf = x.mean[c];
     isf = x.invstd[c];
   }
-  epi_scale_shift(muf, isf, x.gamma[c], x.beta[c], sc, sf);
+  bn_scale_shift(muf, isf, x.gamma[c], x.beta[c], sc, sf);
 }
 // 8 staged 16-bit values (one 16-byte piece, channels c0 .. c0+7) -> relu(fma(v, sc, sf)), tables in LDS
 template <typename H>

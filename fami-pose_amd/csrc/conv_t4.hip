@@ -422,7 +422,7 @@ __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float a, b;
-          epi_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
+          bn_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
           esc[r] = a;
           esf[r] = b;
         }

@@ -446,7 +446,7 @@ __device__ __forceinline__ void conv3x3_t5_body(const ConvT5Args& p, const int b
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float a, b;
-            epi_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
+            bn_scale_shift(emu[r], eis[r], ga[r], be[r], a, b);
             esc[r] = a;
             esf[r] = b;
           }

@@ -156,7 +156,7 @@ __device__ __forceinline__ void conv3x3_t6_body(const ConvT6Args& p, const int b
       const int co = ntg0 * 16 + tid;
       const float mu = e->mean[co], is = e->invstd[co];
       float a = 0.f, b = 0.f;
-      if (rmode == 2) epi_scale_shift(mu, is, e->gamma[co], e->beta[co], a, b);
+      if (rmode == 2) bn_scale_shift(mu, is, e->gamma[co], e->beta[co], a, b);
       ctab[tid] = mu;
       ctab[NT * 16 + tid] = is;
       ctab[2 * NT * 16 + tid] = a;
@@ -648,7 +648,7 @@ __device__ __forceinline__ void conv3x3_t7_body(const ConvT7Args& p, const int b
       const int co = ntg0 * 16 + tid;
       const float mu = e->mean[co], is = e->invstd[co];
       float a = 0.f, b = 0.f;
-      if (rmode == 2) epi_scale_shift(mu, is, e->gamma[co], e->beta[co], a, b);
+      if (rmode == 2) bn_scale_shift(mu, is, e->gamma[co], e->beta[co], a, b);
       ctab[tid] = mu;
       ctab[NT * 16 + tid] = is;
       ctab[2 * NT * 16 + tid] = a;

@@ -41,9 +41,106 @@ __device__ __forceinline__ double block_sum_d(double v, double* sm4) {
   return (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
 }
 
-// partial[g][0][c] = sum (x - K), partial[g][1][c] = sum (x - K)^2 over this block's pixels, with the pivot
-// K[c] = x[0][c] (the first pixel): shifted sums keep E[d^2] - E[d]^2 free of the cancellation that the raw
-// moments suffer when |mean| >> std.
+// ---- the pieces every generation of the kernels below shares (three-launch, two-launch slot, one-launch small forms)
+
+// forward statistics walk: s = sum (x - K), q = sum (x - K)^2 over this thread's rows of its 4-channel column, with the pivot
+// K[c] = x[0][c] (the first pixel): shifted sums keep E[d^2] - E[d]^2 free of the cancellation that the raw moments suffer
+// when |mean| >> std.
+template <typename T>
+__device__ __forceinline__ void bn_fwd_sums(const T* __restrict__ x, const ColMap& m, long P, int C, f32x4& s, f32x4& q) {
+  const f32x4 piv = ld4(x + m.cv * 4);
+  // BN_U rows per thread in flight: with one load per thread and <= 512 workgroups the pass is bound by memory
+  // latency (8 KB in flight per CU), not bandwidth.  The sums are taken in the same row order as a rolled loop.
+  // Main loop + rolled tail, NOT the clamped re-read of the backward walk (bn_bwd_sums): that form measured +7 % here.
+  const long step = (long)gridDim.x * m.rows;
+  long p = (long)blockIdx.x * m.rows + m.prow;
+  for (; p + (BN_U - 1) * step < P; p += BN_U * step) {
+    f32x4 v[BN_U];
+#pragma unroll
+    for (int u = 0; u < BN_U; ++u) v[u] = ld4(x + (p + u * step) * C + m.cv * 4);
+#pragma unroll
+    for (int u = 0; u < BN_U; ++u) {
+      const f32x4 d = v[u] - piv;
+      s += d;
+      q += d * d;
+    }
+  }
+  for (; p < P; p += step) {
+    const f32x4 v = ld4(x + p * C + m.cv * 4) - piv;
+    s += v;
+    q += v * v;
+  }
+}
+
+// a thread's two sums into its row of the [rows][2][C] LDS stage
+__device__ __forceinline__ void bn_stage_rows(float* sm, const ColMap& m, int C, f32x4 s, f32x4 q) {
+  float* d = sm + (long)m.prow * 2 * C;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    d[m.cv * 4 + t] = s[t];
+    d[C + m.cv * 4 + t] = q[t];
+  }
+}
+
+// fold of the [rows][2][C] LDS stage over its rows, with the two endings: the workgroup's row of the partial array
+// (three-launch forms: fixed order, run-to-run bitwise), or an fp64 atomic add into slot row blockIdx.x % NS (two-launch forms)
+template <bool SLOTS>
+__device__ __forceinline__ void bn_fold_rows(const float* sm, int rows, int C, float* __restrict__ partial,
+                                             double* __restrict__ slots, int NS) {
+  __syncthreads();
+  for (int e = threadIdx.x; e < 2 * C; e += 256) {
+    float tot = 0.f;
+    for (int r = 0; r < rows; ++r) tot += sm[(long)r * 2 * C + e];
+    if (SLOTS) unsafeAtomicAdd(slots + (long)(blockIdx.x % NS) * 2 * C + e, (double)tot);
+    else partial[(long)blockIdx.x * 2 * C + e] = tot;
+  }
+}
+
+// s = sum_k slots[k][0][c], q = sum_k slots[k][1][c]
+__device__ __forceinline__ void bn_fold_slots(const double* __restrict__ slots, int NS, int C, int c, double& s, double& q) {
+  s = 0.0;
+  q = 0.0;
+  for (int k = 0; k < NS; ++k) {
+    s += slots[(long)k * 2 * C + c];
+    q += slots[(long)k * 2 * C + C + c];
+  }
+}
+
+// mean and biased variance from dm = E[x - K], dq = E[(x - K)^2] and the pivot K, in fp64
+struct BnMoments {
+  double mu, var;
+};
+__device__ __forceinline__ float bn_invstd(double var, float eps) { return (float)(1.0 / sqrt(var + (double)eps)); }
+__device__ __forceinline__ BnMoments bn_moments(double dm, double dq, double piv) {
+  double var = dq - dm * dm;
+  if (var < 0.0) var = 0.0;
+  return BnMoments{piv + dm, var};
+}
+// The two arithmetic forms of the expectations stay apart (they round differently): by division in the three-launch and
+// one-launch forms ...
+__device__ __forceinline__ BnMoments bn_moments_div(double s, double q, long P, double piv) {
+  return bn_moments(s / (double)P, q / (double)P, piv);
+}
+// ... and by one reciprocal in the slot forms (as conv_epi.h xbn_channel takes them)
+__device__ __forceinline__ BnMoments bn_moments_rcp(double s, double q, long P, double piv) {
+  const double invP = 1.0 / (double)P;
+  return bn_moments(s * invP, q * invP, piv);
+}
+// biased variance back from a finalised invstd
+__device__ __forceinline__ double bn_var_of_invstd(double is, float eps) {
+  double var = 1.0 / (is * is) - (double)eps;
+  if (var < 0.0) var = 0.0;
+  return var;
+}
+
+// running statistics of channel c: momentum step towards the batch mean and the UNBIASED batch variance
+__device__ __forceinline__ void bn_running_update(float* rm, float* rv, int c, double mu, double var, double P, float momentum) {
+  const double unb = P > 1.0 ? var * P / (P - 1.0) : var;
+  rm[c] = (float)((1.0 - momentum) * rm[c] + momentum * mu);
+  rv[c] = (float)((1.0 - momentum) * rv[c] + momentum * unb);
+}
+
+// partial[g][0][c] = sum (x - K), partial[g][1][c] = sum (x - K)^2 over this block's pixels (bn_fwd_sums)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x, float* __restrict__ partial,
                                                          long P, int C) {
@@ -51,40 +148,10 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x
   const ColMap m = col_map(C);
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
   if (m.active) {
-    const f32x4 piv = ld4(x + m.cv * 4);
-    // BN_U rows per thread in flight: with one load per thread and <= 512 workgroups the pass is bound by memory
-    // latency (8 KB in flight per CU), not bandwidth.  The sums are taken in the same row order as a rolled loop.
-    const long step = (long)gridDim.x * m.rows;
-    long p = (long)blockIdx.x * m.rows + m.prow;
-    for (; p + (BN_U - 1) * step < P; p += BN_U * step) {
-      f32x4 v[BN_U];
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) v[u] = ld4(x + (p + u * step) * C + m.cv * 4);
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        const f32x4 d = v[u] - piv;
-        s += d;
-        q += d * d;
-      }
-    }
-    for (; p < P; p += step) {
-      const f32x4 v = ld4(x + p * C + m.cv * 4) - piv;
-      s += v;
-      q += v * v;
-    }
-    float* d = sm + (long)m.prow * 2 * C;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      d[m.cv * 4 + t] = s[t];
-      d[C + m.cv * 4 + t] = q[t];
-    }
+    bn_fwd_sums(x, m, P, C, s, q);
+    bn_stage_rows(sm, m, C, s, q);
   }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * C; e += 256) {
-    float tot = 0.f;
-    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
-    partial[(long)blockIdx.x * 2 * C + e] = tot;
-  }
+  bn_fold_rows<false>(sm, m.rows, C, partial, nullptr, 0);
 }
 
 template <typename T>
@@ -101,17 +168,10 @@ __global__ void bn_finalize_kernel(const float* __restrict__ partial, const T* _
   s = block_sum_d(s, sm4);
   q = block_sum_d(q, sm4);
   if (threadIdx.x != 0) return;
-  const double dm = s / (double)P;              // mean of (x - pivot)
-  double var = q / (double)P - dm * dm;
-  if (var < 0.0) var = 0.0;
-  const double mu = (double)ld1(x + c) + dm;
-  mean[c] = (float)mu;
-  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mu);
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-  }
+  const BnMoments mo = bn_moments_div(s, q, P, (double)ld1(x + c));
+  mean[c] = (float)mo.mu;
+  invstd[c] = bn_invstd(mo.var, eps);
+  if (running_mean) bn_running_update(running_mean, running_var, c, mo.mu, mo.var, (double)P, momentum);
 }
 
 // mean / invstd (+ running statistics) from slot rows a convolution epilogue filled (fuse terms: the cross-resolution sum
@@ -121,23 +181,12 @@ __global__ void bn_finalize_slots_kernel(const double* __restrict__ slots, int N
                                          float momentum, float eps) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double s = 0.0, q = 0.0;
-  for (int k = 0; k < NS; ++k) {
-    s += slots[(long)k * 2 * C + c];
-    q += slots[(long)k * 2 * C + C + c];
-  }
-  const double invP = 1.0 / (double)P;
-  const double dm = s * invP;
-  double var = q * invP - dm * dm;
-  if (var < 0.0) var = 0.0;
-  const double mu = (double)pivot[c] + dm;
-  mean[c] = (float)mu;
-  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mu);
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-  }
+  double s, q;
+  bn_fold_slots(slots, NS, C, c, s, q);
+  const BnMoments mo = bn_moments_rcp(s, q, P, (double)pivot[c]);
+  mean[c] = (float)mo.mu;
+  invstd[c] = bn_invstd(mo.var, eps);
+  if (running_mean) bn_running_update(running_mean, running_var, c, mo.mu, mo.var, (double)P, momentum);
 }
 
 // running statistics from an already finalised (mean, invstd): lets BatchNorm calls that SHARE a module run concurrently
@@ -147,14 +196,8 @@ __global__ void bn_running_update_kernel(float* running_mean, float* running_var
                                          const float* __restrict__ invstd, int C, long P, float momentum, float eps) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double mu = (double)mean[c], is = (double)invstd[c];
-  double var = 1.0 / (is * is) - (double)eps;
-  if (var < 0.0) var = 0.0;
-  const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-  running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mu);
-  running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
+  bn_running_update(running_mean, running_var, c, (double)mean[c], bn_var_of_invstd((double)invstd[c], eps), (double)P, momentum);
 }
-
 
 // Batched form: the deferred updates of a forked region (32 per step for the translation regressors) in ONE launch, in
 // call order -- thread c walks the entries sequentially for its channel, so several updates of one module's buffers
@@ -166,14 +209,8 @@ __global__ __launch_bounds__(256) void bn_running_update_batch_kernel(BnRunBatch
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   for (int k = 0; k < b.n; ++k) {
     if (c >= b.C[k]) continue;
-    const double mu = (double)b.mean[k][c], is = (double)b.invstd[k][c];
-    double var = 1.0 / (is * is) - (double)b.eps[k];
-    if (var < 0.0) var = 0.0;
-    const double P = (double)b.P[k];
-    const double unb = P > 1.0 ? var * P / (P - 1.0) : var;
-    const float momentum = b.mom[k];
-    b.rm[k][c] = (float)((1.0 - momentum) * b.rm[k][c] + momentum * mu);
-    b.rv[k][c] = (float)((1.0 - momentum) * b.rv[k][c] + momentum * unb);
+    bn_running_update(b.rm[k], b.rv[k], c, (double)b.mean[k][c], bn_var_of_invstd((double)b.invstd[k][c], b.eps[k]),
+                      (double)b.P[k], b.mom[k]);
   }
 }
 
@@ -186,6 +223,8 @@ __global__ void bn_eval_stats_kernel(const float* running_mean, const float* run
 }
 
 // y = [relu]( (x-mean)*invstd*gamma + beta [+ residual] )
+// NOT bn_scale_shift: here (and in bn_small_fwd_kernel) sf = beta - mean*sc and x*sc + sf are left to the compiler's contraction;
+// the relu == 2 mask and the convolution-side XBN / bnin kernels are bit-matched to bn_apply2_kernel's explicit fmas only.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, const float* __restrict__ mean,
                                                        const float* __restrict__ invstd,
@@ -214,6 +253,72 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
   }
 }
 
+// ReLU mask of a BatchNorm output from the stored output y: dz = dy*(y > 0)
+__device__ __forceinline__ f32x4 bn_relu_mask(f32x4 g, f32x4 yy) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) g[t] = yy[t] > 0.f ? g[t] : 0.f;
+  return g;
+}
+// relu 0 = none, 1 = from y, 2 = recomputed from x (only valid without a residual, and only against a forward that applied
+// bn_scale_shift with explicit fused multiply-adds: bn_apply2_kernel)
+__device__ __forceinline__ f32x4 bn_relu_mask(f32x4 g, int relu, f32x4 yy, f32x4 xv, f32x4 sc, f32x4 sf) {
+  if (relu == 1) return bn_relu_mask(g, yy);
+  if (relu == 2) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) g[t] = __builtin_fmaf(xv[t], sc[t], sf[t]) > 0.f ? g[t] : 0.f;
+  }
+  return g;
+}
+
+// mean / invstd of this thread's four channels
+__device__ __forceinline__ void bn_load_stats(const float* __restrict__ mean, const float* __restrict__ invstd, int c0, f32x4& mu,
+                                              f32x4& is) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    mu[t] = mean[c0 + t];
+    is[t] = invstd[c0 + t];
+  }
+}
+
+// backward statistics walk: s = sum dz, q = sum dz*xhat over this thread's rows; dz = bn_relu_mask(dy) (sc / sf: relu 2 only).
+// The spelling of the two relu tests is the one that keeps both callers' register counts at or below what their own copies of
+// this loop had (`relu == 1` on the y loads, or one three-way bn_relu_mask call: +1 SGPR on one, +4-6 VGPRs on the other).
+template <typename T>
+__device__ __forceinline__ void bn_bwd_sums(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ y,
+                                            const ColMap& m, long P, int C, int relu, f32x4 mu, f32x4 is, f32x4 sc, f32x4 sf,
+                                            f32x4& s, f32x4& q) {
+  const long step = (long)gridDim.x * m.rows;
+  // Rows past the end re-read row p (a cache hit) and contribute an exact 0: the 3-7 rows per thread of the
+  // low-resolution branches then also go out BN_U at a time instead of through a rolled tail (backward statistics
+  // of the 48x36 / 24x18 maps -3...-11 %; the same form measured +7 % on the forward statistics of the 96x72 map,
+  // which keeps the main loop + rolled tail: bn_fwd_sums).
+  for (long p = (long)blockIdx.x * m.rows + m.prow; p < P; p += BN_U * step) {
+    f32x4 g[BN_U], yy[BN_U], xx[BN_U];
+    long o[BN_U];
+#pragma unroll
+    for (int u = 0; u < BN_U; ++u) {
+      const long pu = p + u * step;
+      o[u] = (pu < P ? pu : p) * C + m.cv * 4;
+      g[u] = ld4(dy + o[u]);
+    }
+    if (relu & 1) {  // relu 1 of {0, 1, 2}
+#pragma unroll
+      for (int u = 0; u < BN_U; ++u) yy[u] = ld4(y + o[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < BN_U; ++u) xx[u] = ld4(x + o[u]);
+#pragma unroll
+    for (int u = 0; u < BN_U; ++u) {
+      if (relu == 1) g[u] = bn_relu_mask(g[u], yy[u]);
+      if (relu == 2) g[u] = bn_relu_mask(g[u], relu, yy[u], xx[u], sc, sf);
+      if (p + u * step >= P) g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 xh = (xx[u] - mu) * is;
+      s += g[u];
+      q += g[u] * xh;
+    }
+  }
+}
+
 // backward pass 1: partial[g][0][c] = sum dz, partial[g][1][c] = sum dz*xhat ; dz = relu ? dy*(y>0) : dy
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict__ dy,
@@ -227,56 +332,12 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
   if (m.active) {
     f32x4 mu, is;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      mu[t] = mean[m.cv * 4 + t];
-      is[t] = invstd[m.cv * 4 + t];
-    }
-    const long step = (long)gridDim.x * m.rows;
-    // Rows past the end re-read row p (a cache hit) and contribute an exact 0: the 3-7 rows per thread of the
-    // low-resolution branches then also go out BN_U at a time instead of through a rolled tail (backward statistics
-    // of the 48x36 / 24x18 maps -3...-11 %; the same form measured +7 % on the forward statistics of the 96x72 map,
-    // which keeps the main loop + rolled tail).
-    for (long p = (long)blockIdx.x * m.rows + m.prow; p < P; p += BN_U * step) {
-      f32x4 g[BN_U], yy[BN_U], xx[BN_U];
-      long o[BN_U];
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        const long pu = p + u * step;
-        o[u] = (pu < P ? pu : p) * C + m.cv * 4;
-        g[u] = ld4(dy + o[u]);
-      }
-      if (relu) {
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) yy[u] = ld4(y + o[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) xx[u] = ld4(x + o[u]);
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        if (relu) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) g[u][t] = yy[u][t] > 0.f ? g[u][t] : 0.f;
-        }
-        if (p + u * step >= P) g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const f32x4 xh = (xx[u] - mu) * is;
-        s += g[u];
-        q += g[u] * xh;
-      }
-    }
-    float* d = sm + (long)m.prow * 2 * C;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      d[m.cv * 4 + t] = s[t];
-      d[C + m.cv * 4 + t] = q[t];
-    }
+    bn_load_stats(mean, invstd, m.cv * 4, mu, is);
+    const f32x4 none = {0.f, 0.f, 0.f, 0.f};  // any non-zero relu is "mask from y" here: no recomputed mask, no scale / shift
+    bn_bwd_sums(dy, x, y, m, P, C, relu ? 1 : 0, mu, is, none, none, s, q);
+    bn_stage_rows(sm, m, C, s, q);
   }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * C; e += 256) {
-    float tot = 0.f;
-    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
-    partial[(long)blockIdx.x * 2 * C + e] = tot;
-  }
+  bn_fold_rows<false>(sm, m.rows, C, partial, nullptr, 0);
 }
 
 // coef[0][c] = mean(dz), coef[1][c] = mean(dz*xhat) (coef optional); dgamma/dbeta optional
@@ -298,6 +359,20 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ partial, int G,
   }
   if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
   if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
+}
+
+// one 4-channel row of the train-mode backward: dx (=|+=) gamma*invstd*(dz - c1 - xhat*c2) ; dres (=|+=) dz
+template <typename T>
+__device__ __forceinline__ void bn_bwd_row(T* __restrict__ dx, T* __restrict__ dres, long o, f32x4 g, f32x4 xh, f32x4 gi, f32x4 c1,
+                                           f32x4 c2, int acc_dx, int acc_dres) {
+  f32x4 d = gi * (g - c1 - xh * c2);
+  if (acc_dx) d += ld4(dx + o);
+  st4(dx + o, d);
+  if (dres) {
+    f32x4 r = g;
+    if (acc_dres) r += ld4(dres + o);
+    st4(dres + o, r);
+  }
 }
 
 // backward pass 2: dx = gamma*invstd*(dz - c1 - xhat*c2) ; dres (=|+=) dz
@@ -325,26 +400,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   for (long p = (long)blockIdx.x * m.rows + m.prow; p < P; p += (long)gridDim.x * m.rows) {
     const long o = p * C + m.cv * 4;
     f32x4 g = ld4(dy + o);
-    if (relu) {
-      const f32x4 yy = ld4(y + o);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) g[t] = yy[t] > 0.f ? g[t] : 0.f;
-    }
-    const f32x4 xh = (ld4(x + o) - mu) * is;
-    f32x4 d = gi * (g - c1 - xh * c2);
-    if (acc_dx) d += ld4(dx + o);
-    st4(dx + o, d);
-    if (dres) {
-      f32x4 r = g;
-      if (acc_dres) r += ld4(dres + o);
-      st4(dres + o, r);
-    }
+    if (relu) g = bn_relu_mask(g, ld4(y + o));
+    bn_bwd_row(dx, dres, o, g, (ld4(x + o) - mu) * is, gi, c1, c2, acc_dx, acc_dres);
   }
 }
 
 // ---- backward with FROZEN statistics (eval-mode BatchNorm, Engine.bn_batch_stats false): mean / invstd are constants, not
 // functions of x, so the batch terms of the train-mode backward vanish and ONE pass does it:
 //   dz = relu ? dy*(y>0) : dy ; dx (=|+=) dz*gamma*invstd ; dres (=|+=) dz
+// The walk is bn_bwd_sums' with the dx / dres loads and stores woven into it, so it stays here (sharing it would make the
+// shared walk branch on its caller); the mask, the LDS stage and the fold are the shared ones.
 // SUMS: the workgroup also leaves partial[g][0][c] = sum dz, partial[g][1][c] = sum dz*xhat for bn_bwd_finalize_kernel
 // (fixed order, fp64: run-to-run bitwise).  Without SUMS (gamma / beta frozen too) x and mean are never read: dy (+ y) in,
 // dx out.  BN_U rows per thread in flight; rows past the end re-read row p (a cache hit), contribute an exact 0 to the sums
@@ -396,10 +461,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ 
       }
 #pragma unroll
       for (int u = 0; u < BN_U; ++u) {
-        if (relu) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) g[u][t] = yy[u][t] > 0.f ? g[u][t] : 0.f;
-        }
+        if (relu) g[u] = bn_relu_mask(g[u], yy[u]);
         const bool in = p + u * step < P;
         if (SUMS) {
           const f32x4 gz = in ? g[u] : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -418,22 +480,9 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T* __restrict__ 
         }
       }
     }
-    if (SUMS) {
-      float* d = sm + (long)m.prow * 2 * C;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        d[m.cv * 4 + t] = s[t];
-        d[C + m.cv * 4 + t] = q[t];
-      }
-    }
+    if (SUMS) bn_stage_rows(sm, m, C, s, q);
   }
-  if (!SUMS) return;
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * C; e += 256) {
-    float tot = 0.f;
-    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
-    partial[(long)blockIdx.x * 2 * C + e] = tot;
-  }
+  if (SUMS) bn_fold_rows<false>(sm, m.rows, C, partial, nullptr, 0);
 }
 
 // ---- two-launch forms (fami_bn_train_fwd2 / fami_bn_bwd2): the statistics pass adds its per-workgroup partial sums into
@@ -452,45 +501,10 @@ __global__ __launch_bounds__(256) void bn_partial2_kernel(const T* __restrict__ 
   const ColMap m = col_map(C);
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
   if (m.active) {
-    const f32x4 piv = ld4(x + m.cv * 4);
-    const long step = (long)gridDim.x * m.rows;
-    long p = (long)blockIdx.x * m.rows + m.prow;
-    for (; p + (BN_U - 1) * step < P; p += BN_U * step) {
-      f32x4 v[BN_U];
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) v[u] = ld4(x + (p + u * step) * C + m.cv * 4);
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        const f32x4 d = v[u] - piv;
-        s += d;
-        q += d * d;
-      }
-    }
-    for (; p < P; p += step) {
-      const f32x4 v = ld4(x + p * C + m.cv * 4) - piv;
-      s += v;
-      q += v * v;
-    }
-    float* d = sm + (long)m.prow * 2 * C;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      d[m.cv * 4 + t] = s[t];
-      d[C + m.cv * 4 + t] = q[t];
-    }
+    bn_fwd_sums(x, m, P, C, s, q);
+    bn_stage_rows(sm, m, C, s, q);
   }
-  __syncthreads();
-  double* row = slots + (long)(blockIdx.x % NS) * 2 * C;
-  for (int e = threadIdx.x; e < 2 * C; e += 256) {
-    float tot = 0.f;
-    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
-    unsafeAtomicAdd(row + e, (double)tot);
-  }
-}
-
-// scale / shift of the normalisation exactly as the forward applies them; the backward recomputes the ReLU mask from them
-__device__ __forceinline__ void bn_scale_shift(float mean, float invstd, float gamma, float beta, float& sc, float& sf) {
-  sc = invstd * gamma;
-  sf = __builtin_fmaf(-mean, sc, beta);
+  bn_fold_rows<true>(sm, m.rows, C, nullptr, slots, NS);
 }
 
 // y = [relu]( (x-mean)*invstd*gamma + beta [+ residual] ), mean / invstd folded from the slot rows by every workgroup
@@ -506,26 +520,14 @@ __global__ __launch_bounds__(256) void bn_apply2_kernel(const T* __restrict__ x,
   // convolution epilogue that filled the slots wrote behind them (conv.hip, EpiBN mode 1)
   extern __shared__ float sm[];  // [2][C]: scale, shift
   for (int c = threadIdx.x; c < C; c += 256) {
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < NS; ++k) {
-      s += slots[(long)k * 2 * C + c];
-      q += slots[(long)k * 2 * C + C + c];
-    }
-    const double invP = 1.0 / (double)P;
-    const double dm = s * invP;                       // mean of (x - pivot)
-    double var = q * invP - dm * dm;
-    if (var < 0.0) var = 0.0;
-    const double mu = (double)(pivot ? pivot[c] : ld1(x + c)) + dm;
-    const float muf = (float)mu;
-    const float isf = (float)(1.0 / sqrt(var + (double)eps));
+    double s, q;
+    bn_fold_slots(slots, NS, C, c, s, q);
+    const BnMoments mo = bn_moments_rcp(s, q, P, (double)(pivot ? pivot[c] : ld1(x + c)));
+    const float muf = (float)mo.mu, isf = bn_invstd(mo.var, eps);
     if (blockIdx.x == 0) {
       mean[c] = muf;
       invstd[c] = isf;
-      if (running_mean) {
-        const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-        running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mu);
-        running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-      }
+      if (running_mean) bn_running_update(running_mean, running_var, c, mo.mu, mo.var, (double)P, momentum);
     }
     float sc, sf;
     bn_scale_shift(muf, isf, gamma[c], beta[c], sc, sf);
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(256) void bn_apply2_kernel(const T* __restrict__ x,
     const f32x4 xv = ld4(x + o);
     f32x4 v;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = __builtin_fmaf(xv[t], sc[t], sf[t]);
+    for (int t = 0; t < 4; ++t) v[t] = __builtin_fmaf(xv[t], sc[t], sf[t]);  // explicit: bn_relu_mask (relu 2) recomputes exactly this
     if (residual) v += ld4(residual + o);
     if (relu) {
 #pragma unroll
@@ -549,19 +551,6 @@ __global__ __launch_bounds__(256) void bn_apply2_kernel(const T* __restrict__ x,
     }
     st4(y + o, v);
   }
-}
-
-// ReLU mask of a BatchNorm output: relu 1 = from the stored output y, relu 2 = recomputed from x (only valid without a
-// residual, and only against a forward that applied bn_scale_shift with explicit fused multiply-adds: bn_apply2_kernel)
-__device__ __forceinline__ f32x4 bn_relu_mask(f32x4 g, int relu, f32x4 yy, f32x4 xv, f32x4 sc, f32x4 sf) {
-  if (relu == 1) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) g[t] = yy[t] > 0.f ? g[t] : 0.f;
-  } else if (relu == 2) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) g[t] = __builtin_fmaf(xv[t], sc[t], sf[t]) > 0.f ? g[t] : 0.f;
-  }
-  return g;
 }
 
 template <typename T>
@@ -576,55 +565,18 @@ __global__ __launch_bounds__(256) void bn_bwd_partial2_kernel(const T* __restric
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
   if (m.active) {
     f32x4 mu, is, sc, sf;
+    bn_load_stats(mean, invstd, m.cv * 4, mu, is);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int c = m.cv * 4 + t;
-      mu[t] = mean[c];
-      is[t] = invstd[c];
       float a, b;
-      bn_scale_shift(mu[t], is[t], gamma[c], beta[c], a, b);
+      bn_scale_shift(mu[t], is[t], gamma[m.cv * 4 + t], beta[m.cv * 4 + t], a, b);
       sc[t] = a;
       sf[t] = b;
     }
-    const long step = (long)gridDim.x * m.rows;
-    for (long p = (long)blockIdx.x * m.rows + m.prow; p < P; p += BN_U * step) {
-      f32x4 g[BN_U], yy[BN_U], xx[BN_U];
-      long o[BN_U];
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        const long pu = p + u * step;
-        o[u] = (pu < P ? pu : p) * C + m.cv * 4;
-        g[u] = ld4(dy + o[u]);
-      }
-      if (relu == 1) {
-#pragma unroll
-        for (int u = 0; u < BN_U; ++u) yy[u] = ld4(y + o[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) xx[u] = ld4(x + o[u]);
-#pragma unroll
-      for (int u = 0; u < BN_U; ++u) {
-        g[u] = bn_relu_mask(g[u], relu, yy[u], xx[u], sc, sf);
-        if (p + u * step >= P) g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const f32x4 xh = (xx[u] - mu) * is;
-        s += g[u];
-        q += g[u] * xh;
-      }
-    }
-    float* d = sm + (long)m.prow * 2 * C;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      d[m.cv * 4 + t] = s[t];
-      d[C + m.cv * 4 + t] = q[t];
-    }
+    bn_bwd_sums(dy, x, y, m, P, C, relu, mu, is, sc, sf, s, q);
+    bn_stage_rows(sm, m, C, s, q);
   }
-  __syncthreads();
-  double* row = slots + (long)(blockIdx.x % NS) * 2 * C;
-  for (int e = threadIdx.x; e < 2 * C; e += 256) {
-    float tot = 0.f;
-    for (int r = 0; r < m.rows; ++r) tot += sm[(long)r * 2 * C + e];
-    unsafeAtomicAdd(row + e, (double)tot);
-  }
+  bn_fold_rows<true>(sm, m.rows, C, nullptr, slots, NS);
 }
 
 // dx = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)) ; dres (=|+=) dz ; the two means folded from the slot rows by
@@ -640,11 +592,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(const T* __restrict_
                                                             int C, int relu, int acc_dx, int acc_param, int acc_dres) {
   extern __shared__ float sm[];  // [2][C]: mean(dz), mean(dz*xhat)
   for (int c = threadIdx.x; c < C; c += 256) {
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < NS; ++k) {
-      s += slots[(long)k * 2 * C + c];
-      q += slots[(long)k * 2 * C + C + c];
-    }
+    double s, q;
+    bn_fold_slots(slots, NS, C, c, s, q);
     sm[c] = (float)(s / (double)P);
     sm[C + c] = (float)(q / (double)P);
     if (blockIdx.x == 0) {
@@ -675,15 +624,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(const T* __restrict_
     f32x4 yy = {0.f, 0.f, 0.f, 0.f};
     if (relu == 1) yy = ld4(y + o);
     g = bn_relu_mask(g, relu, yy, xv, sc, sf);
-    const f32x4 xh = (xv - mu) * is;
-    f32x4 d = gi * (g - c1 - xh * c2);
-    if (acc_dx) d += ld4(dx + o);
-    st4(dx + o, d);
-    if (dres) {
-      f32x4 r = g;
-      if (acc_dres) r += ld4(dres + o);
-      st4(dres + o, r);
-    }
+    bn_bwd_row(dx, dres, o, g, (xv - mu) * is, gi, c1, c2, acc_dx, acc_dres);
   }
 }
 
@@ -735,23 +676,16 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const T* __restrict__
   f32x4 mu, is, sc, sf;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    const double dm = (double)s[t] / (double)P;
-    double var = (double)q[t] / (double)P - dm * dm;
-    if (var < 0.0) var = 0.0;
-    const double m = (double)piv[t] + dm;
-    mu[t] = (float)m;
-    is[t] = (float)(1.0 / sqrt(var + (double)eps));
+    const BnMoments mo = bn_moments_div((double)s[t], (double)q[t], P, (double)piv[t]);
+    mu[t] = (float)mo.mu;
+    is[t] = bn_invstd(mo.var, eps);
     if (threadIdx.x == 0) {
       mean[c0 + t] = mu[t];
       invstd[c0 + t] = is[t];
-      if (running_mean) {
-        const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
-        running_mean[c0 + t] = (float)((1.0 - momentum) * running_mean[c0 + t] + momentum * m);
-        running_var[c0 + t] = (float)((1.0 - momentum) * running_var[c0 + t] + momentum * unb);
-      }
+      if (running_mean) bn_running_update(running_mean, running_var, c0 + t, mo.mu, mo.var, (double)P, momentum);
     }
     sc[t] = is[t] * gamma[c0 + t];
-    sf[t] = beta[c0 + t] - mu[t] * sc[t];
+    sf[t] = beta[c0 + t] - mu[t] * sc[t];  // the compiler's contraction, as in bn_apply_kernel: not bn_scale_shift
   }
   for (long p = threadIdx.x; p < P; p += 256) {
     const long o = p * C + c0;
@@ -775,21 +709,14 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const T* __restrict__
   __shared__ float sm[16];
   const int c0 = blockIdx.x * 4;
   f32x4 mu, is, gi;
+  bn_load_stats(mean, invstd, c0, mu, is);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    mu[t] = mean[c0 + t];
-    is[t] = invstd[c0 + t];
-    gi[t] = gamma[c0 + t] * is[t];
-  }
+  for (int t = 0; t < 4; ++t) gi[t] = gamma[c0 + t] * is[t];
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
   for (long p = threadIdx.x; p < P; p += 256) {
     const long o = p * C + c0;
     f32x4 g = ld4(dy + o);
-    if (relu) {
-      const f32x4 yy = ld4(y + o);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) g[t] = yy[t] > 0.f ? g[t] : 0.f;
-    }
+    if (relu) g = bn_relu_mask(g, ld4(y + o));
     s += g;
     q += g * ((ld4(x + o) - mu) * is);
   }
@@ -800,7 +727,7 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const T* __restrict__
   for (int t = 0; t < 4; ++t) {
     c1[t] = (float)((double)s[t] / (double)P);
     c2[t] = (float)((double)q[t] / (double)P);
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {  // the float sums as they are: the other forms add (float) of an fp64 sum
       if (dgamma) dgamma[c0 + t] = acc_param ? dgamma[c0 + t] + q[t] : q[t];
       if (dbeta) dbeta[c0 + t] = acc_param ? dbeta[c0 + t] + s[t] : s[t];
     }
@@ -808,20 +735,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const T* __restrict__
   for (long p = threadIdx.x; p < P; p += 256) {
     const long o = p * C + c0;
     f32x4 g = ld4(dy + o);
-    if (relu) {
-      const f32x4 yy = ld4(y + o);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) g[t] = yy[t] > 0.f ? g[t] : 0.f;
-    }
-    const f32x4 xh = (ld4(x + o) - mu) * is;
-    f32x4 d = gi * (g - c1 - xh * c2);
-    if (acc_dx) d += ld4(dx + o);
-    st4(dx + o, d);
-    if (dres) {
-      f32x4 r = g;
-      if (acc_dres) r += ld4(dres + o);
-      st4(dres + o, r);
-    }
+    if (relu) g = bn_relu_mask(g, ld4(y + o));
+    bn_bwd_row(dx, dres, o, g, (ld4(x + o) - mu) * is, gi, c1, c2, acc_dx, acc_dres);
   }
 }
 
@@ -893,43 +808,68 @@ __global__ void chan_sum_finalize_kernel(const float* __restrict__ partial, int 
   out[c] = accumulate ? out[c] + (float)s : (float)s;
 }
 
-static inline int bn_grid(long P, int C) {
-  const int rows = 256 / (C >> 2);
-  // at least 2*BN_U row steps per workgroup: on the low-resolution branches (12x9x384: 1080 row groups) a grid of 512
-  // made the partial array as large as the tensor itself and the finalize pass, which walks it with a stride, the
-  // longer half of the chain
-  long g = (P + (long)rows * 2 * BN_U - 1) / ((long)rows * 2 * BN_U);
-  if (g > BN_MAXG) g = BN_MAXG;
+static inline int bn_rows(int C) { return 256 / (C >> 2); }  // pixel rows a 256-thread workgroup covers at 4 channels per thread
+// workgroups that give each `steps` row steps over P pixels, at most `cap` and at least one
+static inline int bn_capped_grid(long P, int C, int steps, long cap) {
+  const long per = (long)bn_rows(C) * steps;
+  long g = (P + per - 1) / per;
+  if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
 }
+// at least 2*BN_U row steps per workgroup: on the low-resolution branches (12x9x384: 1080 row groups) a grid of 512
+// made the partial array as large as the tensor itself and the finalize pass, which walks it with a stride, the
+// longer half of the chain
+static inline int bn_grid(long P, int C) { return bn_capped_grid(P, C, 2 * BN_U, BN_MAXG); }
 // the statistics passes of the two-launch forms write no partial array (fp64 slot atomics), so their grid is not tied to BN_MAXG:
 // fami_bn_tune_small(-(1000 + n)) sets the cap (route field bn2_maxg)
 // Measured inside the step (tools/ab_env.py, caps 512 / 1024 / 2048 / 4096): f32 storage 45.50 / 45.45 / 45.30 ms and 46.68 / - / 46.64 /
 // 46.57 on a second box, config 4 (512x384, 8 frames) 116.8 / - / 116.5 / 116.2 ms; bf16 20.02 / 20.01 / 20.14 ms -- the f32 tensors of
 // the stem stretch are twice the bytes and want more loads in flight: four times the cap in f32 storage.
 static inline int bn_grid2(long P, int C, int esz) {
-  const int rows = 256 / (C >> 2);
-  long g = (P + (long)rows * 2 * BN_U - 1) / ((long)rows * 2 * BN_U);
-  const long cap = (long)g_bn2_maxg * (esz == 4 ? 4 : 1);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
+  return bn_capped_grid(P, C, 2 * BN_U, (long)g_bn2_maxg * (esz == 4 ? 4 : 1));
 }
-static inline bool bn_shape_ok(long P, int C) { return P > 0 && C >= 4 && (C % 4) == 0 && C <= 1024; }
+// apply passes, one row step at a time: the three-launch forms, and the two-launch forms whose every workgroup folds the slot
+// rows in its prologue -- fewer, longer workgroups
+static inline int bn_apply_grid(long P, int C) { return bn_capped_grid(P, C, 1, 2048); }
+static inline int bn_apply_grid2(long P, int C) { return bn_capped_grid(P, C, 1, 1024); }
+// FAMI_OK, or FAMI_ESHAPE with the error text set
+static inline int bn_check_shape(long P, int C, const char* nm) {
+  if (P > 0 && C >= 4 && (C % 4) == 0 && C <= 1024) return FAMI_OK;
+  fami_set_error(nm, "C must be a multiple of 4, <= 1024");
+  return FAMI_ESHAPE;
+}
+
+static inline size_t bn_stage_bytes(int C) { return (size_t)bn_rows(C) * 2 * C * sizeof(float); }  // the [rows][2][C] LDS stage
 
 // ------------------------------------------------------------------ host side (templates over the storage type)
+// the one-launch kernels, for both generations of the entry points
+template <typename T>
+static int bn_small_fwd_launch(const T* x, const T* residual, T* y, const float* gamma, const float* beta, float* mean,
+                               float* invstd, float* running_mean, float* running_var, long P, int C, int relu,
+                               float momentum, float eps, hipStream_t s, const char* nm) {
+  hipLaunchKernelGGL(bn_small_fwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, x, residual, y, gamma, beta, mean, invstd,
+                     running_mean, running_var, P, C, relu, momentum, eps);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+template <typename T>
+static int bn_small_bwd_launch(const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
+                               const float* gamma, T* dx, float* dgamma, float* dbeta, T* dres, long P, int C, int relu,
+                               int acc_dx, int acc_param, int acc_dres, hipStream_t s, const char* nm) {
+  hipLaunchKernelGGL(bn_small_bwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, dx, dgamma,
+                     dbeta, dres, P, C, relu, acc_dx, acc_param, acc_dres);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+
 template <typename T>
 static int bn_stats_impl(const T* x, long P, int C, float* mean, float* invstd, float* running_mean,
                          float* running_var, float momentum, float eps, float* ws, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(x && mean && invstd && ws, nm, "null pointer");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
   const int G = bn_grid(P, C);
-  const int rows = 256 / (C >> 2);
-  hipLaunchKernelGGL(bn_partial_kernel<T>, dim3(G), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, x, ws, P, C);
+  hipLaunchKernelGGL(bn_partial_kernel<T>, dim3(G), dim3(256), bn_stage_bytes(C), s, x, ws, P, C);
   FAMI_CHECK_LAUNCH(nm);
   hipLaunchKernelGGL(bn_finalize_kernel<T>, dim3(C), dim3(256), 0, s, ws, x, G, P, C, mean, invstd, running_mean,
                      running_var, momentum, eps);
@@ -941,14 +881,8 @@ template <typename T>
 static int bn_apply_impl(const T* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                          const T* residual, T* y, long P, int C, int relu, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(x && mean && invstd && gamma && beta && y, nm, "null pointer");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
-  const int rows = 256 / (C >> 2);
-  long g = (P + rows - 1) / rows;
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((int)g), dim3(256), 0, s, x, mean, invstd, gamma, beta, residual, y, P,
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
+  hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(bn_apply_grid(P, C)), dim3(256), 0, s, x, mean, invstd, gamma, beta, residual, y, P,
                      C, relu);
   FAMI_CHECK_LAUNCH(nm);
   return FAMI_OK;
@@ -960,28 +894,18 @@ static int bn_bwd_impl(const T* dy, const T* x, const T* y, const float* mean, c
                        int acc_dx, int acc_param, int acc_dres, float* ws, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(dy && x && mean && invstd && gamma && dx && ws, nm, "null pointer");
   FAMI_REQUIRE(!relu || y, nm, "relu needs y");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
-  if (bn_small_ok(P, C)) {  // low-resolution branches: one launch (see bn_small_bwd_kernel)
-    hipLaunchKernelGGL(bn_small_bwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, dx, dgamma,
-                       dbeta, dres, P, C, relu, acc_dx, acc_param, acc_dres);
-    FAMI_CHECK_LAUNCH(nm);
-    return FAMI_OK;
-  }
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
+  if (bn_small_ok(P, C))  // low-resolution branches: one launch (see bn_small_bwd_kernel)
+    return bn_small_bwd_launch<T>(dy, x, y, mean, invstd, gamma, dx, dgamma, dbeta, dres, P, C, relu, acc_dx, acc_param, acc_dres, s, nm);
   const int G = bn_grid(P, C);
-  const int rows = 256 / (C >> 2);
   float* coef = ws + (long)BN_MAXG * 2 * C - 2 * C;  // tail of the workspace (G < BN_MAXG leaves it free)
   const int Gp = G < BN_MAXG ? G : BN_MAXG - 1;
-  hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(Gp), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, dy, x, y,
-                     mean, invstd, ws, P, C, relu);
+  hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(Gp), dim3(256), bn_stage_bytes(C), s, dy, x, y, mean, invstd, ws, P,
+                     C, relu);
   FAMI_CHECK_LAUNCH(nm);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, ws, Gp, P, C, coef, dgamma, dbeta, acc_param);
   FAMI_CHECK_LAUNCH(nm);
-  long g = (P + rows - 1) / rows;
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((int)g), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, coef, dx,
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(bn_apply_grid(P, C)), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, coef, dx,
                      dres, P, C, relu, acc_dx, acc_dres);
   FAMI_CHECK_LAUNCH(nm);
   return FAMI_OK;
@@ -994,23 +918,17 @@ static int bn_eval_bwd_impl(const T* dy, const T* x, const T* y, const float* me
                             int acc_dx, int acc_param, int acc_dres, float* ws, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(dy && invstd && gamma && dx, nm, "null pointer");
   FAMI_REQUIRE(!relu || y, nm, "relu needs y");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
-  const int rows = 256 / (C >> 2);
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
   if (!dgamma && !dbeta) {  // gamma / beta frozen too: no sums, no workspace, no second launch; x and mean are not read
-    long g = (P + (long)rows * BN_U - 1) / ((long)rows * BN_U);
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL((bn_eval_bwd_kernel<T, false>), dim3((int)g), dim3(256), 0, s, dy, x, y, mean, invstd, gamma,
+    hipLaunchKernelGGL((bn_eval_bwd_kernel<T, false>), dim3(bn_capped_grid(P, C, BN_U, 2048)), dim3(256), 0, s, dy, x, y, mean, invstd, gamma,
                        (float*)nullptr, dx, dres, P, C, relu, acc_dx, acc_dres);
     FAMI_CHECK_LAUNCH(nm);
     return FAMI_OK;
   }
   FAMI_REQUIRE(x && mean && ws, nm, "parameter sums need x, mean and ws");
   const int G = bn_grid(P, C);  // <= BN_MAXG partial rows: the whole of fami_bn_workspace(C)
-  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, true>), dim3(G), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, dy, x, y,
-                     mean, invstd, gamma, ws, dx, dres, P, C, relu, acc_dx, acc_dres);
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, true>), dim3(G), dim3(256), bn_stage_bytes(C), s, dy, x, y, mean, invstd,
+                     gamma, ws, dx, dres, P, C, relu, acc_dx, acc_dres);
   FAMI_CHECK_LAUNCH(nm);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, ws, G, P, C, (float*)nullptr, dgamma, dbeta,
                      acc_param);
@@ -1025,52 +943,30 @@ static int bn_train_fwd_impl(const T* x, const T* residual, T* y, const float* g
                              float* invstd, float* running_mean, float* running_var, long P, int C, int relu,
                              float momentum, float eps, float* ws, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(x && y && gamma && beta && mean && invstd && ws, nm, "null pointer");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
-  if (bn_small_ok(P, C)) {
-    hipLaunchKernelGGL(bn_small_fwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, x, residual, y, gamma, beta, mean, invstd,
-                       running_mean, running_var, P, C, relu, momentum, eps);
-    FAMI_CHECK_LAUNCH(nm);
-    return FAMI_OK;
-  }
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
+  if (bn_small_ok(P, C))
+    return bn_small_fwd_launch<T>(x, residual, y, gamma, beta, mean, invstd, running_mean, running_var, P, C, relu, momentum, eps, s, nm);
   int rc = bn_stats_impl<T>(x, P, C, mean, invstd, running_mean, running_var, momentum, eps, ws, s, nm);
   if (rc != FAMI_OK) return rc;
   return bn_apply_impl<T>(x, mean, invstd, gamma, beta, residual, y, P, C, relu, s, nm);
 }
 
 // two-launch forms: `slots` = fami_bn_slots_bytes(C) bytes, ZERO on entry
-static inline int bn_apply_grid(long P, int C) {
-  const int rows = 256 / (C >> 2);
-  long g = (P + rows - 1) / rows;
-  if (g > 1024) g = 1024;   // every workgroup folds the slot rows in its prologue: fewer, longer workgroups than bn_apply_impl
-  return (int)g;
-}
-
 template <typename T>
 static int bn_train_fwd2_impl(const T* x, const T* residual, T* y, const float* gamma, const float* beta, float* mean,
                               float* invstd, float* running_mean, float* running_var, long P, int C, int relu,
                               float momentum, float eps, void* slots, int pre, hipStream_t s, const char* nm) {
   FAMI_REQUIRE(x && y && gamma && beta && mean && invstd && slots, nm, "null pointer");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
-  if (bn_small_ok(P, C) && !pre) {
-    hipLaunchKernelGGL(bn_small_fwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, x, residual, y, gamma, beta, mean, invstd,
-                       running_mean, running_var, P, C, relu, momentum, eps);
-    FAMI_CHECK_LAUNCH(nm);
-    return FAMI_OK;
-  }
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
+  if (bn_small_ok(P, C) && !pre)
+    return bn_small_fwd_launch<T>(x, residual, y, gamma, beta, mean, invstd, running_mean, running_var, P, C, relu, momentum, eps, s, nm);
   const int G = bn_grid2(P, C, (int)sizeof(T)), NS = bn_slots(C);
-  const int rows = 256 / (C >> 2);
   if (!pre) {   // pre: the producing convolution's epilogue has filled the slot rows and the pivots already
-    hipLaunchKernelGGL(bn_partial2_kernel<T>, dim3(G), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, x,
-                       reinterpret_cast<double*>(slots), NS, P, C);
+    hipLaunchKernelGGL(bn_partial2_kernel<T>, dim3(G), dim3(256), bn_stage_bytes(C), s, x, reinterpret_cast<double*>(slots), NS,
+                       P, C);
     FAMI_CHECK_LAUNCH(nm);
   }
-  hipLaunchKernelGGL(bn_apply2_kernel<T>, dim3(bn_apply_grid(P, C)), dim3(256), (size_t)2 * C * sizeof(float), s, x,
+  hipLaunchKernelGGL(bn_apply2_kernel<T>, dim3(bn_apply_grid2(P, C)), dim3(256), (size_t)2 * C * sizeof(float), s, x,
                      reinterpret_cast<const double*>(slots), NS, gamma, beta, residual, y, mean, invstd, running_mean,
                      running_var, P, C, relu, momentum, eps, pre ? bn_slots_pivot(slots, C) : (const float*)nullptr);
   FAMI_CHECK_LAUNCH(nm);
@@ -1084,25 +980,18 @@ static int bn_bwd2_impl(const T* dy, const T* x, const T* y, const float* mean, 
   FAMI_REQUIRE(dy && x && mean && invstd && gamma && beta && dx && slots, nm, "null pointer");
   FAMI_REQUIRE(relu != 1 || y, nm, "relu = 1 needs y");
   FAMI_REQUIRE(relu >= 0 && relu <= 2, nm, "relu must be 0, 1 (mask from y) or 2 (mask recomputed from x)");
-  if (!bn_shape_ok(P, C)) {
-    fami_set_error(nm, "C must be a multiple of 4, <= 1024");
-    return FAMI_ESHAPE;
-  }
+  if (const int rc = bn_check_shape(P, C, nm)) return rc;
   if (bn_small_ok(P, C) && !pre) {  // the one-launch kernel takes its mask from y
     FAMI_REQUIRE(relu != 2 || y, nm, "small tensors take the ReLU mask from y");
-    hipLaunchKernelGGL(bn_small_bwd_kernel<T>, dim3(C / 4), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, dx, dgamma,
-                       dbeta, dres, P, C, relu ? 1 : 0, acc_dx, acc_param, acc_dres);
-    FAMI_CHECK_LAUNCH(nm);
-    return FAMI_OK;
+    return bn_small_bwd_launch<T>(dy, x, y, mean, invstd, gamma, dx, dgamma, dbeta, dres, P, C, relu ? 1 : 0, acc_dx, acc_param, acc_dres, s, nm);
   }
   const int G = bn_grid2(P, C, (int)sizeof(T)), NS = bn_slots(C);
-  const int rows = 256 / (C >> 2);
   if (!pre) {   // pre: the input-gradient convolution that produced dy summed dz and dz*xhat in its epilogue
-    hipLaunchKernelGGL(bn_bwd_partial2_kernel<T>, dim3(G), dim3(256), (size_t)rows * 2 * C * sizeof(float), s, dy, x, y, mean,
-                       invstd, gamma, beta, reinterpret_cast<double*>(slots), NS, P, C, relu);
+    hipLaunchKernelGGL(bn_bwd_partial2_kernel<T>, dim3(G), dim3(256), bn_stage_bytes(C), s, dy, x, y, mean, invstd, gamma, beta,
+                       reinterpret_cast<double*>(slots), NS, P, C, relu);
     FAMI_CHECK_LAUNCH(nm);
   }
-  hipLaunchKernelGGL(bn_bwd_apply2_kernel<T>, dim3(bn_apply_grid(P, C)), dim3(256), (size_t)2 * C * sizeof(float), s, dy, x,
+  hipLaunchKernelGGL(bn_bwd_apply2_kernel<T>, dim3(bn_apply_grid2(P, C)), dim3(256), (size_t)2 * C * sizeof(float), s, dy, x,
                      y, mean, invstd, gamma, beta, reinterpret_cast<const double*>(slots), NS, dx, dgamma, dbeta, dres, P,
                      C, relu, acc_dx, acc_param, acc_dres);
   FAMI_CHECK_LAUNCH(nm);
@@ -1116,7 +1005,7 @@ static int channel_sum_impl(const T* x, long P, int C, float* out, int accumulat
   FAMI_REQUIRE(C <= 4096, nm, "C > 4096 unsupported");
   int rows = C > 256 ? 1 : 256 / C;
   const bool vec4 = C % 4 == 0 && C <= 1024 && P >= 4096;
-  if (vec4) rows = 256 / (C >> 2);
+  if (vec4) rows = bn_rows(C);
   long g = (P + rows - 1) / rows;
   if (vec4) g = (g + 2 * BN_U - 1) / (2 * BN_U);          // at least 2 BN_U row steps per workgroup
   if (g > BN_MAXG) g = BN_MAXG;
