@@ -1774,11 +1774,7 @@ static DcnWinPlan dcn_win_plan(int B, int Ho, int Wo, int C, int G, int kh, int 
 
 template <typename T, int NT, bool ABL, int KSPLIT>
 static void dcn_fwd_win_launch1(const DcnWinArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dcn_fwd_win_kernel<T, NT, ABL, KSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    attr_set = true;
-  }
+  fami_lds_limit<dcn_fwd_win_kernel<T, NT, ABL, KSPLIT>>(156 * 1024);
   hipLaunchKernelGGL((dcn_fwd_win_kernel<T, NT, ABL, KSPLIT>), grid, dim3(512 * KSPLIT), lds, s, a);
 }
 // [fami_route_t] g_dcn_ksplit (default 1)  // fami_dcn_tune(256 + k): 2 = the 16-wave K-split build (measured slower: 35.5 vs 29.8 us)
@@ -1794,21 +1790,13 @@ static void dcn_fwd_win_launch(const DcnWinArgs<T>& a, dim3 grid, size_t lds, hi
 
 template <typename T, int NT, int PF, int MINW>
 static void dcn_fwd_direct_launch(const DcnArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dcn_fwd_direct_kernel<T, NT, PF, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr_set = true;
-  }
+  fami_lds_limit<dcn_fwd_direct_kernel<T, NT, PF, MINW>>(150 * 1024);
   hipLaunchKernelGGL((dcn_fwd_direct_kernel<T, NT, PF, MINW>), grid, dim3(256), lds, s, a);
 }
 
 template <typename T, int NT>
 static void dcn_fwd_launch(const DcnArgs<T>& a, dim3 grid, size_t lds, size_t lds_direct, bool direct, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dcn_fwd_kernel<T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr_set = true;
-  }
+  fami_lds_limit<dcn_fwd_kernel<T, NT>>(150 * 1024);
   if (!direct) {
     hipLaunchKernelGGL((dcn_fwd_kernel<T, NT>), grid, dim3(256), lds, s, a);
     return;
@@ -1955,11 +1943,7 @@ static inline long dcn_bwd2_image_elems(const DcnBwd2Plan& q, int esz) {
 template <typename T, int NCO, bool STG>
 static void dcn_bwd2_launch1(const DcnBwd2Args<T>& a, dim3 grid, size_t lds, hipStream_t s) {
   constexpr bool F32 = sizeof(T) == 2;       // 16-bit storage: 32-bit fixed-point region
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dcn_bwd2_kernel<T, NCO, F32, STG>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    attr_set = true;
-  }
+  fami_lds_limit<dcn_bwd2_kernel<T, NCO, F32, STG>>(64 * 1024);
   hipLaunchKernelGGL((dcn_bwd2_kernel<T, NCO, F32, STG>), grid, dim3(256), lds, s, a);
 }
 template <typename T, int NCO>
@@ -1977,11 +1961,7 @@ static int dcn_bwd_chunk_groups(int G, int cg, int K) {
 
 template <typename T, int KSO, int MODE>
 static void dcn_bwd_launch1(const DcnBwdArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dcn_bwd_kernel<T, KSO, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr_set = true;
-  }
+  fami_lds_limit<dcn_bwd_kernel<T, KSO, MODE>>(150 * 1024);
   hipLaunchKernelGGL((dcn_bwd_kernel<T, KSO, MODE>), grid, dim3(256), lds, s, a);
 }
 template <typename T, int KSO>

@@ -103,6 +103,16 @@ template <> struct H16<f16_t> {
 
 static inline int fami_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Allows `Kernel` dynamic LDS beyond the 64 KiB default, once per process: call before launching it with more.
+template <auto Kernel>
+static inline void fami_lds_limit(int bytes) {
+  static bool done = false;
+  if (!done) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = true;
+  }
+}
+
 // grid for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8.
 static inline int fami_ew_grid(long n, int block = 256) {
   long g = (n + block - 1) / block;

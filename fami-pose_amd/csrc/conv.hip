@@ -24,10 +24,17 @@
 #include <string.h>
 
 #include "conv_epi.h"
-extern "C" int fami_conv2d_fwd_bnin_ok(int N, int H, int W, int Ci, int Co);      // conv_t6.hip
-// conv_pair.hip
 #include "conv_pair.h"
-int fami_pair_launch(const PairCapture& c, hipStream_t s);
+// defined in other translation units
+extern "C" int fami_conv2d_fwd_bnin_ok(int N, int H, int W, int Ci, int Co);      // conv_t6.hip
+extern "C" int fami_dcn_tune(int mode);          // align.hip
+extern "C" int fami_bn_tune_small(long elems);   // norm.hip
+extern "C" void fami_conv_stem_tune(int on);     // conv_stem.hip
+int fami_pair_launch(const PairCapture& c, hipStream_t s);      // conv_pair.hip
+// conv_stem.hip: the stem's 3 -> 64 stride-2 convolution with K dense over (tap, channel)
+int fami_try_conv_stem1(int half_kind, const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
+                        int kh, int kw, int stride, int pad, int dil, int NTt, int relu, int accumulate, int out_f32, hipStream_t s,
+                        const char* name, const EpiBN& epi);
 
 
 struct ConvArgs {
@@ -2343,6 +2350,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_lds_f32_kernel(WgradLdsArgsF p
 }
 
 // ------------------------------------------------------------------ host side
+// ---- helpers and plans
 static int pick_nt(int tiles) {
   const int cand[5] = {6, 4, 3, 2, 1};
   int best = 1;
@@ -2371,6 +2379,51 @@ static int pick_small(int tiles) {  // wgrad tile counts in {4,3,2,1}
     }
   }
   return best;
+}
+
+// storage-kind code of the kernels behind fami_try_* (conv_epi.h): 0 bf16, 1 fp16, 2 f32
+template <typename T>
+constexpr int storage_kind() { return std::is_same<T, float>::value ? 2 : (std::is_same<T, f16_t>::value ? 1 : 0); }
+
+static bool wgrad_lin_ok(int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
+  return stride == 1 && 2 * pad == dil * (kh - 1) && 2 * pad == dil * (kw - 1) && kh * kw > 1 && kh * kw <= 9 && W >= 4 &&
+         Ci % 16 == 0 && Co % 16 == 0;
+}
+static bool geom_ok(int kh, int kw, int stride, int pad, int dil) {
+  return kh >= 1 && kw >= 1 && kh <= 7 && kw <= 7 && (stride == 1 || stride == 2) && pad >= 0 && dil >= 1;
+}
+static inline int out_dim(int i, int k, int stride, int pad, int dil) {
+  return (i + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+}
+// The argument check every convolution entry point opens with (forward, input gradient, weight gradient): `ptrs` = all
+// required tensors are set; [N,H,W,Ci] is the convolution's input, Co its output channels.
+static int conv_args_check(const char* nm, bool ptrs, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad,
+                           int dil) {
+  FAMI_REQUIRE(ptrs && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
+  if (!geom_ok(kh, kw, stride, pad, dil)) {
+    fami_set_error(nm, "unsupported geometry");
+    return FAMI_ESHAPE;
+  }
+  return FAMI_OK;
+}
+// The geometry fields of ConvArgs / ConvArgsH (the same names in both) for the convolution [N,H,W,Ci] -> Co channels, after
+// conv_args_check.  mode is the kernels' MODE: 0 forward (the GEMM reads x), 1 input gradient (the GEMM reads dy: maps and
+// channel counts change places).  esize = bytes per activation element, kchunk = channels per K chunk of the packed weight
+// image (16 f32 | 32 16-bit).
+template <typename Args>
+static int conv_geometry(Args& a, const char* nm, int mode, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride,
+                         int pad, int dil, int esize, int kchunk) {
+  const int Hc = out_dim(H, kh, stride, pad, dil), Wc = out_dim(W, kw, stride, pad, dil);
+  a.N = N;
+  a.Hi = mode ? Hc : H; a.Wi = mode ? Wc : W; a.Ci = mode ? Co : Ci;
+  a.Ho = mode ? H : Hc; a.Wo = mode ? W : Wc; a.Co = mode ? Ci : Co;
+  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
+  a.KC = fami_cdiv(a.Ci, kchunk); a.NTt = fami_cdiv(a.Co, 16);
+  const long P = (long)N * a.Ho * a.Wo;
+  const long xb = (long)N * a.Hi * a.Wi * a.Ci * esize, wb = (long)kh * kw * a.KC * a.NTt * 1024;
+  FAMI_REQUIRE(P > 0 && P < (1L << 31) && xb < (1L << 31) && wb < (1L << 31), nm, "tensor >= 2 GiB");
+  a.P = (int)P; a.x_bytes = (unsigned)xb; a.wp_bytes = (unsigned)wb;
+  return FAMI_OK;
 }
 
 // A weight-gradient call made through fami_conv2d_wgrad_defer_* records its reduce here instead of launching it
@@ -2412,12 +2465,156 @@ static void launch_reduce_plain(const float* part, float* dw, int Co, int Ci, in
   }
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(fami_cdiv(n, 64)), dim3(256), 0, s, part, dw, n, psplit, accumulate);
 }
+// Runs a weight-gradient call with its slab reduce recorded instead of launched and copies the record to desc_out (not null).
+// g_defer is cleared whatever the call returns.
+template <typename Call>
+static int with_deferred_reduce(const char* nm, long* desc_out, Call&& wgrad) {
+  ReduceDesc d;
+  d.part = nullptr;
+  g_defer = &d;
+  const int rc = wgrad();
+  g_defer = nullptr;
+  if (rc != FAMI_OK) return rc;
+  FAMI_REQUIRE(d.part, nm, "no reduce recorded");
+  memcpy(desc_out, &d, sizeof(d));
+  return FAMI_OK;
+}
+// conv_pair.h: input gradient, then deferred weight gradient, with their launches recorded; then the combined launch (or the
+// recorded halves as single kernels).  The capture is gone whatever the two calls return.
+template <typename Dgrad, typename Wgrad>
+static int bwd_pair_run(const char* nm, long* desc_out, hipStream_t s, Dgrad&& dgrad, Wgrad&& wgrad) {
+  PairCapture pc;
+  pc.a.kind = pc.b.kind = 0;
+  fami_pair_capture() = &pc;
+  int rc = dgrad();
+  if (rc == FAMI_OK) rc = with_deferred_reduce(nm, desc_out, wgrad);
+  fami_pair_capture() = nullptr;
+  if (rc != FAMI_OK) return rc;
+  const int pr = fami_pair_launch(pc, s);
+  FAMI_REQUIRE(pr >= 0, nm, "a recorded launch has no kernel instance");
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
 
+// The three weight-gradient plans below look alike and carry different measured constants: they stay apart.
+// [fami_route_t] g_wgrad_nsub (default 2)  // sub-chunks per workgroup of the 16-bit LDS wgrad (fewer, larger partial slabs): 2 = half the slab
+                             // traffic and reduce pass, bf16 step 34.6 -> 33.3 ms in both A/B orders; 3 and 4 equal to 2
+// [fami_route_t] g_wgrad_ps (default 0)  // fami_conv_tune_wgrad_lds(1000 + n): pixel-split target of the per-tap f32 wgrad (benchmarks)
+// [fami_route_t] g_wgrad_mt (default 0)  // fami_conv_tune_wgrad_lds(100 + mt): cap on input-channel tiles per f32 wgrad workgroup
+struct WgradPlan { int MT, NT, ciBlocks, coBlocks, psplit, chunk, pertap, w8; long P; };
+static WgradPlan wgrad_plan(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int w8 = 0) {
+  WgradPlan q;
+  const int Ho = out_dim(H, kh, stride, pad, dil), Wo = out_dim(W, kw, stride, pad, dil);
+  q.P = (long)N * Ho * Wo;
+  q.MT = pick_small(fami_cdiv(Ci, 16));
+  q.NT = pick_small(fami_cdiv(Co, 16));
+  if (g_wgrad_mt > 0 && g_wgrad_mt <= q.MT) q.MT = g_wgrad_mt;  // benchmarks: fewer input-channel tiles per workgroup
+  q.ciBlocks = fami_cdiv(fami_cdiv(Ci, 16), q.MT);
+  q.coBlocks = fami_cdiv(fami_cdiv(Co, 16), q.NT);
+  q.pertap = (kh * kw > 1 && kh * kw <= 9) ? 1 : 0;   // one wave per tap (3x3): workgroups of kh*kw waves
+  const long by = q.pertap ? (long)q.ciBlocks * q.coBlocks : (long)kh * kw * q.ciBlocks * q.coBlocks;
+  long ps = ((q.pertap ? (g_wgrad_ps ? g_wgrad_ps : 512) : 1024) + by - 1) / by;
+  q.w8 = 0;
+  // w8 = 3: 16-wave workgroups while a column of the grid still has >= 16 of them (48 / 96 / 192 channels: 66.9 vs 69.2,
+  // 64.3 vs 67.7, 67.1 vs 70.2 us, and half the slabs), 8-wave ones beyond (384 channels, 7 per column: 120 vs 78 us)
+  if (w8 == 3) w8 = 256 / by >= 16 ? 2 : 1;
+  if (w8 && q.pertap && kh * kw == 9 && ps >= 9) {
+    // 8-/16-wave workgroups: c slabs need c + ceil(c/8) workgroups.  Never more workgroups than the target (one
+    // workgroup beyond the resident set costs a whole extra round: 192 channels, 9 columns x 57 = 513 workgroups ran
+    // 90 us against 80 us for 9 x 43)
+    q.w8 = w8;
+    const long T = (g_wgrad_ps ? g_wgrad_ps : (w8 == 2 ? 256 : 512)) / by;
+    ps = T * 8 / 9;
+    while (ps > 1 && ps + (ps + 7) / 8 > T) --ps;
+    if (ps < 1) ps = 1;
+    if (w8 == 2) ps *= 2;   // pixel chunks: two per slab
+  }
+  const long maxps = q.pertap ? (q.P + 63) / 64 : (q.P + 255) / 256;
+  if (ps > maxps) ps = maxps;
+  if (ps < 1) ps = 1;
+  long chunk = (q.P + ps - 1) / ps;
+  chunk = ((chunk + 15) / 16) * 16;
+  ps = (q.P + chunk - 1) / chunk;
+  if (q.w8 == 2) ps = (ps + 1) / 2;   // slabs
+  q.psplit = (int)ps;
+  q.chunk = (int)chunk;
+  return q;
+}
+
+// bf16 transposing-LDS wgrad plan (3x3 stride-1 pad-1): pixel groups G, chunk pixels, channel blocks
+struct WgradLdsPlan { int ok, CIT, COT, ciBlocks, coBlocks, G, chunk, nsub; size_t lds; int xrow, yrow, xbytes; };
+static WgradLdsPlan wgrad_lds_plan(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
+  WgradLdsPlan q;
+  q.ok = 0;
+  if (!(kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) || (Ci % 16) || (Co % 16) || W > 160) return q;
+  q.CIT = Ci % 48 == 0 ? 3 : (Ci % 32 == 0 ? 2 : 1);
+  q.COT = Co % 48 == 0 ? 3 : (Co % 32 == 0 ? 2 : 1);
+  q.ciBlocks = Ci / (16 * q.CIT);
+  q.coBlocks = Co / (16 * q.COT);
+  const long P = (long)N * H * W;
+  const long blocks = (long)q.ciBlocks * q.coBlocks;
+  long G = (512 + blocks - 1) / blocks;
+  long chunk = (P + G - 1) / G;
+  chunk = ((chunk + 31) / 32) * 32;
+  if (chunk < 32) chunk = 32;
+  if (chunk > 320) chunk = 320;
+  q.nsub = g_wgrad_nsub;
+  G = (P + chunk * q.nsub - 1) / (chunk * q.nsub);
+  q.G = (int)G;
+  q.chunk = (int)chunk;
+  // LDS rows are unpadded: the 4 pixel rows a 16-lane group hands to one transposing read are 32/64/96 bytes apart
+  // (distinct bank groups); padding would only separate the kq groups and costs the second resident workgroup
+  q.xrow = 32 * q.CIT;
+  q.yrow = 32 * q.COT;
+  q.xbytes = (q.chunk + 2 * (W + 1)) * q.xrow;
+  q.lds = (size_t)q.xbytes + (size_t)q.chunk * q.yrow + 32;
+  q.ok = q.lds <= 150 * 1024 && P < (1L << 31) && G < 65536;
+  return q;
+}
+
+// f32 LDS wgrad plan (3x3 stride-1 pad-1): one 8-wave workgroup per CU (the tile takes most of the 160 KB), about two
+// workgroups per CU in total so the partial-slab traffic stays at ~512 slabs
+static int lds_row_floats(int cb) {  // row stride with (stride mod 64) in {16, 48}: conflict-free 4-row reads
+  const int m = cb % 64;
+  return (m == 16 || m == 48) ? cb : cb + 16;  // cb is a multiple of 16: m in {0, 32} -> +16
+}
+static WgradLdsPlan wgrad_lds_plan_f32(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
+  WgradLdsPlan q;
+  q.ok = 0;
+  if (!(kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) || (Ci % 16) || (Co % 16) || W < 4) return q;
+  q.CIT = Ci % 48 == 0 ? 3 : (Ci % 64 == 0 ? 4 : (Ci % 32 == 0 ? 2 : 1));
+  q.COT = Co % 48 == 0 ? 3 : (Co % 64 == 0 ? 4 : (Co % 32 == 0 ? 2 : 1));
+  q.ciBlocks = Ci / (16 * q.CIT);
+  q.coBlocks = Co / (16 * q.COT);
+  q.nsub = 1;
+  q.xrow = lds_row_floats(16 * q.CIT);
+  q.yrow = lds_row_floats(16 * q.COT);
+  const long P = (long)N * H * W;
+  const long blocks = (long)q.ciBlocks * q.coBlocks;
+  const long budget = 156 * 1024 / 4 - 16 - 2L * (W + 1) * q.xrow;  // floats left for the chunk rows
+  if (budget < 8L * (q.xrow + q.yrow)) return q;
+  long cmax = budget / (q.xrow + q.yrow);
+  cmax -= cmax % 8;
+  long G = (512 + blocks - 1) / blocks;
+  long chunk = (P + G - 1) / G;
+  chunk = ((chunk + 7) / 8) * 8;
+  if (chunk > cmax) chunk = cmax;
+  G = (P + chunk - 1) / chunk;
+  q.G = (int)G;
+  q.chunk = (int)chunk;
+  q.xbytes = (int)((chunk + 2 * (W + 1)) * q.xrow);  // floats
+  q.lds = ((size_t)q.xbytes + (size_t)chunk * q.yrow + 16) * 4;
+  q.ok = P < (1L << 31) && G < 65536;
+  return q;
+}
+
+// ---- implementations
 // [fami_route_t] g_prio (default 0)  // fami_conv_tune_stages(120 / 121): s_setprio in the f32 MFMA kernels off / on
 // [fami_route_t] g_lin_conv (default 1)  // fami_conv_tune_stages(100 / 101): linear-address form of the f32 implicit GEMM off / on
 // [fami_route_t] g_par (default 1)  // fami_conv_tune_stages(110 / 111): parity-class stride-2 input gradient off / on
 // pixel tiles of MT*16 pixels: all of them, or (stride-2 dgrad by parity class) the sum over the four classes
-static long igemm_tiles(const ConvArgs& a, int MT) {
+template <typename Args>
+static long igemm_tiles(const Args& a, int MT) {
   if (!a.par) return fami_cdiv(a.P, MT * 16);
   long t = 0;
   for (int c = 0; c < 4; ++c) {
@@ -2469,6 +2666,7 @@ static int launch_igemm(const ConvArgs& a, int MT, int NT, int KS, int ST, hipSt
 // [fami_route_t] g_xcd (default -1)  // fami_conv_tune_xcd: 0 natural tile order, 1 XCD-contiguous, -1 default (= 1: PMC FETCH_SIZE of the
                         // 48->48 3x3 @96x72 N=20 launch drops from 46.6 MB to 13.7 MB, time -1..-2 %; tools/bench_xcd.py)
 
+// (tile heuristics: run_igemm32, run_igemm and run_igemm_h look alike and carry different measured constants: they stay apart)
 static int run_igemm32(ConvArgs a, int mode, hipStream_t s, const char* name) {
   a.xcd = g_xcd < 0 ? 1 : g_xcd;
   a.prio = g_prio;
@@ -2558,13 +2756,6 @@ static int run_igemm(ConvArgs a, int mode, hipStream_t s, const char* name) {
 // Default (-1): bf16 staged, f32 direct.  fami_conv_tune_lds(0/1) forces one path for both (tests exercise both).
 // [fami_route_t] g_use_lds (default -1)
 // [fami_route_t] g_lds_sim (default 0)  // fami_conv_tune_lds(2): LDS kernel in its split-operand cost-simulation form (benchmarks)
-// [fami_route_t] g_wgrad_nsub (default 2)  // sub-chunks per workgroup of the 16-bit LDS wgrad (fewer, larger partial slabs): 2 = half the slab
-                             // traffic and reduce pass, bf16 step 34.6 -> 33.3 ms in both A/B orders; 3 and 4 equal to 2
-// [fami_route_t] g_wgrad_ps (default 0)  // fami_conv_tune_wgrad_lds(1000 + n): pixel-split target of the per-tap f32 wgrad (benchmarks)
-// [fami_route_t] g_wgrad_mt (default 0)  // fami_conv_tune_wgrad_lds(100 + mt): cap on input-channel tiles per f32 wgrad workgroup
-// [fami_route_t] g_wgrad_lds (default 1)  // fami_conv_tune_wgrad_lds(0): bf16 weight gradients on the scalar-operand kernels
-// [fami_route_t] g_wgrad_lds_f32 (default 2)  // f32 LDS weight gradient: 0 never, 1 whenever eligible, 2 only where it measured faster
-// [fami_route_t] g_wgrad_lin (default 1)  // fami_conv_tune_wgrad_lds(50 / 51): linear-address per-tap f32 kernel off / on
 
 // LDS-staged path: plan + launch.  Returns 1 if launched, 0 if the shape is not eligible, <0 on error.
 template <typename T>
@@ -2574,7 +2765,7 @@ static int try_conv3x3_lds(const void* x, const void* wp, const float* bias, voi
   constexpr int SZ = (int)sizeof(T), KSTEP = LdsTraits<T>::KSTEP;
   if (g_use_lds != 0) {   // fami_conv_tune_lds(0) still forces the direct kernels
     // register-blocked LDS kernel (conv_t4.hip): every storage type since round 3
-    const int rc = fami_try_conv3x3_t4(std::is_same<T, float>::value ? 2 : (std::is_same<T, f16_t>::value ? 1 : 0), x, wp, bias, y,
+    const int rc = fami_try_conv3x3_t4(storage_kind<T>(), x, wp, bias, y,
                                        N, H, W, Ci, Co, KC, NTt, sgn, relu, accumulate, out_f32, s, name, epi, xbn);
     if (rc != 0) return rc;
   }
@@ -2616,17 +2807,9 @@ static int try_conv3x3_lds(const void* x, const void* wp, const float* bias, voi
   bool launched = false;
 #define FAMI_LDS_CASE(nt, ksc)                                                                                     \
   if (NT == nt && KSC == ksc) {                                                                                    \
-    static bool attr = false;                                                                                      \
-    if (!attr) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<T, nt, ksc>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); \
-      attr = true;                                                                                                 \
-    }                                                                                                              \
+    fami_lds_limit<conv3x3_lds_kernel<T, nt, ksc>>(156 * 1024);                                                    \
     if (g_lds_sim && SZ == 2) {                                                                                    \
-      static bool attr2 = false;                                                                                   \
-      if (!attr2) {                                                                                                \
-        (void)hipFuncSetAttribute((const void*)conv3x3_lds_kernel<T, nt, ksc, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); \
-        attr2 = true;                                                                                              \
-      }                                                                                                            \
+      fami_lds_limit<conv3x3_lds_kernel<T, nt, ksc, 1>>(156 * 1024);                                               \
       hipLaunchKernelGGL((conv3x3_lds_kernel<T, nt, ksc, 1>), grid, dim3(256), lds, s, a);                         \
     } else                                                                                                         \
     hipLaunchKernelGGL((conv3x3_lds_kernel<T, nt, ksc>), grid, dim3(256), lds, s, a);                              \
@@ -2644,20 +2827,473 @@ static int try_conv3x3_lds(const void* x, const void* wp, const float* bias, voi
   return 1;
 }
 
-static bool wgrad_lin_ok(int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
-  return stride == 1 && 2 * pad == dil * (kh - 1) && 2 * pad == dil * (kw - 1) && kh * kw > 1 && kh * kw <= 9 && W >= 4 &&
-         Ci % 16 == 0 && Co % 16 == 0;
-}
-static bool geom_ok(int kh, int kw, int stride, int pad, int dil) {
-  return kh >= 1 && kw >= 1 && kh <= 7 && kw <= 7 && (stride == 1 || stride == 2) && pad >= 0 && dil >= 1;
-}
-static inline int out_dim(int i, int k, int stride, int pad, int dil) {
-  return (i + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+// y[N,Ho,Wo,Co] = conv(x[N,H,W,Ci], W) (+bias) (+addend) (relu) ; wp packed with mode 0
+// (conv_fwd_h_impl is the 16-bit form: no addend, an out_f32 switch, two more refusals, other routes -- folding the two needs flags)
+static int conv_fwd_f32_impl(const char* nm, const float* x, const float* wp, const float* bias, const float* addend,
+                             float* y, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil,
+                             int relu, int accumulate, const EpiBN& e, hipStream_t s, const XBN& xbn = xbn_none()) {
+  if (const int rc = conv_args_check(nm, x && wp && y, N, H, W, Ci, Co, kh, kw, stride, pad, dil)) return rc;
+  ConvArgs a;
+  a.e = e; a.emode = e.slots ? e.mode : 0;
+  a.x = x; a.wp = wp; a.y = y; a.bias = bias; a.addend = addend; a.relu = relu; a.accumulate = accumulate;
+  if (const int rc = conv_geometry(a, nm, 0, N, H, W, Ci, Co, kh, kw, stride, pad, dil, 4, 16)) return rc;
+  if (Ci == 3 && !addend && !xbn.on) {
+    const int rc = fami_try_conv_stem1(storage_kind<float>(), x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil, a.NTt, relu, accumulate, 1, s, nm, e);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !addend) {
+    const int rc = try_conv3x3_lds<float>(x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, 1, s, nm, e, xbn);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !addend && !e.slots && !xbn.on && g_use_lds != 0) {
+    const int rc = fami_try_conv3x3_t4_dil(storage_kind<float>(), x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, 1, dil, s, nm);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (xbn.on) {
+    fami_set_error(nm, "input BatchNorm needs the split-product 3x3 kernel (ask fami_conv2d_xbn_ok_f32 first)");
+    return FAMI_ESHAPE;
+  }
+  return run_igemm(a, 0, s, nm);
 }
 
+// dx[N,H,W,Ci] = conv^T(dy[N,Ho,Wo,Co], W) (+addend) ; wp packed with mode 1
+// (conv_dgrad_h_impl is the 16-bit form: no addend, one more refusal, other routes -- folding the two needs flags)
+static int conv_dgrad_f32_impl(const char* nm, const float* dy, const float* wp, const float* addend, float* dx, int N,
+                               int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
+                               const EpiBN& e, hipStream_t s) {
+  if (const int rc = conv_args_check(nm, dy && wp && dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil)) return rc;
+  ConvArgs a;
+  a.e = e; a.emode = e.slots ? e.mode : 0;
+  a.x = dy; a.wp = wp; a.y = dx; a.bias = nullptr; a.addend = addend; a.relu = 0; a.accumulate = accumulate;
+  if (const int rc = conv_geometry(a, nm, 1, N, H, W, Ci, Co, kh, kw, stride, pad, dil, 4, 16)) return rc;
+  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !addend) {
+    // dgrad of a stride-1 "same" conv is the same conv on dy with the taps mirrored: GEMM K = Co, N = Ci
+    const int rc = try_conv3x3_lds<float>(dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 1, s, nm, e);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !addend && !e.slots && g_use_lds != 0) {
+    const int rc = fami_try_conv3x3_t4_dil(storage_kind<float>(), dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 1, dil, s, nm);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  return run_igemm(a, 1, s, nm);
+}
+
+// [fami_route_t] g_wgrad_lds (default 1)  // fami_conv_tune_wgrad_lds(0): bf16 weight gradients on the scalar-operand kernels
+// [fami_route_t] g_wgrad_lds_f32 (default 2)  // f32 LDS weight gradient: 0 never, 1 whenever eligible, 2 only where it measured faster
+// [fami_route_t] g_wgrad_lin (default 1)  // fami_conv_tune_wgrad_lds(50 / 51): linear-address per-tap f32 kernel off / on
+// dw[Co,Ci,kh,kw] fp32 (=|+=) sum_pixels x (*) dy ; workspace from fami_conv2d_wgrad_workspace
+template <typename T>
+static int wgrad_impl(const T* x, const T* dy, float* dw, float* workspace, long ws_bytes, int N, int H, int W, int Ci,
+                      int Co, int kh, int kw, int stride, int pad, int dil, int accumulate, hipStream_t s,
+                      const char* nm) {
+  if (const int rc = conv_args_check(nm, x && dy && dw && workspace, N, H, W, Ci, Co, kh, kw, stride, pad, dil)) return rc;
+  // stride-1 same-size convolutions of whole 16-channel tiles: linear-address kernel (f32 storage only)
+  const bool lin = std::is_same<T, float>::value && g_wgrad_lin && wgrad_lin_ok(H, W, Ci, Co, kh, kw, stride, pad, dil);
+  const WgradPlan q = wgrad_plan(N, H, W, Ci, Co, kh, kw, stride, pad, dil, !lin ? 0 : (g_wgrad_lin == 1 ? 3 : (g_wgrad_lin == 3 ? 1 : (g_wgrad_lin == 4 ? 2 : 0))));
+  const long need = (long)q.psplit * Co * Ci * kh * kw * (long)sizeof(float);
+  FAMI_REQUIRE(ws_bytes >= need, nm, "workspace too small");
+  FAMI_REQUIRE(q.P < (1L << 31), nm, "size out of range");
+  WgradArgs<T> a;
+  a.x = x; a.dy = dy; a.part = workspace;
+  a.N = N; a.H = H; a.W = W; a.Ci = Ci;
+  a.Ho = out_dim(H, kh, stride, pad, dil); a.Wo = out_dim(W, kw, stride, pad, dil); a.Co = Co;
+  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
+  a.P = (int)q.P; a.chunk = q.chunk; a.ciBlocks = q.ciBlocks; a.coBlocks = q.coBlocks; a.xcd = g_xcd_w; a.prio = g_prio;
+  const long xb = (long)N * H * W * Ci * (long)sizeof(T), yb = q.P * Co * (long)sizeof(T);
+  FAMI_REQUIRE(xb < (1L << 31) && yb < (1L << 31), nm, "tensor >= 2 GiB");
+  a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)yb;
+  if (q.pertap) {
+    const dim3 grid(q.w8 ? q.psplit + (q.psplit + 7) / 8 : q.psplit, q.ciBlocks * q.coBlocks), block(q.w8 ? 512 * q.w8 : kh * kw * 64);
+    const size_t lin_lds = q.w8 == 2 ? (size_t)8 * q.MT * q.NT * 1024 : 0;
+    a.psplit = q.psplit; a.w8 = q.w8;
+    bool ok = false;
+#define FAMI_TCASE(mt, nt)                                                                  \
+  if (q.MT == mt && q.NT == nt) {                                                           \
+    if constexpr (std::is_same<T, float>::value) {                                          \
+      if (lin) {                                                                            \
+        fami_lds_limit<conv_wgrad_taps_lin_f32<T, mt, nt>>(8 * mt * nt * 1024);             \
+        hipLaunchKernelGGL((conv_wgrad_taps_lin_f32<T, mt, nt>), grid, block, lin_lds, s, a); \
+      }                                                                                     \
+      else hipLaunchKernelGGL((conv_wgrad_taps_f32<T, mt, nt>), grid, block, 0, s, a);      \
+    } else {                                                                                \
+      hipLaunchKernelGGL((conv_wgrad_taps_f32<T, mt, nt>), grid, block, 0, s, a);           \
+    }                                                                                       \
+    ok = true;                                                                              \
+  }
+    FAMI_TCASE(1, 1) FAMI_TCASE(1, 2) FAMI_TCASE(1, 3) FAMI_TCASE(1, 4)
+    FAMI_TCASE(2, 1) FAMI_TCASE(2, 2) FAMI_TCASE(2, 3) FAMI_TCASE(2, 4)
+    FAMI_TCASE(3, 1) FAMI_TCASE(3, 2) FAMI_TCASE(3, 3) FAMI_TCASE(3, 4)
+    FAMI_TCASE(4, 1) FAMI_TCASE(4, 2) FAMI_TCASE(4, 3) FAMI_TCASE(4, 4)
+#undef FAMI_TCASE
+    if (!ok) {
+      fami_set_error(nm, "no kernel instance");
+      return FAMI_ESHAPE;
+    }
+    FAMI_CHECK_LAUNCH(nm);
+    launch_reduce_taps(workspace, dw, Co, Ci, kh * kw, q.psplit, accumulate, s);
+    FAMI_CHECK_LAUNCH(nm);
+    return FAMI_OK;
+  }
+  const dim3 grid(q.psplit, kh * kw * q.ciBlocks * q.coBlocks);
+  bool done = false;
+#define FAMI_WCASE(mt, nt)                                                                  \
+  if (q.MT == mt && q.NT == nt) {                                                           \
+    hipLaunchKernelGGL((conv_wgrad_f32<T, mt, nt>), grid, dim3(256), 0, s, a);              \
+    done = true;                                                                            \
+  }
+  FAMI_WCASE(1, 1) FAMI_WCASE(1, 2) FAMI_WCASE(1, 3) FAMI_WCASE(1, 4)
+  FAMI_WCASE(2, 1) FAMI_WCASE(2, 2) FAMI_WCASE(2, 3) FAMI_WCASE(2, 4)
+  FAMI_WCASE(3, 1) FAMI_WCASE(3, 2) FAMI_WCASE(3, 3) FAMI_WCASE(3, 4)
+  FAMI_WCASE(4, 1) FAMI_WCASE(4, 2) FAMI_WCASE(4, 3) FAMI_WCASE(4, 4)
+#undef FAMI_WCASE
+  if (!done) {
+    fami_set_error(nm, "no kernel instance");
+    return FAMI_ESHAPE;
+  }
+  FAMI_CHECK_LAUNCH(nm);
+  launch_reduce_plain(workspace, dw, Co, Ci, kh * kw, q.psplit, accumulate, s);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+
+// ---- bf16 implicit GEMM launch
+template <typename H, int MODE, int VEC>
+static int launch_igemm_h(const ConvArgsH& a, int MT, int NT, int KS, int ST, hipStream_t s) {
+  const dim3 grid(fami_cdiv(igemm_tiles(a, MT), 4 / KS), fami_cdiv(a.NTt, NT));
+#define FAMI_CASE(mt, nt, ks)                                                                        \
+  if (MT == mt && NT == nt && KS == ks) {                                                            \
+    if (ST == 3 && mt <= 2) hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 3>), grid, dim3(256), 0, s, a); \
+    else if (ST == 4 && mt <= 2) hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 4>), grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 2>), grid, dim3(256), 0, s, a);   \
+    return 0;                                                                                        \
+  }
+  if constexpr (VEC) {
+#define FAMI_ROW(nt) FAMI_CASE(1, nt, 1) FAMI_CASE(1, nt, 2) FAMI_CASE(1, nt, 4) FAMI_CASE(2, nt, 1) FAMI_CASE(2, nt, 2) FAMI_CASE(2, nt, 4) FAMI_CASE(4, nt, 1)
+    FAMI_ROW(1) FAMI_ROW(2) FAMI_ROW(3) FAMI_ROW(4)
+#undef FAMI_ROW
+  } else {
+    FAMI_CASE(2, 1, 1) FAMI_CASE(2, 2, 1) FAMI_CASE(2, 3, 1) FAMI_CASE(2, 4, 1)
+  }
+#undef FAMI_CASE
+  return -1;
+}
+
+template <typename H>
+static int run_igemm_h(ConvArgsH a, int mode, hipStream_t s, const char* name) {
+  a.xcd = g_xcd < 0 ? 1 : g_xcd;
+  a.par = (mode == 1 && a.sh == 1 && g_par) ? 1 : 0;
+  const int vec = (a.Ci % 8 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
+  int NT = pick_nt(a.NTt);
+  if (NT == 6) NT = 3;
+  if (NT > 4) NT = 4;
+  int MT = 2, KS = 1;
+  if (vec) {
+    // the bf16 kernel is operand-fetch bound (an MFMA needs 2 KiB of fragments): larger register tiles raise the
+    // MFMAs per fetched KiB, split-K restores parallelism on the low-resolution branches
+    const long nblk = fami_cdiv(a.NTt, NT);
+    const long tiles = (long)fami_cdiv(a.P, 16) * nblk;
+    const long iters = (long)a.kh * a.kw * a.KC;
+    // (a two-chunk reduction -- the 64 -> 256 1x1 of stage 1 and the input gradient of its 256 -> 64 twin, 20 frames @96x72 -- is all
+    //  prologue and epilogue: 64-pixel waves instead of 128: forward 38.1 -> 32.6 us, input gradient 38.6 -> 32.2, accumulating 58.4 -> 52.0,
+    //  tools/probes/layer1_1x1_tiles.py)
+    if (tiles >= 16384) MT = iters <= 2 ? 2 : 4;
+    else if (tiles >= 4096) MT = 2;
+    else {
+      MT = 1;
+      if (iters >= 8) KS = tiles < 1024 ? 4 : 2;
+    }
+  }
+  if (vec && g_force_mt) { MT = g_force_mt; NT = g_force_nt ? g_force_nt : NT; KS = g_force_ks ? g_force_ks : 1; }
+  const int ST = g_stages ? g_stages : 2;
+  int rc;
+  if (mode == 0)
+    rc = vec ? launch_igemm_h<H, 0, 1>(a, MT, NT, KS, ST, s) : launch_igemm_h<H, 0, 0>(a, MT, NT, KS, 2, s);
+  else
+    rc = vec ? launch_igemm_h<H, 1, 1>(a, MT, NT, KS, ST, s) : launch_igemm_h<H, 1, 0>(a, MT, NT, KS, 2, s);
+  if (rc != 0) {
+    fami_set_error(name, "no kernel instance for tile shape");
+    return FAMI_ESHAPE;
+  }
+  FAMI_CHECK_LAUNCH(name);
+  return FAMI_OK;
+}
+
+// f32 weight gradient.  Errors carry the names below whoever the caller is (fami_conv2d_wgrad_defer_f32, fami_conv2d_bwd_pair_f32 too).
+static int wgrad_f32_entry(const float* x, const float* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
+                           int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
+                           hipStream_t s, const XBN& xbn) {
+  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && x && dy && dw && workspace) {
+    // split-product kernel on the bf16 matrix pipe (conv_wgs3.hip)
+    const int G = fami_try_wgrad_s3(x, dy, workspace, ws_bytes, N, H, W, Ci, Co, s, "fami_conv2d_wgrad_f32", xbn);
+    if (G < 0) return G;
+    if (G > 0) {
+      launch_reduce_taps(workspace, dw, Co, Ci, 9, G, accumulate, s);
+      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/reduce");
+      return FAMI_OK;
+    }
+  }
+  if (xbn.on) {
+    fami_set_error("fami_conv2d_wgrad_defer_xbn_f32", "input BatchNorm needs the split-product kernel (ask fami_conv2d_xbn_ok_f32 first)");
+    return FAMI_ESHAPE;
+  }
+  WgradLdsPlan l = g_wgrad_lds_f32 ? wgrad_lds_plan_f32(N, H, W, Ci, Co, kh, kw, stride, pad, dil) : WgradLdsPlan{0};
+  // measured (tools/bench_wgrad.py f32): the staged kernel wins once the channel blocks alone give >= 64 workgroup
+  // columns (384 channels: 136 vs 151 us); below that the per-tap scalar-operand kernel is faster (85 vs 105 us)
+  // ... and the linear-address per-tap kernel beats both wherever it applies (384 channels: 78 vs 103 us)
+  if (g_wgrad_lds_f32 == 2 && l.ok &&
+      (l.ciBlocks * l.coBlocks < 64 || (g_wgrad_lin && wgrad_lin_ok(H, W, Ci, Co, kh, kw, stride, pad, dil))))
+    l.ok = 0;
+  if (l.ok && x && dy && dw && workspace && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
+    const long need = (long)l.G * Co * Ci * 9 * (long)sizeof(float);
+    FAMI_REQUIRE(ws_bytes >= need, "fami_conv2d_wgrad_f32", "workspace too small");
+    WgradLdsArgsF a;
+    a.x = x; a.dy = dy; a.part = workspace;
+    a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.P = N * H * W;
+    a.chunk = l.chunk; a.ciBlocks = l.ciBlocks; a.coBlocks = l.coBlocks; a.xcd = g_xcd_w;
+    a.CiB = 16 * l.CIT; a.CoB = 16 * l.COT; a.xrow = l.xrow; a.yrow = l.yrow; a.xfloats = l.xbytes;
+    const dim3 grid(l.G, l.ciBlocks * l.coBlocks);
+    bool ok = false;
+#define FAMI_WF_CASE(cit, cot)                                                                                        \
+  if (l.CIT == cit && l.COT == cot) {                                                                                 \
+    fami_lds_limit<conv_wgrad_lds_f32_kernel<cit, cot>>(160 * 1024);                                                  \
+    hipLaunchKernelGGL((conv_wgrad_lds_f32_kernel<cit, cot>), grid, dim3(512), l.lds, s, a);                          \
+    ok = true;                                                                                                        \
+  }
+    FAMI_WF_CASE(1, 1) FAMI_WF_CASE(1, 2) FAMI_WF_CASE(1, 3) FAMI_WF_CASE(1, 4) FAMI_WF_CASE(2, 1) FAMI_WF_CASE(2, 2)
+    FAMI_WF_CASE(2, 3) FAMI_WF_CASE(2, 4) FAMI_WF_CASE(3, 1) FAMI_WF_CASE(3, 2) FAMI_WF_CASE(3, 3) FAMI_WF_CASE(3, 4)
+    FAMI_WF_CASE(4, 1) FAMI_WF_CASE(4, 2) FAMI_WF_CASE(4, 3) FAMI_WF_CASE(4, 4)
+#undef FAMI_WF_CASE
+    if (ok) {
+      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/lds");
+      launch_reduce_taps(workspace, dw, Co, Ci, 9, l.G, accumulate, s);
+      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/reduce");
+      return FAMI_OK;
+    }
+  }
+  return wgrad_impl<float>(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s,
+                           "fami_conv2d_wgrad_f32");
+}
+
+// 16-bit activations / gradients, fp32 weight gradient
+template <typename HT>
+static int wgrad_h_impl(const char* nm, const HT* x, const HT* dy, float* dw, float* workspace, long ws_bytes, int N,
+                        int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
+                        hipStream_t s, const XBN& xbn = xbn_none()) {
+  if (g_wgrad_lds && x && dy && dw && workspace && kh == kw) {
+    // round-3 kernel (conv_wg16.hip): pipelined staging, padded patch, 8 waves; 1x1 / 3x3, stride 1 / 2, any dilation
+    const int G = fami_try_wgrad16(storage_kind<HT>(), x, dy, workspace, ws_bytes, N, H, W, Ci, Co, kh, stride,
+                                   pad, dil, s, nm, xbn);
+    if (G < 0) return G;
+    if (G > 0) {
+      launch_reduce_taps(workspace, dw, Co, Ci, kh * kw, G, accumulate, s);
+      FAMI_CHECK_LAUNCH(nm);
+      return FAMI_OK;
+    }
+  }
+  if (xbn.on) {
+    fami_set_error(nm, "input BatchNorm needs the conv_wg16 kernel (ask fami_conv2d_xbn_ok first)");
+    return FAMI_ESHAPE;
+  }
+  const WgradLdsPlan l = g_wgrad_lds ? wgrad_lds_plan(N, H, W, Ci, Co, kh, kw, stride, pad, dil) : WgradLdsPlan{0};
+  if (l.ok && x && dy && dw && workspace && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
+    const long need = (long)l.G * Co * Ci * 9 * (long)sizeof(float);
+    FAMI_REQUIRE(ws_bytes >= need, nm, "workspace too small");
+    WgradLdsArgs a;
+    a.x = x; a.dy = dy; a.part = workspace;
+    a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.P = N * H * W;
+    a.chunk = l.chunk; a.nsub = l.nsub; a.ciBlocks = l.ciBlocks; a.coBlocks = l.coBlocks; a.xcd = g_xcd_w;
+    a.CiB = 16 * l.CIT; a.CoB = 16 * l.COT; a.xrow = l.xrow; a.yrow = l.yrow; a.xbytes = l.xbytes;
+    const dim3 grid(l.G, l.ciBlocks * l.coBlocks);
+    bool ok = false;
+#define FAMI_WL_CASE(cit, cot)                                                                                     \
+  if (l.CIT == cit && l.COT == cot) {                                                                              \
+    fami_lds_limit<conv_wgrad_h_kernel<HT, cit, cot>>(150 * 1024);                                                 \
+    hipLaunchKernelGGL((conv_wgrad_h_kernel<HT, cit, cot>), grid, dim3(256), l.lds, s, a);                         \
+    ok = true;                                                                                                     \
+  }
+    FAMI_WL_CASE(1, 1) FAMI_WL_CASE(1, 2) FAMI_WL_CASE(1, 3) FAMI_WL_CASE(2, 1) FAMI_WL_CASE(2, 2) FAMI_WL_CASE(2, 3)
+    FAMI_WL_CASE(3, 1) FAMI_WL_CASE(3, 2) FAMI_WL_CASE(3, 3)
+#undef FAMI_WL_CASE
+    if (ok) {
+      FAMI_CHECK_LAUNCH(nm);
+      launch_reduce_taps(workspace, dw, Co, Ci, 9, l.G, accumulate, s);
+      FAMI_CHECK_LAUNCH(nm);
+      return FAMI_OK;
+    }
+  }
+  return wgrad_impl<HT>(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s, nm);
+}
+
+template <typename HT>
+static int pack_conv_weight_h_impl(const char* nm, const float* w_oihw, HT* wp, int Co, int Ci, int kh, int kw, int mode,
+                                   hipStream_t s) {
+  FAMI_REQUIRE(w_oihw && wp && Co > 0 && Ci > 0 && (mode == 0 || mode == 1), nm, "bad argument");
+  const int kd = mode == 0 ? Ci : Co, nd = mode == 0 ? Co : Ci;
+  const int KC = fami_cdiv(kd, 32), NTt = fami_cdiv(nd, 16);
+  const long total = (long)kh * kw * KC * NTt * 512;
+  hipLaunchKernelGGL(pack_w_h_kernel<HT>, dim3(fami_ew_grid(total)), dim3(256), 0, s, w_oihw, wp, Co, Ci, kh * kw, KC, NTt, mode);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+
+// y[N,Ho,Wo,Co] (16-bit, or f32 when out_f32) (=|+=) relu?( conv(x[N,H,W,Ci]) + bias ) ; wp packed with mode 0
+// (the f32 form is conv_fwd_f32_impl, see there)
+template <typename HT>
+static int conv_fwd_h_impl(const char* nm, const HT* x, const HT* wp, const float* bias, void* y, int N, int H, int W,
+                           int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int relu, int accumulate,
+                           int out_f32, hipStream_t s, const EpiBN& e = epi_none(), const XBN& xbn = xbn_none()) {
+  if (const int rc = conv_args_check(nm, x && wp && y, N, H, W, Ci, Co, kh, kw, stride, pad, dil)) return rc;
+  if (e.slots && (out_f32 || relu || (Co & 3))) {
+    fami_set_error(nm, "fused BatchNorm statistics need a 16-bit output, no ReLU and Co % 4 == 0");
+    return FAMI_ESHAPE;
+  }
+  ConvArgsH a;
+  a.e = e; a.emode = e.slots ? e.mode : 0;
+  a.x = x; a.wp = wp; a.y = y; a.bias = bias; a.relu = relu; a.accumulate = accumulate; a.out_f32 = out_f32;
+  if (const int rc = conv_geometry(a, nm, 0, N, H, W, Ci, Co, kh, kw, stride, pad, dil, 2, 32)) return rc;
+  if (Ci == 3 && !xbn.on) {
+    const int rc = fami_try_conv_stem1(storage_kind<HT>(), x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil,
+                                       a.NTt, relu, accumulate, out_f32, s, nm, e);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) {
+    const int rc = try_conv3x3_lds<HT>(x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, out_f32, s, nm, e, xbn);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !e.slots && !xbn.on && g_use_lds != 0) {
+    const int rc = fami_try_conv3x3_t4_dil(storage_kind<HT>(), x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu,
+                                           accumulate, out_f32, dil, s, nm);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (xbn.on) {
+    fami_set_error(nm, "input BatchNorm needs the register-blocked 3x3 kernel (ask fami_conv2d_xbn_ok first)");
+    return FAMI_ESHAPE;
+  }
+  return run_igemm_h<HT>(a, 0, s, nm);
+}
+
+// dx[N,H,W,Ci] (=|+=) conv_transpose(dy[N,Ho,Wo,Co]) ; wp packed with mode 1
+// (the f32 form is conv_dgrad_f32_impl, see there)
+template <typename HT>
+static int conv_dgrad_h_impl(const char* nm, const HT* dy, const HT* wp, HT* dx, int N, int H, int W, int Ci, int Co,
+                             int kh, int kw, int stride, int pad, int dil, int accumulate, hipStream_t s,
+                             const EpiBN& e = epi_none()) {
+  if (const int rc = conv_args_check(nm, dy && wp && dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil)) return rc;
+  if (e.slots && (Ci & 3)) {
+    fami_set_error(nm, "fused BatchNorm statistics need Ci % 4 == 0");
+    return FAMI_ESHAPE;
+  }
+  ConvArgsH a;
+  a.e = e; a.emode = e.slots ? e.mode : 0;
+  a.x = dy; a.wp = wp; a.y = dx; a.bias = nullptr; a.relu = 0; a.accumulate = accumulate; a.out_f32 = 0;
+  if (const int rc = conv_geometry(a, nm, 1, N, H, W, Ci, Co, kh, kw, stride, pad, dil, 2, 32)) return rc;
+  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) {
+    const int rc = try_conv3x3_lds<HT>(dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 0, s, nm, e);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !e.slots && g_use_lds != 0) {
+    const int rc = fami_try_conv3x3_t4_dil(storage_kind<HT>(), dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0,
+                                           accumulate, 0, dil, s, nm);
+    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
+  }
+  return run_igemm_h<HT>(a, 1, s, nm);
+}
+
+// ---- bodies of the 16-bit entry points (FAMI_CONV_H_ABI below stamps the bf16 / f16 exports; nm = the export's name)
+// Deferred slab reduce: see fami_conv2d_wgrad_defer_f32
+template <typename HT>
+static int wgrad_defer_h(const char* nm, const HT* x, const HT* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
+                         int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate, long* desc_out,
+                         hipStream_t s) {
+  FAMI_REQUIRE(desc_out, nm, "null descriptor");
+  return with_deferred_reduce(nm, desc_out, [&] {
+    return wgrad_h_impl<HT>(nm, x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s);
+  });
+}
+template <typename HT>
+static int pack_conv_weights_batch_h(const char* nm, const float* params, HT* packed, const void* desc, int n, hipStream_t s) {
+  FAMI_REQUIRE(params && packed && desc && n > 0 && n < 65536, nm, "bad argument");
+  hipLaunchKernelGGL(pack_w_batch_kernel<HT>, dim3(48, n), dim3(256), 0, s, params, packed, reinterpret_cast<const PackDesc*>(desc));
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+// BatchNorm (+ReLU) of the INPUT applied while it is staged (XBN, conv_epi.h): x is the pre-normalisation tensor z.
+// fwd: statistics of z come from xslots (filled by fami_conv2d_fwd_stats_*), mean / invstd / running statistics are
+// published; slots / pivot_src (optional) request the statistics of y for the BatchNorm that follows.
+template <typename HT>
+static int fwd_xbn_h(const char* nm, const HT* z, const HT* wp, const float* bias, HT* y, int N, int H, int W, int Ci, int Co,
+                     void* slots, const float* pivot_src, const void* xslots, long xP, const float* xgamma, const float* xbeta,
+                     float* xmean, float* xinvstd, float* xrunning_mean, float* xrunning_var, float xmomentum, float xeps,
+                     hipStream_t s) {
+  FAMI_REQUIRE(xslots && xgamma && xbeta && xmean && xinvstd && xP > 0, nm, "bad argument");
+  return conv_fwd_h_impl<HT>(nm, z, wp, bias, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0, 0, s, epi_fwd_stats(slots, Co, pivot_src),
+                             xbn_fwd(xslots, xP, Ci, xgamma, xbeta, xmean, xinvstd, xrunning_mean, xrunning_var, xmomentum, xeps));
+}
+// Round 6: the same BatchNorm + ReLU of the input INSIDE the convolution's launch, with the normalised tensor written to
+// a_out as well (the weight-resident 48-channel kernel transforms its patch in LDS and stores the rows it owns): one launch
+// and one read of z per BasicBlock less than fami_bn_apply_slots_* + fami_conv2d_fwd_stats_*, bit for bit their results.
+// Ask fami_conv2d_fwd_bnin_ok first.
+template <typename HT>
+static int fwd_bnin_h(const char* nm, const HT* z, const HT* wp, const float* bias, HT* y, HT* a_out, int N, int H, int W, int Ci,
+                      int Co, void* slots, const float* pivot_src, const void* xslots, long xP, const float* xgamma,
+                      const float* xbeta, float* xmean, float* xinvstd, float* xrunning_mean, float* xrunning_var, float xmomentum,
+                      float xeps, hipStream_t s) {
+  FAMI_REQUIRE(a_out && xslots && xgamma && xbeta && xmean && xinvstd && xP > 0, nm, "bad argument");
+  if (!fami_conv2d_fwd_bnin_ok(N, H, W, Ci, Co)) {
+    fami_set_error(nm, "no kernel applies the input BatchNorm in its launch for this shape (ask fami_conv2d_fwd_bnin_ok)");
+    return FAMI_ESHAPE;
+  }
+  return conv_fwd_h_impl<HT>(nm, z, wp, bias, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0, 0, s, epi_fwd_stats(slots, Co, pivot_src),
+                             xbn_fwd(xslots, xP, Ci, xgamma, xbeta, xmean, xinvstd, xrunning_mean, xrunning_var, xmomentum, xeps, a_out));
+}
+template <typename HT>
+static int wgrad_defer_xbn_h(const char* nm, const HT* z, const HT* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
+                             int W, int Ci, int Co, int accumulate, long* desc_out, const float* xmean, const float* xinvstd,
+                             const float* xgamma, const float* xbeta, hipStream_t s) {
+  FAMI_REQUIRE(desc_out && xmean && xinvstd && xgamma && xbeta, nm, "bad argument");
+  return with_deferred_reduce(nm, desc_out, [&] {
+    return wgrad_h_impl<HT>(nm, z, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, 3, 3, 1, 1, 1, accumulate, s,
+                            xbn_wgrad(Ci, xmean, xinvstd, xgamma, xbeta));
+  });
+}
+// fused BatchNorm statistics, see the _f32 forms
+template <typename HT>
+static int fwd_stats_h(const char* nm, const HT* x, const HT* wp, const float* bias, HT* y, int N, int H, int W, int Ci, int Co,
+                       int kh, int kw, int stride, int pad, int dil, void* slots, const float* pivot_src, hipStream_t s) {
+  FAMI_REQUIRE(slots, nm, "null slots");
+  return conv_fwd_h_impl<HT>(nm, x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil, 0, 0, 0, s,
+                             epi_fwd_stats(slots, Co, pivot_src));
+}
+template <typename HT>
+static int dgrad_bnstats_h(const char* nm, const HT* dy, const HT* wp, HT* dx, int N, int H, int W, int Ci, int Co, int kh, int kw,
+                           int stride, int pad, int dil, int accumulate, const HT* z, const HT* yrelu, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, int relu, void* slots, hipStream_t s) {
+  FAMI_REQUIRE(slots && epi_bwd_stats_ok(z, yrelu, mean, invstd, gamma, beta, relu), nm, "bad argument");
+  return conv_dgrad_h_impl<HT>(nm, dy, wp, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s,
+                               epi_bwd_stats(slots, Ci, z, yrelu, mean, invstd, gamma, beta, relu));
+}
+// conv_pair.h: input gradient (optionally with the backward-statistics epilogue of fami_conv2d_dgrad_bnstats_*: slots != NULL)
+// and deferred weight gradient of one 3x3 stride-1 convolution as ONE launch where a combined instance exists (ask
+// fami_conv2d_bwd_pair_ok), as the two single launches otherwise.  Results are bitwise those of the two-call form.
+template <typename HT>
+static int bwd_pair_h(const char* nm, const HT* x, const HT* dy, const HT* wpd, HT* dx, float* dw, float* workspace, long ws_bytes,
+                      int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int acc_dx, int acc_dw,
+                      long* desc_out, const HT* z, const HT* yrelu, const float* mean, const float* invstd, const float* gamma,
+                      const float* beta, int relu, void* slots, hipStream_t s) {
+  FAMI_REQUIRE(desc_out, nm, "null descriptor");
+  EpiBN e = epi_none();
+  if (slots) {
+    FAMI_REQUIRE(epi_bwd_stats_ok(z, yrelu, mean, invstd, gamma, beta, relu), nm, "bad argument");
+    e = epi_bwd_stats(slots, Ci, z, yrelu, mean, invstd, gamma, beta, relu);
+  }
+  return bwd_pair_run(
+      nm, desc_out, s,
+      [&] { return conv_dgrad_h_impl<HT>(nm, dy, wpd, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dx, s, e); },
+      [&] { return wgrad_h_impl<HT>(nm, x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dw, s); });
+}
+
+// ---- C ABI: tuning hooks, shape queries and the f32 entry points
 extern "C" {
-int fami_dcn_tune(int mode);          // align.hip
-int fami_bn_tune_small(long elems);   // norm.hip
 
 // tuning hook (benchmarks only): force the implicit-GEMM tile (0 = heuristic)
 int fami_conv_tune(int mt, int nt, int ks) {
@@ -2668,7 +3304,6 @@ int fami_conv_tune(int mt, int nt, int ks) {
 }
 // 1 routes eligible 3x3 stride-1 convolutions through the LDS-staged kernel, 0 through the direct kernels,
 // -1 = default (bf16: staged, f32: direct)
-void fami_conv_stem_tune(int on);
 int fami_conv_tune_lds(int on) {
   if (on == 9000 || on == 9001) {            // conv_stem.hip (the stem's first convolution, 16-bit forward): off / on
     fami_conv_stem_tune(on - 9000);
@@ -2788,10 +3423,18 @@ int fami_pack_conv_weight_f32(const float* w_oihw, float* wp, int Co, int Ci, in
   return FAMI_OK;
 }
 
+// every weight image of a step in one launch.  desc: device array of n records {long src_elem_off, long dst_elem_off,
+// int Co, int Ci, int taps, int mode} (32 bytes each); params = fp32 parameter arena, packed = destination arena.
+int fami_pack_conv_weights_batch_f32(const float* params, float* packed, const void* desc, int n, hipStream_t s) {
+  FAMI_REQUIRE(params && packed && desc && n > 0 && n < 65536, "fami_pack_conv_weights_batch_f32", "bad argument");
+  hipLaunchKernelGGL(pack_w_batch_kernel<float>, dim3(48, n), dim3(256), 0, s, params, packed, reinterpret_cast<const PackDesc*>(desc));
+  FAMI_CHECK_LAUNCH("fami_pack_conv_weights_batch_f32");
+  fami_pack_split_batch(params, packed, desc, n, s);      // the split images behind the 3x3 fragment images (conv_t5.hip)
+  FAMI_CHECK_LAUNCH("fami_pack_conv_weights_batch_f32/split");
+  return FAMI_OK;
+}
+
 // y[N,Ho,Wo,Co] = conv(x[N,H,W,Ci], W) (+bias) (+addend) (relu) ; wp packed with mode 0
-static int conv_fwd_f32_impl(const char* nm, const float* x, const float* wp, const float* bias, const float* addend,
-                             float* y, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil,
-                             int relu, int accumulate, const EpiBN& e, hipStream_t s, const XBN& xbn = xbn_none());
 int fami_conv2d_fwd_f32(const float* x, const float* wp, const float* bias, const float* addend, float* y, int N,
                         int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int relu,
                         int accumulate, hipStream_t s) {
@@ -2805,10 +3448,8 @@ int fami_conv2d_fwd_stats_f32(const float* x, const float* wp, const float* bias
                               int Co, int kh, int kw, int stride, int pad, int dil, void* slots, const float* pivot_src,
                               hipStream_t s) {
   FAMI_REQUIRE(slots, "fami_conv2d_fwd_stats_f32", "null slots");
-  EpiBN e = epi_none();
-  e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;
   return conv_fwd_f32_impl("fami_conv2d_fwd_stats_f32", x, wp, bias, nullptr, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil,
-                           0, 0, e, s);
+                           0, 0, epi_fwd_stats(slots, Co, pivot_src), s);
 }
 // f32 form of fami_conv2d_fwd_xbn_* (see the 16-bit entry points below): z is the PRE-normalisation input; the
 // split-product kernel applies BatchNorm + ReLU while it stages z
@@ -2817,63 +3458,12 @@ int fami_conv2d_fwd_xbn_f32(const float* z, const float* wp, const float* bias, 
                             const float* xbeta, float* xmean, float* xinvstd, float* xrunning_mean, float* xrunning_var,
                             float xmomentum, float xeps, hipStream_t s) {
   FAMI_REQUIRE(xslots && xgamma && xbeta && xmean && xinvstd && xP > 0, "fami_conv2d_fwd_xbn_f32", "bad argument");
-  EpiBN e = epi_none();
-  if (slots) {
-    e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;
-  }
-  XBN xb = xbn_none();
-  xb.on = 1; xb.slots = reinterpret_cast<const double*>(xslots); xb.ns = bn_slots(Ci); xb.C = Ci; xb.P = xP;
-  xb.gamma = xgamma; xb.beta = xbeta; xb.mean = xmean; xb.invstd = xinvstd; xb.running_mean = xrunning_mean;
-  xb.running_var = xrunning_var; xb.momentum = xmomentum; xb.eps = xeps;
-  return conv_fwd_f32_impl("fami_conv2d_fwd_xbn_f32", z, wp, bias, nullptr, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0, e, s, xb);
+  return conv_fwd_f32_impl("fami_conv2d_fwd_xbn_f32", z, wp, bias, nullptr, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0,
+                           epi_fwd_stats(slots, Co, pivot_src), s,
+                           xbn_fwd(xslots, xP, Ci, xgamma, xbeta, xmean, xinvstd, xrunning_mean, xrunning_var, xmomentum, xeps));
 }
-}  // extern "C"
-int fami_try_conv_stem1(int half_kind, const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
-                        int kh, int kw, int stride, int pad, int dil, int NTt, int relu, int accumulate, int out_f32, hipStream_t s,
-                        const char* name, const EpiBN& epi);      // conv_stem.hip
-static int conv_fwd_f32_impl(const char* nm, const float* x, const float* wp, const float* bias, const float* addend,
-                             float* y, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil,
-                             int relu, int accumulate, const EpiBN& e, hipStream_t s, const XBN& xbn) {
-  FAMI_REQUIRE(x && wp && y && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
-  if (!geom_ok(kh, kw, stride, pad, dil)) {
-    fami_set_error(nm, "unsupported geometry");
-    return FAMI_ESHAPE;
-  }
-  ConvArgs a;
-  a.e = e; a.emode = e.slots ? e.mode : 0;
-  a.x = x; a.wp = wp; a.y = y; a.bias = bias; a.addend = addend;
-  a.N = N; a.Hi = H; a.Wi = W; a.Ci = Ci;
-  a.Ho = out_dim(H, kh, stride, pad, dil); a.Wo = out_dim(W, kw, stride, pad, dil); a.Co = Co;
-  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
-  a.KC = fami_cdiv(Ci, 16); a.NTt = fami_cdiv(Co, 16); a.relu = relu; a.accumulate = accumulate;
-  const long P = (long)N * a.Ho * a.Wo;
-  const long xb = (long)N * H * W * Ci * 4, wb = (long)kh * kw * a.KC * a.NTt * 1024;
-  FAMI_REQUIRE(P > 0 && P < (1L << 31) && xb < (1L << 31) && wb < (1L << 31), nm, "tensor >= 2 GiB");
-  a.P = (int)P; a.x_bytes = (unsigned)xb; a.wp_bytes = (unsigned)wb;
-  if (Ci == 3 && !addend && !xbn.on) {
-    const int rc = fami_try_conv_stem1(2, x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil, a.NTt, relu, accumulate, 1, s, nm, e);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !addend) {
-    const int rc = try_conv3x3_lds<float>(x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, 1, s, nm, e, xbn);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !addend && !e.slots && !xbn.on && g_use_lds != 0) {
-    const int rc = fami_try_conv3x3_t4_dil(2, x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, 1, dil, s, nm);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (xbn.on) {
-    fami_set_error(nm, "input BatchNorm needs the split-product 3x3 kernel (ask fami_conv2d_xbn_ok_f32 first)");
-    return FAMI_ESHAPE;
-  }
-  return run_igemm(a, 0, s, nm);
-}
-extern "C" {
 
 // dx[N,H,W,Ci] = conv^T(dy[N,Ho,Wo,Co], W) (+addend) ; wp packed with mode 1
-static int conv_dgrad_f32_impl(const char* nm, const float* dy, const float* wp, const float* addend, float* dx, int N,
-                               int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                               const EpiBN& e, hipStream_t s);
 int fami_conv2d_dgrad_f32(const float* dy, const float* wp, const float* addend, float* dx, int N, int H, int W,
                           int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
                           hipStream_t s) {
@@ -2887,153 +3477,9 @@ int fami_conv2d_dgrad_bnstats_f32(const float* dy, const float* wp, float* dx, i
                                   int kh, int kw, int stride, int pad, int dil, int accumulate, const float* z,
                                   const float* yrelu, const float* mean, const float* invstd, const float* gamma,
                                   const float* beta, int relu, void* slots, hipStream_t s) {
-  FAMI_REQUIRE(slots && z && mean && invstd && gamma && beta && (relu != 1 || yrelu) && relu >= 0 && relu <= 2,
-               "fami_conv2d_dgrad_bnstats_f32", "bad argument");
-  EpiBN e = epi_none();
-  e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Ci); e.mode = 2; e.relu = relu; e.C = Ci;
-  e.z = z; e.yr = yrelu; e.mean = mean; e.invstd = invstd; e.gamma = gamma; e.beta = beta;
+  FAMI_REQUIRE(slots && epi_bwd_stats_ok(z, yrelu, mean, invstd, gamma, beta, relu), "fami_conv2d_dgrad_bnstats_f32", "bad argument");
   return conv_dgrad_f32_impl("fami_conv2d_dgrad_bnstats_f32", dy, wp, nullptr, dx, N, H, W, Ci, Co, kh, kw, stride, pad,
-                             dil, accumulate, e, s);
-}
-}  // extern "C"
-static int conv_dgrad_f32_impl(const char* nm, const float* dy, const float* wp, const float* addend, float* dx, int N,
-                               int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                               const EpiBN& e, hipStream_t s) {
-  FAMI_REQUIRE(dy && wp && dx && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
-  if (!geom_ok(kh, kw, stride, pad, dil)) {
-    fami_set_error(nm, "unsupported geometry");
-    return FAMI_ESHAPE;
-  }
-  ConvArgs a;
-  a.e = e; a.emode = e.slots ? e.mode : 0;
-  a.x = dy; a.wp = wp; a.y = dx; a.bias = nullptr; a.addend = addend;
-  a.N = N; a.Hi = out_dim(H, kh, stride, pad, dil); a.Wi = out_dim(W, kw, stride, pad, dil); a.Ci = Co;
-  a.Ho = H; a.Wo = W; a.Co = Ci;
-  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
-  a.KC = fami_cdiv(Co, 16); a.NTt = fami_cdiv(Ci, 16); a.relu = 0; a.accumulate = accumulate;
-  const long P = (long)N * H * W;
-  const long xb = (long)N * a.Hi * a.Wi * Co * 4, wb = (long)kh * kw * a.KC * a.NTt * 1024;
-  FAMI_REQUIRE(P > 0 && P < (1L << 31) && xb < (1L << 31) && wb < (1L << 31), nm, "tensor >= 2 GiB");
-  a.P = (int)P; a.x_bytes = (unsigned)xb; a.wp_bytes = (unsigned)wb;
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && !addend) {
-    // dgrad of a stride-1 "same" conv is the same conv on dy with the taps mirrored: GEMM K = Co, N = Ci
-    const int rc = try_conv3x3_lds<float>(dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 1, s, nm, e);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !addend && !e.slots && g_use_lds != 0) {
-    const int rc = fami_try_conv3x3_t4_dil(2, dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 1, dil, s, nm);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  return run_igemm(a, 1, s, nm);
-}
-extern "C" {
-
-struct WgradPlan { int MT, NT, ciBlocks, coBlocks, psplit, chunk, pertap, w8; long P; };
-static bool wgrad_lin_ok(int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil);
-static WgradPlan wgrad_plan(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int w8 = 0) {
-  WgradPlan q;
-  const int Ho = out_dim(H, kh, stride, pad, dil), Wo = out_dim(W, kw, stride, pad, dil);
-  q.P = (long)N * Ho * Wo;
-  q.MT = pick_small(fami_cdiv(Ci, 16));
-  q.NT = pick_small(fami_cdiv(Co, 16));
-  if (g_wgrad_mt > 0 && g_wgrad_mt <= q.MT) q.MT = g_wgrad_mt;  // benchmarks: fewer input-channel tiles per workgroup
-  q.ciBlocks = fami_cdiv(fami_cdiv(Ci, 16), q.MT);
-  q.coBlocks = fami_cdiv(fami_cdiv(Co, 16), q.NT);
-  q.pertap = (kh * kw > 1 && kh * kw <= 9) ? 1 : 0;   // one wave per tap (3x3): workgroups of kh*kw waves
-  const long by = q.pertap ? (long)q.ciBlocks * q.coBlocks : (long)kh * kw * q.ciBlocks * q.coBlocks;
-  long ps = ((q.pertap ? (g_wgrad_ps ? g_wgrad_ps : 512) : 1024) + by - 1) / by;
-  q.w8 = 0;
-  // w8 = 3: 16-wave workgroups while a column of the grid still has >= 16 of them (48 / 96 / 192 channels: 66.9 vs 69.2,
-  // 64.3 vs 67.7, 67.1 vs 70.2 us, and half the slabs), 8-wave ones beyond (384 channels, 7 per column: 120 vs 78 us)
-  if (w8 == 3) w8 = 256 / by >= 16 ? 2 : 1;
-  if (w8 && q.pertap && kh * kw == 9 && ps >= 9) {
-    // 8-/16-wave workgroups: c slabs need c + ceil(c/8) workgroups.  Never more workgroups than the target (one
-    // workgroup beyond the resident set costs a whole extra round: 192 channels, 9 columns x 57 = 513 workgroups ran
-    // 90 us against 80 us for 9 x 43)
-    q.w8 = w8;
-    const long T = (g_wgrad_ps ? g_wgrad_ps : (w8 == 2 ? 256 : 512)) / by;
-    ps = T * 8 / 9;
-    while (ps > 1 && ps + (ps + 7) / 8 > T) --ps;
-    if (ps < 1) ps = 1;
-    if (w8 == 2) ps *= 2;   // pixel chunks: two per slab
-  }
-  const long maxps = q.pertap ? (q.P + 63) / 64 : (q.P + 255) / 256;
-  if (ps > maxps) ps = maxps;
-  if (ps < 1) ps = 1;
-  long chunk = (q.P + ps - 1) / ps;
-  chunk = ((chunk + 15) / 16) * 16;
-  ps = (q.P + chunk - 1) / chunk;
-  if (q.w8 == 2) ps = (ps + 1) / 2;   // slabs
-  q.psplit = (int)ps;
-  q.chunk = (int)chunk;
-  return q;
-}
-
-// bf16 transposing-LDS wgrad plan (3x3 stride-1 pad-1): pixel groups G, chunk pixels, channel blocks
-struct WgradLdsPlan { int ok, CIT, COT, ciBlocks, coBlocks, G, chunk, nsub; size_t lds; int xrow, yrow, xbytes; };
-static WgradLdsPlan wgrad_lds_plan(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
-  WgradLdsPlan q;
-  q.ok = 0;
-  if (!(kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) || (Ci % 16) || (Co % 16) || W > 160) return q;
-  q.CIT = Ci % 48 == 0 ? 3 : (Ci % 32 == 0 ? 2 : 1);
-  q.COT = Co % 48 == 0 ? 3 : (Co % 32 == 0 ? 2 : 1);
-  q.ciBlocks = Ci / (16 * q.CIT);
-  q.coBlocks = Co / (16 * q.COT);
-  const long P = (long)N * H * W;
-  const long blocks = (long)q.ciBlocks * q.coBlocks;
-  long G = (512 + blocks - 1) / blocks;
-  long chunk = (P + G - 1) / G;
-  chunk = ((chunk + 31) / 32) * 32;
-  if (chunk < 32) chunk = 32;
-  if (chunk > 320) chunk = 320;
-  q.nsub = g_wgrad_nsub;
-  G = (P + chunk * q.nsub - 1) / (chunk * q.nsub);
-  q.G = (int)G;
-  q.chunk = (int)chunk;
-  // LDS rows are unpadded: the 4 pixel rows a 16-lane group hands to one transposing read are 32/64/96 bytes apart
-  // (distinct bank groups); padding would only separate the kq groups and costs the second resident workgroup
-  q.xrow = 32 * q.CIT;
-  q.yrow = 32 * q.COT;
-  q.xbytes = (q.chunk + 2 * (W + 1)) * q.xrow;
-  q.lds = (size_t)q.xbytes + (size_t)q.chunk * q.yrow + 32;
-  q.ok = q.lds <= 150 * 1024 && P < (1L << 31) && G < 65536;
-  return q;
-}
-
-// f32 LDS wgrad plan (3x3 stride-1 pad-1): one 8-wave workgroup per CU (the tile takes most of the 160 KB), about two
-// workgroups per CU in total so the partial-slab traffic stays at ~512 slabs
-static int lds_row_floats(int cb) {  // row stride with (stride mod 64) in {16, 48}: conflict-free 4-row reads
-  const int m = cb % 64;
-  return (m == 16 || m == 48) ? cb : cb + 16;  // cb is a multiple of 16: m in {0, 32} -> +16
-}
-static WgradLdsPlan wgrad_lds_plan_f32(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil) {
-  WgradLdsPlan q;
-  q.ok = 0;
-  if (!(kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) || (Ci % 16) || (Co % 16) || W < 4) return q;
-  q.CIT = Ci % 48 == 0 ? 3 : (Ci % 64 == 0 ? 4 : (Ci % 32 == 0 ? 2 : 1));
-  q.COT = Co % 48 == 0 ? 3 : (Co % 64 == 0 ? 4 : (Co % 32 == 0 ? 2 : 1));
-  q.ciBlocks = Ci / (16 * q.CIT);
-  q.coBlocks = Co / (16 * q.COT);
-  q.nsub = 1;
-  q.xrow = lds_row_floats(16 * q.CIT);
-  q.yrow = lds_row_floats(16 * q.COT);
-  const long P = (long)N * H * W;
-  const long blocks = (long)q.ciBlocks * q.coBlocks;
-  const long budget = 156 * 1024 / 4 - 16 - 2L * (W + 1) * q.xrow;  // floats left for the chunk rows
-  if (budget < 8L * (q.xrow + q.yrow)) return q;
-  long cmax = budget / (q.xrow + q.yrow);
-  cmax -= cmax % 8;
-  long G = (512 + blocks - 1) / blocks;
-  long chunk = (P + G - 1) / G;
-  chunk = ((chunk + 7) / 8) * 8;
-  if (chunk > cmax) chunk = cmax;
-  G = (P + chunk - 1) / chunk;
-  q.G = (int)G;
-  q.chunk = (int)chunk;
-  q.xbytes = (int)((chunk + 2 * (W + 1)) * q.xrow);  // floats
-  q.lds = ((size_t)q.xbytes + (size_t)chunk * q.yrow + 16) * 4;
-  q.ok = P < (1L << 31) && G < 65536;
-  return q;
+                             dil, accumulate, epi_bwd_stats(slots, Ci, z, yrelu, mean, invstd, gamma, beta, relu), s);
 }
 
 // 1 if a 16-bit 3x3 stride-1 pad-1 convolution of this shape can take its input un-normalised (fami_conv2d_fwd_xbn_* and
@@ -3067,232 +3513,11 @@ long fami_conv2d_wgrad_workspace(int N, int H, int W, int Ci, int Co, int kh, in
   return need;
 }
 
-}  // extern "C"
-
-// dw[Co,Ci,kh,kw] fp32 (=|+=) sum_pixels x (*) dy ; workspace from fami_conv2d_wgrad_workspace
-template <typename T>
-static int wgrad_impl(const T* x, const T* dy, float* dw, float* workspace, long ws_bytes, int N, int H, int W, int Ci,
-                      int Co, int kh, int kw, int stride, int pad, int dil, int accumulate, hipStream_t s,
-                      const char* nm) {
-  FAMI_REQUIRE(x && dy && dw && workspace && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
-  if (!geom_ok(kh, kw, stride, pad, dil)) {
-    fami_set_error(nm, "unsupported geometry");
-    return FAMI_ESHAPE;
-  }
-  // stride-1 same-size convolutions of whole 16-channel tiles: linear-address kernel (f32 storage only)
-  const bool lin = std::is_same<T, float>::value && g_wgrad_lin && wgrad_lin_ok(H, W, Ci, Co, kh, kw, stride, pad, dil);
-  const WgradPlan q = wgrad_plan(N, H, W, Ci, Co, kh, kw, stride, pad, dil, !lin ? 0 : (g_wgrad_lin == 1 ? 3 : (g_wgrad_lin == 3 ? 1 : (g_wgrad_lin == 4 ? 2 : 0))));
-  const long need = (long)q.psplit * Co * Ci * kh * kw * (long)sizeof(float);
-  FAMI_REQUIRE(ws_bytes >= need, nm, "workspace too small");
-  FAMI_REQUIRE(q.P < (1L << 31), nm, "size out of range");
-  WgradArgs<T> a;
-  a.x = x; a.dy = dy; a.part = workspace;
-  a.N = N; a.H = H; a.W = W; a.Ci = Ci;
-  a.Ho = out_dim(H, kh, stride, pad, dil); a.Wo = out_dim(W, kw, stride, pad, dil); a.Co = Co;
-  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
-  a.P = (int)q.P; a.chunk = q.chunk; a.ciBlocks = q.ciBlocks; a.coBlocks = q.coBlocks; a.xcd = g_xcd_w; a.prio = g_prio;
-  const long xb = (long)N * H * W * Ci * (long)sizeof(T), yb = q.P * Co * (long)sizeof(T);
-  FAMI_REQUIRE(xb < (1L << 31) && yb < (1L << 31), nm, "tensor >= 2 GiB");
-  a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)yb;
-  if (q.pertap) {
-    const dim3 grid(q.w8 ? q.psplit + (q.psplit + 7) / 8 : q.psplit, q.ciBlocks * q.coBlocks), block(q.w8 ? 512 * q.w8 : kh * kw * 64);
-    const size_t lin_lds = q.w8 == 2 ? (size_t)8 * q.MT * q.NT * 1024 : 0;
-    a.psplit = q.psplit; a.w8 = q.w8;
-    bool ok = false;
-#define FAMI_TCASE(mt, nt)                                                                  \
-  if (q.MT == mt && q.NT == nt) {                                                           \
-    if constexpr (std::is_same<T, float>::value) {                                          \
-      if (lin) {                                                                            \
-        static bool attr = false;                                                           \
-        if (!attr) {                                                                        \
-          (void)hipFuncSetAttribute((const void*)conv_wgrad_taps_lin_f32<T, mt, nt>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * mt * nt * 1024); \
-          attr = true;                                                                      \
-        }                                                                                   \
-        hipLaunchKernelGGL((conv_wgrad_taps_lin_f32<T, mt, nt>), grid, block, lin_lds, s, a); \
-      }                                                                                     \
-      else hipLaunchKernelGGL((conv_wgrad_taps_f32<T, mt, nt>), grid, block, 0, s, a);      \
-    } else {                                                                                \
-      hipLaunchKernelGGL((conv_wgrad_taps_f32<T, mt, nt>), grid, block, 0, s, a);           \
-    }                                                                                       \
-    ok = true;                                                                              \
-  }
-    FAMI_TCASE(1, 1) FAMI_TCASE(1, 2) FAMI_TCASE(1, 3) FAMI_TCASE(1, 4)
-    FAMI_TCASE(2, 1) FAMI_TCASE(2, 2) FAMI_TCASE(2, 3) FAMI_TCASE(2, 4)
-    FAMI_TCASE(3, 1) FAMI_TCASE(3, 2) FAMI_TCASE(3, 3) FAMI_TCASE(3, 4)
-    FAMI_TCASE(4, 1) FAMI_TCASE(4, 2) FAMI_TCASE(4, 3) FAMI_TCASE(4, 4)
-#undef FAMI_TCASE
-    if (!ok) {
-      fami_set_error(nm, "no kernel instance");
-      return FAMI_ESHAPE;
-    }
-    FAMI_CHECK_LAUNCH(nm);
-    launch_reduce_taps(workspace, dw, Co, Ci, kh * kw, q.psplit, accumulate, s);
-    FAMI_CHECK_LAUNCH(nm);
-    return FAMI_OK;
-  }
-  const dim3 grid(q.psplit, kh * kw * q.ciBlocks * q.coBlocks);
-  bool done = false;
-#define FAMI_WCASE(mt, nt)                                                                  \
-  if (q.MT == mt && q.NT == nt) {                                                           \
-    hipLaunchKernelGGL((conv_wgrad_f32<T, mt, nt>), grid, dim3(256), 0, s, a);              \
-    done = true;                                                                            \
-  }
-  FAMI_WCASE(1, 1) FAMI_WCASE(1, 2) FAMI_WCASE(1, 3) FAMI_WCASE(1, 4)
-  FAMI_WCASE(2, 1) FAMI_WCASE(2, 2) FAMI_WCASE(2, 3) FAMI_WCASE(2, 4)
-  FAMI_WCASE(3, 1) FAMI_WCASE(3, 2) FAMI_WCASE(3, 3) FAMI_WCASE(3, 4)
-  FAMI_WCASE(4, 1) FAMI_WCASE(4, 2) FAMI_WCASE(4, 3) FAMI_WCASE(4, 4)
-#undef FAMI_WCASE
-  if (!done) {
-    fami_set_error(nm, "no kernel instance");
-    return FAMI_ESHAPE;
-  }
-  FAMI_CHECK_LAUNCH(nm);
-  launch_reduce_plain(workspace, dw, Co, Ci, kh * kw, q.psplit, accumulate, s);
-  FAMI_CHECK_LAUNCH(nm);
-  return FAMI_OK;
-}
-
-// ---- bf16 implicit GEMM launch
-template <typename H, int MODE, int VEC>
-static int launch_igemm_h(const ConvArgsH& a, int MT, int NT, int KS, int ST, hipStream_t s) {
-  long tiles = fami_cdiv(a.P, MT * 16);
-  if (a.par) {
-    tiles = 0;
-    for (int c = 0; c < 4; ++c) {
-      const long Ha = (c >> 1) ? a.Ho / 2 : (a.Ho + 1) / 2, Wb = (c & 1) ? a.Wo / 2 : (a.Wo + 1) / 2;
-      tiles += fami_cdiv(a.N * Ha * Wb, MT * 16);
-    }
-  }
-  const dim3 grid(fami_cdiv(tiles, 4 / KS), fami_cdiv(a.NTt, NT));
-#define FAMI_CASE(mt, nt, ks)                                                                        \
-  if (MT == mt && NT == nt && KS == ks) {                                                            \
-    if (ST == 3 && mt <= 2) hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 3>), grid, dim3(256), 0, s, a); \
-    else if (ST == 4 && mt <= 2) hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 4>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((conv_igemm_h<H, mt, nt, MODE, VEC, ks, 2>), grid, dim3(256), 0, s, a);   \
-    return 0;                                                                                        \
-  }
-  if constexpr (VEC) {
-#define FAMI_ROW(nt) FAMI_CASE(1, nt, 1) FAMI_CASE(1, nt, 2) FAMI_CASE(1, nt, 4) FAMI_CASE(2, nt, 1) FAMI_CASE(2, nt, 2) FAMI_CASE(2, nt, 4) FAMI_CASE(4, nt, 1)
-    FAMI_ROW(1) FAMI_ROW(2) FAMI_ROW(3) FAMI_ROW(4)
-#undef FAMI_ROW
-  } else {
-    FAMI_CASE(2, 1, 1) FAMI_CASE(2, 2, 1) FAMI_CASE(2, 3, 1) FAMI_CASE(2, 4, 1)
-  }
-#undef FAMI_CASE
-  return -1;
-}
-
-template <typename H>
-static int run_igemm_h(ConvArgsH a, int mode, hipStream_t s, const char* name) {
-  a.xcd = g_xcd < 0 ? 1 : g_xcd;
-  a.par = (mode == 1 && a.sh == 1 && g_par) ? 1 : 0;
-  const int vec = (a.Ci % 8 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
-  int NT = pick_nt(a.NTt);
-  if (NT == 6) NT = 3;
-  if (NT > 4) NT = 4;
-  int MT = 2, KS = 1;
-  if (vec) {
-    // the bf16 kernel is operand-fetch bound (an MFMA needs 2 KiB of fragments): larger register tiles raise the
-    // MFMAs per fetched KiB, split-K restores parallelism on the low-resolution branches
-    const long nblk = fami_cdiv(a.NTt, NT);
-    const long tiles = (long)fami_cdiv(a.P, 16) * nblk;
-    const long iters = (long)a.kh * a.kw * a.KC;
-    // (a two-chunk reduction -- the 64 -> 256 1x1 of stage 1 and the input gradient of its 256 -> 64 twin, 20 frames @96x72 -- is all
-    //  prologue and epilogue: 64-pixel waves instead of 128: forward 38.1 -> 32.6 us, input gradient 38.6 -> 32.2, accumulating 58.4 -> 52.0,
-    //  tools/probes/layer1_1x1_tiles.py)
-    if (tiles >= 16384) MT = iters <= 2 ? 2 : 4;
-    else if (tiles >= 4096) MT = 2;
-    else {
-      MT = 1;
-      if (iters >= 8) KS = tiles < 1024 ? 4 : 2;
-    }
-  }
-  if (vec && g_force_mt) { MT = g_force_mt; NT = g_force_nt ? g_force_nt : NT; KS = g_force_ks ? g_force_ks : 1; }
-  const int ST = g_stages ? g_stages : 2;
-  int rc;
-  if (mode == 0)
-    rc = vec ? launch_igemm_h<H, 0, 1>(a, MT, NT, KS, ST, s) : launch_igemm_h<H, 0, 0>(a, MT, NT, KS, 2, s);
-  else
-    rc = vec ? launch_igemm_h<H, 1, 1>(a, MT, NT, KS, ST, s) : launch_igemm_h<H, 1, 0>(a, MT, NT, KS, 2, s);
-  if (rc != 0) {
-    fami_set_error(name, "no kernel instance for tile shape");
-    return FAMI_ESHAPE;
-  }
-  FAMI_CHECK_LAUNCH(name);
-  return FAMI_OK;
-}
-
-extern "C" {
-
-static int wgrad_f32_entry(const float* x, const float* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
-                           int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                           hipStream_t s, const XBN& xbn);
 int fami_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
                           int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
                           hipStream_t s) {
   return wgrad_f32_entry(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s, xbn_none());
 }
-static int wgrad_f32_entry(const float* x, const float* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
-                           int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                           hipStream_t s, const XBN& xbn) {
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && x && dy && dw && workspace) {
-    // split-product kernel on the bf16 matrix pipe (conv_wgs3.hip)
-    const int G = fami_try_wgrad_s3(x, dy, workspace, ws_bytes, N, H, W, Ci, Co, s, "fami_conv2d_wgrad_f32", xbn);
-    if (G < 0) return G;
-    if (G > 0) {
-      launch_reduce_taps(workspace, dw, Co, Ci, 9, G, accumulate, s);
-      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/reduce");
-      return FAMI_OK;
-    }
-  }
-  if (xbn.on) {
-    fami_set_error("fami_conv2d_wgrad_defer_xbn_f32", "input BatchNorm needs the split-product kernel (ask fami_conv2d_xbn_ok_f32 first)");
-    return FAMI_ESHAPE;
-  }
-  WgradLdsPlan l = g_wgrad_lds_f32 ? wgrad_lds_plan_f32(N, H, W, Ci, Co, kh, kw, stride, pad, dil) : WgradLdsPlan{0};
-  // measured (tools/bench_wgrad.py f32): the staged kernel wins once the channel blocks alone give >= 64 workgroup
-  // columns (384 channels: 136 vs 151 us); below that the per-tap scalar-operand kernel is faster (85 vs 105 us)
-  // ... and the linear-address per-tap kernel beats both wherever it applies (384 channels: 78 vs 103 us)
-  if (g_wgrad_lds_f32 == 2 && l.ok &&
-      (l.ciBlocks * l.coBlocks < 64 || (g_wgrad_lin && wgrad_lin_ok(H, W, Ci, Co, kh, kw, stride, pad, dil))))
-    l.ok = 0;
-  if (l.ok && x && dy && dw && workspace && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
-    const long need = (long)l.G * Co * Ci * 9 * (long)sizeof(float);
-    FAMI_REQUIRE(ws_bytes >= need, "fami_conv2d_wgrad_f32", "workspace too small");
-    WgradLdsArgsF a;
-    a.x = x; a.dy = dy; a.part = workspace;
-    a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.P = N * H * W;
-    a.chunk = l.chunk; a.ciBlocks = l.ciBlocks; a.coBlocks = l.coBlocks; a.xcd = g_xcd_w;
-    a.CiB = 16 * l.CIT; a.CoB = 16 * l.COT; a.xrow = l.xrow; a.yrow = l.yrow; a.xfloats = l.xbytes;
-    const dim3 grid(l.G, l.ciBlocks * l.coBlocks);
-    bool ok = false;
-#define FAMI_WF_CASE(cit, cot)                                                                                        \
-  if (l.CIT == cit && l.COT == cot) {                                                                                 \
-    static bool attr = false;                                                                                         \
-    if (!attr) {                                                                                                      \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad_lds_f32_kernel<cit, cot>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((conv_wgrad_lds_f32_kernel<cit, cot>), grid, dim3(512), l.lds, s, a);                          \
-    ok = true;                                                                                                        \
-  }
-    FAMI_WF_CASE(1, 1) FAMI_WF_CASE(1, 2) FAMI_WF_CASE(1, 3) FAMI_WF_CASE(1, 4) FAMI_WF_CASE(2, 1) FAMI_WF_CASE(2, 2)
-    FAMI_WF_CASE(2, 3) FAMI_WF_CASE(2, 4) FAMI_WF_CASE(3, 1) FAMI_WF_CASE(3, 2) FAMI_WF_CASE(3, 3) FAMI_WF_CASE(3, 4)
-    FAMI_WF_CASE(4, 1) FAMI_WF_CASE(4, 2) FAMI_WF_CASE(4, 3) FAMI_WF_CASE(4, 4)
-#undef FAMI_WF_CASE
-    if (ok) {
-      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/lds");
-      launch_reduce_taps(workspace, dw, Co, Ci, 9, l.G, accumulate, s);
-      FAMI_CHECK_LAUNCH("fami_conv2d_wgrad_f32/reduce");
-      return FAMI_OK;
-    }
-  }
-  return wgrad_impl<float>(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s,
-                           "fami_conv2d_wgrad_f32");
-}
-}  // extern "C"
-
-extern "C" {
 // Deferred slab reduce: the weight-gradient kernel is launched now, its reduce is described in desc_out (a HOST buffer of
 // FAMI_REDUCE_DESC_LONGS longs, opaque) and launched later -- up to 16 at a time -- by fami_wgrad_reduce_batch.  The
 // workspace must stay untouched until then.  Two deferred reduces into the same dw must not share a batch when the
@@ -3301,32 +3526,18 @@ int fami_conv2d_wgrad_defer_f32(const float* x, const float* dy, float* dw, floa
                                 int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
                                 long* desc_out, hipStream_t s) {
   FAMI_REQUIRE(desc_out, "fami_conv2d_wgrad_defer_f32", "null descriptor");
-  ReduceDesc d;
-  d.part = nullptr;
-  g_defer = &d;
-  const int rc = fami_conv2d_wgrad_f32(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s);
-  g_defer = nullptr;
-  if (rc != FAMI_OK) return rc;
-  FAMI_REQUIRE(d.part, "fami_conv2d_wgrad_defer_f32", "no reduce recorded");
-  memcpy(desc_out, &d, sizeof(d));
-  return FAMI_OK;
+  return with_deferred_reduce("fami_conv2d_wgrad_defer_f32", desc_out, [&] {
+    return fami_conv2d_wgrad_f32(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s);
+  });
 }
 int fami_conv2d_wgrad_defer_xbn_f32(const float* z, const float* dy, float* dw, float* workspace, long ws_bytes, int N, int H,
                                     int W, int Ci, int Co, int accumulate, long* desc_out, const float* xmean,
                                     const float* xinvstd, const float* xgamma, const float* xbeta, hipStream_t s) {
   FAMI_REQUIRE(desc_out && xmean && xinvstd && xgamma && xbeta, "fami_conv2d_wgrad_defer_xbn_f32", "bad argument");
-  XBN xb = xbn_none();
-  xb.on = 1; xb.C = Ci; xb.gamma = xgamma; xb.beta = xbeta; xb.mean = const_cast<float*>(xmean);
-  xb.invstd = const_cast<float*>(xinvstd);
-  ReduceDesc d;
-  d.part = nullptr;
-  g_defer = &d;
-  const int rc = wgrad_f32_entry(z, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, 3, 3, 1, 1, 1, accumulate, s, xb);
-  g_defer = nullptr;
-  if (rc != FAMI_OK) return rc;
-  FAMI_REQUIRE(d.part, "fami_conv2d_wgrad_defer_xbn_f32", "no reduce recorded");
-  memcpy(desc_out, &d, sizeof(d));
-  return FAMI_OK;
+  return with_deferred_reduce("fami_conv2d_wgrad_defer_xbn_f32", desc_out, [&] {
+    return wgrad_f32_entry(z, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, 3, 3, 1, 1, 1, accumulate, s,
+                           xbn_wgrad(Ci, xmean, xinvstd, xgamma, xbeta));
+  });
 }
 // conv_pair.h, f32 storage: the split-product input gradient (conv_t5.hip's persistent kernel) and the deferred split-product weight
 // gradient (conv_wgs3.hip) of a 3x3 stride-1 convolution as ONE launch where a combined instance exists (ask
@@ -3336,33 +3547,17 @@ int fami_conv2d_bwd_pair_f32(const float* x, const float* dy, const float* wpd, 
                              long ws_bytes, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil,
                              int acc_dx, int acc_dw, long* desc_out, const float* xmean, const float* xinvstd,
                              const float* xgamma, const float* xbeta, hipStream_t s) {
-  static const char* nm = "fami_conv2d_bwd_pair_f32";
+  const char* const nm = "fami_conv2d_bwd_pair_f32";
   FAMI_REQUIRE(desc_out, nm, "null descriptor");
   XBN xb = xbn_none();
   if (xmean) {
     FAMI_REQUIRE(xinvstd && xgamma && xbeta, nm, "bad argument");
-    xb.on = 1; xb.C = Ci; xb.gamma = xgamma; xb.beta = xbeta; xb.mean = const_cast<float*>(xmean);
-    xb.invstd = const_cast<float*>(xinvstd);
+    xb = xbn_wgrad(Ci, xmean, xinvstd, xgamma, xbeta);
   }
-  PairCapture pc;
-  pc.a.kind = pc.b.kind = 0;
-  ReduceDesc d;
-  d.part = nullptr;
-  fami_pair_capture() = &pc;
-  int rc = conv_dgrad_f32_impl(nm, dy, wpd, nullptr, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dx, epi_none(), s);
-  if (rc == FAMI_OK) {
-    g_defer = &d;
-    rc = wgrad_f32_entry(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dw, s, xb);
-    g_defer = nullptr;
-  }
-  fami_pair_capture() = nullptr;
-  if (rc != FAMI_OK) return rc;
-  FAMI_REQUIRE(d.part, nm, "no reduce recorded");
-  memcpy(desc_out, &d, sizeof(d));
-  const int pr = fami_pair_launch(pc, s);
-  FAMI_REQUIRE(pr >= 0, nm, "a recorded launch has no kernel instance");
-  FAMI_CHECK_LAUNCH(nm);
-  return FAMI_OK;
+  return bwd_pair_run(
+      nm, desc_out, s,
+      [&] { return conv_dgrad_f32_impl(nm, dy, wpd, nullptr, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dx, epi_none(), s); },
+      [&] { return wgrad_f32_entry(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dw, s, xb); });
 }
 // f32 storage: both split-product kernels (conv_t4.hip S3, conv_wgs3.hip) would take the shape
 int fami_conv2d_xbn_ok_f32(int N, int H, int W, int Ci, int Co) {
@@ -3387,173 +3582,8 @@ int fami_wgrad_reduce_batch(const long* descs, int n, hipStream_t s) {
 }
 }  // extern "C"
 
-// 16-bit activations / gradients, fp32 weight gradient
-template <typename HT>
-static int wgrad_h_impl(const char* nm, const HT* x, const HT* dy, float* dw, float* workspace, long ws_bytes, int N,
-                        int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int accumulate,
-                        hipStream_t s, const XBN& xbn = xbn_none()) {
-  if (g_wgrad_lds && x && dy && dw && workspace && kh == kw) {
-    // round-3 kernel (conv_wg16.hip): pipelined staging, padded patch, 8 waves; 1x1 / 3x3, stride 1 / 2, any dilation
-    const int G = fami_try_wgrad16(std::is_same<HT, f16_t>::value ? 1 : 0, x, dy, workspace, ws_bytes, N, H, W, Ci, Co, kh, stride,
-                                   pad, dil, s, nm, xbn);
-    if (G < 0) return G;
-    if (G > 0) {
-      launch_reduce_taps(workspace, dw, Co, Ci, kh * kw, G, accumulate, s);
-      FAMI_CHECK_LAUNCH(nm);
-      return FAMI_OK;
-    }
-  }
-  if (xbn.on) {
-    fami_set_error(nm, "input BatchNorm needs the conv_wg16 kernel (ask fami_conv2d_xbn_ok first)");
-    return FAMI_ESHAPE;
-  }
-  const WgradLdsPlan l = g_wgrad_lds ? wgrad_lds_plan(N, H, W, Ci, Co, kh, kw, stride, pad, dil) : WgradLdsPlan{0};
-  if (l.ok && x && dy && dw && workspace && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
-    const long need = (long)l.G * Co * Ci * 9 * (long)sizeof(float);
-    FAMI_REQUIRE(ws_bytes >= need, nm, "workspace too small");
-    WgradLdsArgs a;
-    a.x = x; a.dy = dy; a.part = workspace;
-    a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.P = N * H * W;
-    a.chunk = l.chunk; a.nsub = l.nsub; a.ciBlocks = l.ciBlocks; a.coBlocks = l.coBlocks; a.xcd = g_xcd_w;
-    a.CiB = 16 * l.CIT; a.CoB = 16 * l.COT; a.xrow = l.xrow; a.yrow = l.yrow; a.xbytes = l.xbytes;
-    const dim3 grid(l.G, l.ciBlocks * l.coBlocks);
-    bool ok = false;
-#define FAMI_WL_CASE(cit, cot)                                                                                     \
-  if (l.CIT == cit && l.COT == cot) {                                                                              \
-    static bool attr = false;                                                                                      \
-    if (!attr) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad_h_kernel<HT, cit, cot>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-      attr = true;                                                                                                 \
-    }                                                                                                              \
-    hipLaunchKernelGGL((conv_wgrad_h_kernel<HT, cit, cot>), grid, dim3(256), l.lds, s, a);                         \
-    ok = true;                                                                                                     \
-  }
-    FAMI_WL_CASE(1, 1) FAMI_WL_CASE(1, 2) FAMI_WL_CASE(1, 3) FAMI_WL_CASE(2, 1) FAMI_WL_CASE(2, 2) FAMI_WL_CASE(2, 3)
-    FAMI_WL_CASE(3, 1) FAMI_WL_CASE(3, 2) FAMI_WL_CASE(3, 3)
-#undef FAMI_WL_CASE
-    if (ok) {
-      FAMI_CHECK_LAUNCH(nm);
-      launch_reduce_taps(workspace, dw, Co, Ci, 9, l.G, accumulate, s);
-      FAMI_CHECK_LAUNCH(nm);
-      return FAMI_OK;
-    }
-  }
-  return wgrad_impl<HT>(x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, accumulate, s, nm);
-}
-
-template <typename HT>
-static int pack_conv_weight_h_impl(const char* nm, const float* w_oihw, HT* wp, int Co, int Ci, int kh, int kw, int mode,
-                                   hipStream_t s) {
-  FAMI_REQUIRE(w_oihw && wp && Co > 0 && Ci > 0 && (mode == 0 || mode == 1), nm, "bad argument");
-  const int kd = mode == 0 ? Ci : Co, nd = mode == 0 ? Co : Ci;
-  const int KC = fami_cdiv(kd, 32), NTt = fami_cdiv(nd, 16);
-  const long total = (long)kh * kw * KC * NTt * 512;
-  hipLaunchKernelGGL(pack_w_h_kernel<HT>, dim3(fami_ew_grid(total)), dim3(256), 0, s, w_oihw, wp, Co, Ci, kh * kw, KC, NTt, mode);
-  FAMI_CHECK_LAUNCH(nm);
-  return FAMI_OK;
-}
-
-// conv_stem.hip: the stem's 3 -> 64 stride-2 convolution with K dense over (tap, channel)
-int fami_try_conv_stem1(int half_kind, const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
-                        int kh, int kw, int stride, int pad, int dil, int NTt, int relu, int accumulate, int out_f32, hipStream_t s,
-                        const char* name, const EpiBN& epi);
-void fami_conv_stem_tune(int on);
-
-// y[N,Ho,Wo,Co] (16-bit, or f32 when out_f32) (=|+=) relu?( conv(x[N,H,W,Ci]) + bias ) ; wp packed with mode 0
-template <typename HT>
-static int conv_fwd_h_impl(const char* nm, const HT* x, const HT* wp, const float* bias, void* y, int N, int H, int W,
-                           int Ci, int Co, int kh, int kw, int stride, int pad, int dil, int relu, int accumulate,
-                           int out_f32, hipStream_t s, const EpiBN& e = epi_none(), const XBN& xbn = xbn_none()) {
-  FAMI_REQUIRE(x && wp && y && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
-  if (!geom_ok(kh, kw, stride, pad, dil)) {
-    fami_set_error(nm, "unsupported geometry");
-    return FAMI_ESHAPE;
-  }
-  if (e.slots && (out_f32 || relu || (Co & 3))) {
-    fami_set_error(nm, "fused BatchNorm statistics need a 16-bit output, no ReLU and Co % 4 == 0");
-    return FAMI_ESHAPE;
-  }
-  ConvArgsH a;
-  a.e = e; a.emode = e.slots ? e.mode : 0;
-  a.x = x; a.wp = wp; a.y = y; a.bias = bias;
-  a.N = N; a.Hi = H; a.Wi = W; a.Ci = Ci;
-  a.Ho = out_dim(H, kh, stride, pad, dil); a.Wo = out_dim(W, kw, stride, pad, dil); a.Co = Co;
-  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
-  a.KC = fami_cdiv(Ci, 32); a.NTt = fami_cdiv(Co, 16); a.relu = relu; a.accumulate = accumulate; a.out_f32 = out_f32;
-  const long P = (long)N * a.Ho * a.Wo;
-  const long xb = (long)N * H * W * Ci * 2, wb = (long)kh * kw * a.KC * a.NTt * 1024;
-  FAMI_REQUIRE(P > 0 && P < (1L << 31) && xb < (1L << 31) && wb < (1L << 31), nm, "tensor >= 2 GiB");
-  a.P = (int)P; a.x_bytes = (unsigned)xb; a.wp_bytes = (unsigned)wb;
-  if (Ci == 3 && !xbn.on) {
-    const int rc = fami_try_conv_stem1(std::is_same<HT, f16_t>::value ? 1 : 0, x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil,
-                                       a.NTt, relu, accumulate, out_f32, s, nm, e);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) {
-    const int rc = try_conv3x3_lds<HT>(x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu, accumulate, out_f32, s, nm, e, xbn);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !e.slots && !xbn.on && g_use_lds != 0) {
-    const int rc = fami_try_conv3x3_t4_dil(std::is_same<HT, f16_t>::value ? 1 : 0, x, wp, bias, y, N, H, W, Ci, Co, a.KC, a.NTt, +1, relu,
-                                           accumulate, out_f32, dil, s, nm);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (xbn.on) {
-    fami_set_error(nm, "input BatchNorm needs the register-blocked 3x3 kernel (ask fami_conv2d_xbn_ok first)");
-    return FAMI_ESHAPE;
-  }
-  return run_igemm_h<HT>(a, 0, s, nm);
-}
-
-// dx[N,H,W,Ci] (=|+=) conv_transpose(dy[N,Ho,Wo,Co]) ; wp packed with mode 1
-template <typename HT>
-static int conv_dgrad_h_impl(const char* nm, const HT* dy, const HT* wp, HT* dx, int N, int H, int W, int Ci, int Co,
-                             int kh, int kw, int stride, int pad, int dil, int accumulate, hipStream_t s,
-                             const EpiBN& e = epi_none()) {
-  FAMI_REQUIRE(dy && wp && dx && N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, nm, "bad argument");
-  if (!geom_ok(kh, kw, stride, pad, dil)) {
-    fami_set_error(nm, "unsupported geometry");
-    return FAMI_ESHAPE;
-  }
-  if (e.slots && (Ci & 3)) {
-    fami_set_error(nm, "fused BatchNorm statistics need Ci % 4 == 0");
-    return FAMI_ESHAPE;
-  }
-  ConvArgsH a;
-  a.e = e; a.emode = e.slots ? e.mode : 0;
-  a.x = dy; a.wp = wp; a.y = dx; a.bias = nullptr;
-  a.N = N; a.Hi = out_dim(H, kh, stride, pad, dil); a.Wi = out_dim(W, kw, stride, pad, dil); a.Ci = Co;
-  a.Ho = H; a.Wo = W; a.Co = Ci;
-  a.kh = kh; a.kw = kw; a.sh = stride == 2 ? 1 : 0; a.pad = pad; a.dil = dil;
-  a.KC = fami_cdiv(Co, 32); a.NTt = fami_cdiv(Ci, 16); a.relu = 0; a.accumulate = accumulate; a.out_f32 = 0;
-  const long P = (long)N * H * W;
-  const long xb = (long)N * a.Hi * a.Wi * Co * 2, wb = (long)kh * kw * a.KC * a.NTt * 1024;
-  FAMI_REQUIRE(P > 0 && P < (1L << 31) && xb < (1L << 31) && wb < (1L << 31), nm, "tensor >= 2 GiB");
-  a.P = (int)P; a.x_bytes = (unsigned)xb; a.wp_bytes = (unsigned)wb;
-  if (kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1) {
-    const int rc = try_conv3x3_lds<HT>(dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0, accumulate, 0, s, nm, e);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  if (kh == 3 && kw == 3 && stride == 1 && pad == dil && dil > 1 && !e.slots && g_use_lds != 0) {
-    const int rc = fami_try_conv3x3_t4_dil(std::is_same<HT, f16_t>::value ? 1 : 0, dy, wp, nullptr, dx, N, H, W, Co, Ci, a.KC, a.NTt, -1, 0,
-                                           accumulate, 0, dil, s, nm);
-    if (rc != 0) return rc < 0 ? rc : FAMI_OK;
-  }
-  return run_igemm_h<HT>(a, 1, s, nm);
-}
-
+// ---- C ABI: the 16-bit entry points, one-line forwards to the templates above
 extern "C" {
-
-// every weight image of a step in one launch.  desc: device array of n records {long src_elem_off, long dst_elem_off,
-// int Co, int Ci, int taps, int mode} (32 bytes each); params = fp32 parameter arena, packed = destination arena.
-int fami_pack_conv_weights_batch_f32(const float* params, float* packed, const void* desc, int n, hipStream_t s) {
-  FAMI_REQUIRE(params && packed && desc && n > 0 && n < 65536, "fami_pack_conv_weights_batch_f32", "bad argument");
-  hipLaunchKernelGGL(pack_w_batch_kernel<float>, dim3(48, n), dim3(256), 0, s, params, packed, reinterpret_cast<const PackDesc*>(desc));
-  FAMI_CHECK_LAUNCH("fami_pack_conv_weights_batch_f32");
-  fami_pack_split_batch(params, packed, desc, n, s);      // the split images behind the 3x3 fragment images (conv_t5.hip)
-  FAMI_CHECK_LAUNCH("fami_pack_conv_weights_batch_f32/split");
-  return FAMI_OK;
-}
 
 // the packed 16-bit image has the same geometry for bf16 and fp16
 long fami_packed_weight_elems_bf16(int Co, int Ci, int kh, int kw, int mode) {
@@ -3574,24 +3604,11 @@ long fami_packed_weight_elems_f16(int Co, int Ci, int kh, int kw, int mode) {
   int fami_conv2d_wgrad_defer_##sfx(const HT* x, const HT* dy, float* dw, float* workspace, long ws_bytes, int N,      \
                                     int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int dil,        \
                                     int accumulate, long* desc_out, hipStream_t s) {                                   \
-    FAMI_REQUIRE(desc_out, "fami_conv2d_wgrad_defer_" #sfx, "null descriptor");                                        \
-    ReduceDesc d;                                                                                                      \
-    d.part = nullptr;                                                                                                  \
-    g_defer = &d;                                                                                                      \
-    const int rc = wgrad_h_impl<HT>("fami_conv2d_wgrad_defer_" #sfx, x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co,  \
-                                    kh, kw, stride, pad, dil, accumulate, s);                                          \
-    g_defer = nullptr;                                                                                                 \
-    if (rc != FAMI_OK) return rc;                                                                                      \
-    FAMI_REQUIRE(d.part, "fami_conv2d_wgrad_defer_" #sfx, "no reduce recorded");                                       \
-    memcpy(desc_out, &d, sizeof(d));                                                                                   \
-    return FAMI_OK;                                                                                                    \
+    return wgrad_defer_h<HT>("fami_conv2d_wgrad_defer_" #sfx, x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, \
+                             stride, pad, dil, accumulate, desc_out, s);                                               \
   }                                                                                                                    \
   int fami_pack_conv_weights_batch_##sfx(const float* params, HT* packed, const void* desc, int n, hipStream_t s) {    \
-    FAMI_REQUIRE(params && packed && desc && n > 0 && n < 65536, "fami_pack_conv_weights_batch_" #sfx, "bad argument");\
-    hipLaunchKernelGGL(pack_w_batch_kernel<HT>, dim3(48, n), dim3(256), 0, s, params, packed,                          \
-                       reinterpret_cast<const PackDesc*>(desc));                                                       \
-    FAMI_CHECK_LAUNCH("fami_pack_conv_weights_batch_" #sfx);                                                           \
-    return FAMI_OK;                                                                                                    \
+    return pack_conv_weights_batch_h<HT>("fami_pack_conv_weights_batch_" #sfx, params, packed, desc, n, s);            \
   }                                                                                                                    \
   int fami_pack_conv_weight_##sfx(const float* w_oihw, HT* wp, int Co, int Ci, int kh, int kw, int mode,               \
                                   hipStream_t s) {                                                                     \
@@ -3608,135 +3625,53 @@ long fami_packed_weight_elems_f16(int Co, int Ci, int kh, int kw, int mode) {
     return conv_dgrad_h_impl<HT>("fami_conv2d_dgrad_" #sfx, dy, wp, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil,     \
                                  accumulate, s);                                                                       \
   }                                                                                                                    \
-  /* BatchNorm (+ReLU) of the INPUT applied while it is staged (XBN, conv_epi.h): x is the pre-normalisation tensor z.  */ \
-  /* fwd: statistics of z come from xslots (filled by fami_conv2d_fwd_stats_*), mean / invstd / running statistics are */ \
-  /* published; slots / pivot_src (optional) request the statistics of y for the BatchNorm that follows.               */ \
   int fami_conv2d_fwd_xbn_##sfx(const HT* z, const HT* wp, const float* bias, HT* y, int N, int H, int W, int Ci,      \
                                 int Co, void* slots, const float* pivot_src, const void* xslots, long xP,             \
                                 const float* xgamma, const float* xbeta, float* xmean, float* xinvstd,                 \
                                 float* xrunning_mean, float* xrunning_var, float xmomentum, float xeps,                \
                                 hipStream_t s) {                                                                       \
-    FAMI_REQUIRE(xslots && xgamma && xbeta && xmean && xinvstd && xP > 0, "fami_conv2d_fwd_xbn_" #sfx, "bad argument");\
-    EpiBN e = epi_none();                                                                                              \
-    if (slots) {                                                                                                       \
-      e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;  \
-    }                                                                                                                  \
-    XBN xb = xbn_none();                                                                                               \
-    xb.on = 1; xb.slots = reinterpret_cast<const double*>(xslots); xb.ns = bn_slots(Ci); xb.C = Ci; xb.P = xP;         \
-    xb.gamma = xgamma; xb.beta = xbeta; xb.mean = xmean; xb.invstd = xinvstd; xb.running_mean = xrunning_mean;         \
-    xb.running_var = xrunning_var; xb.momentum = xmomentum; xb.eps = xeps;                                             \
-    return conv_fwd_h_impl<HT>("fami_conv2d_fwd_xbn_" #sfx, z, wp, bias, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0, 0,   \
-                               s, e, xb);                                                                              \
+    return fwd_xbn_h<HT>("fami_conv2d_fwd_xbn_" #sfx, z, wp, bias, y, N, H, W, Ci, Co, slots, pivot_src, xslots, xP,   \
+                         xgamma, xbeta, xmean, xinvstd, xrunning_mean, xrunning_var, xmomentum, xeps, s);              \
   }                                                                                                                    \
-  /* Round 6: the same BatchNorm + ReLU of the input INSIDE the convolution's launch, with the normalised tensor written to   */ \
-  /* a_out as well (the weight-resident 48-channel kernel transforms its patch in LDS and stores the rows it owns): one launch */ \
-  /* and one read of z per BasicBlock less than fami_bn_apply_slots_* + fami_conv2d_fwd_stats_*, bit for bit their results.     */ \
-  /* Ask fami_conv2d_fwd_bnin_ok first.                                                                                          */ \
   int fami_conv2d_fwd_bnin_##sfx(const HT* z, const HT* wp, const float* bias, HT* y, HT* a_out, int N, int H, int W,  \
                                  int Ci, int Co, void* slots, const float* pivot_src, const void* xslots, long xP,     \
                                  const float* xgamma, const float* xbeta, float* xmean, float* xinvstd,                \
                                  float* xrunning_mean, float* xrunning_var, float xmomentum, float xeps,               \
                                  hipStream_t s) {                                                                      \
-    static const char* nm = "fami_conv2d_fwd_bnin_" #sfx;                                                              \
-    FAMI_REQUIRE(a_out && xslots && xgamma && xbeta && xmean && xinvstd && xP > 0, nm, "bad argument");                \
-    if (!fami_conv2d_fwd_bnin_ok(N, H, W, Ci, Co)) {                                                                   \
-      fami_set_error(nm, "no kernel applies the input BatchNorm in its launch for this shape (ask fami_conv2d_fwd_bnin_ok)"); \
-      return FAMI_ESHAPE;                                                                                              \
-    }                                                                                                                  \
-    EpiBN e = epi_none();                                                                                              \
-    if (slots) {                                                                                                       \
-      e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;  \
-    }                                                                                                                  \
-    XBN xb = xbn_none();                                                                                               \
-    xb.on = 1; xb.slots = reinterpret_cast<const double*>(xslots); xb.ns = bn_slots(Ci); xb.C = Ci; xb.P = xP;         \
-    xb.gamma = xgamma; xb.beta = xbeta; xb.mean = xmean; xb.invstd = xinvstd; xb.running_mean = xrunning_mean;         \
-    xb.running_var = xrunning_var; xb.momentum = xmomentum; xb.eps = xeps; xb.out = a_out;                             \
-    return conv_fwd_h_impl<HT>(nm, z, wp, bias, y, N, H, W, Ci, Co, 3, 3, 1, 1, 1, 0, 0, 0, s, e, xb);                 \
+    return fwd_bnin_h<HT>("fami_conv2d_fwd_bnin_" #sfx, z, wp, bias, y, a_out, N, H, W, Ci, Co, slots, pivot_src,      \
+                          xslots, xP, xgamma, xbeta, xmean, xinvstd, xrunning_mean, xrunning_var, xmomentum, xeps, s); \
   }                                                                                                                    \
   int fami_conv2d_wgrad_defer_xbn_##sfx(const HT* z, const HT* dy, float* dw, float* workspace, long ws_bytes, int N,  \
                                         int H, int W, int Ci, int Co, int accumulate, long* desc_out,                  \
                                         const float* xmean, const float* xinvstd, const float* xgamma,                 \
                                         const float* xbeta, hipStream_t s) {                                           \
-    FAMI_REQUIRE(desc_out && xmean && xinvstd && xgamma && xbeta, "fami_conv2d_wgrad_defer_xbn_" #sfx, "bad argument");\
-    XBN xb = xbn_none();                                                                                               \
-    xb.on = 1; xb.C = Ci; xb.gamma = xgamma; xb.beta = xbeta; xb.mean = const_cast<float*>(xmean);                     \
-    xb.invstd = const_cast<float*>(xinvstd);                                                                           \
-    ReduceDesc d;                                                                                                      \
-    d.part = nullptr;                                                                                                  \
-    g_defer = &d;                                                                                                      \
-    const int rc = wgrad_h_impl<HT>("fami_conv2d_wgrad_defer_xbn_" #sfx, z, dy, dw, workspace, ws_bytes, N, H, W, Ci,  \
-                                    Co, 3, 3, 1, 1, 1, accumulate, s, xb);                                             \
-    g_defer = nullptr;                                                                                                 \
-    if (rc != FAMI_OK) return rc;                                                                                      \
-    FAMI_REQUIRE(d.part, "fami_conv2d_wgrad_defer_xbn_" #sfx, "no reduce recorded");                                   \
-    memcpy(desc_out, &d, sizeof(d));                                                                                   \
-    return FAMI_OK;                                                                                                    \
+    return wgrad_defer_xbn_h<HT>("fami_conv2d_wgrad_defer_xbn_" #sfx, z, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, \
+                                 accumulate, desc_out, xmean, xinvstd, xgamma, xbeta, s);                              \
   }                                                                                                                    \
-  /* fused BatchNorm statistics, see the _f32 forms */                                                                \
   int fami_conv2d_fwd_stats_##sfx(const HT* x, const HT* wp, const float* bias, HT* y, int N, int H, int W, int Ci,    \
                                   int Co, int kh, int kw, int stride, int pad, int dil, void* slots,                   \
                                   const float* pivot_src, hipStream_t s) {                                             \
-    FAMI_REQUIRE(slots, "fami_conv2d_fwd_stats_" #sfx, "null slots");                                                  \
-    EpiBN e = epi_none();                                                                                              \
-    e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;    \
-    return conv_fwd_h_impl<HT>("fami_conv2d_fwd_stats_" #sfx, x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad,    \
-                               dil, 0, 0, 0, s, e);                                                                    \
+    return fwd_stats_h<HT>("fami_conv2d_fwd_stats_" #sfx, x, wp, bias, y, N, H, W, Ci, Co, kh, kw, stride, pad, dil,   \
+                           slots, pivot_src, s);                                                                       \
   }                                                                                                                    \
   int fami_conv2d_dgrad_bnstats_##sfx(const HT* dy, const HT* wp, HT* dx, int N, int H, int W, int Ci, int Co,         \
                                       int kh, int kw, int stride, int pad, int dil, int accumulate, const HT* z,       \
                                       const HT* yrelu, const float* mean, const float* invstd, const float* gamma,     \
                                       const float* beta, int relu, void* slots, hipStream_t s) {                       \
-    FAMI_REQUIRE(slots && z && mean && invstd && gamma && beta && (relu != 1 || yrelu) && relu >= 0 && relu <= 2,      \
-                 "fami_conv2d_dgrad_bnstats_" #sfx, "bad argument");                                                   \
-    EpiBN e = epi_none();                                                                                              \
-    e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Ci); e.mode = 2; e.relu = relu; e.C = Ci;              \
-    e.z = z; e.yr = yrelu; e.mean = mean; e.invstd = invstd; e.gamma = gamma; e.beta = beta;                           \
-    return conv_dgrad_h_impl<HT>("fami_conv2d_dgrad_bnstats_" #sfx, dy, wp, dx, N, H, W, Ci, Co, kh, kw, stride, pad,  \
-                                 dil, accumulate, s, e);                                                               \
-  }
-/* conv_pair.h: input gradient (optionally with the backward-statistics epilogue of fami_conv2d_dgrad_bnstats_*: slots != NULL)   */
-/* and deferred weight gradient of one 3x3 stride-1 convolution as ONE launch where a combined instance exists (ask            */
-/* fami_conv2d_bwd_pair_ok), as the two single launches otherwise.  Results are bitwise those of the two-call form.            */
-#define FAMI_CONV_PAIR_ABI(sfx, HT)                                                                                    \
+    return dgrad_bnstats_h<HT>("fami_conv2d_dgrad_bnstats_" #sfx, dy, wp, dx, N, H, W, Ci, Co, kh, kw, stride, pad,    \
+                               dil, accumulate, z, yrelu, mean, invstd, gamma, beta, relu, slots, s);                  \
+  }                                                                                                                    \
   int fami_conv2d_bwd_pair_##sfx(const HT* x, const HT* dy, const HT* wpd, HT* dx, float* dw, float* workspace,        \
                                  long ws_bytes, int N, int H, int W, int Ci, int Co, int kh, int kw, int stride,       \
                                  int pad, int dil, int acc_dx, int acc_dw, long* desc_out, const HT* z,                \
                                  const HT* yrelu, const float* mean, const float* invstd, const float* gamma,          \
                                  const float* beta, int relu, void* slots, hipStream_t s) {                            \
-    static const char* nm = "fami_conv2d_bwd_pair_" #sfx;                                                              \
-    FAMI_REQUIRE(desc_out, nm, "null descriptor");                                                                     \
-    EpiBN e = epi_none();                                                                                              \
-    if (slots) {                                                                                                       \
-      FAMI_REQUIRE(z && mean && invstd && gamma && beta && (relu != 1 || yrelu) && relu >= 0 && relu <= 2, nm,         \
-                   "bad argument");                                                                                    \
-      e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Ci); e.mode = 2; e.relu = relu; e.C = Ci;            \
-      e.z = z; e.yr = yrelu; e.mean = mean; e.invstd = invstd; e.gamma = gamma; e.beta = beta;                         \
-    }                                                                                                                  \
-    PairCapture pc;                                                                                                    \
-    pc.a.kind = pc.b.kind = 0;                                                                                         \
-    ReduceDesc d;                                                                                                      \
-    d.part = nullptr;                                                                                                  \
-    fami_pair_capture() = &pc;                                                                                         \
-    int rc = conv_dgrad_h_impl<HT>(nm, dy, wpd, dx, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dx, s, e);          \
-    if (rc == FAMI_OK) {                                                                                               \
-      g_defer = &d;                                                                                                    \
-      rc = wgrad_h_impl<HT>(nm, x, dy, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh, kw, stride, pad, dil, acc_dw, s); \
-      g_defer = nullptr;                                                                                               \
-    }                                                                                                                  \
-    fami_pair_capture() = nullptr;                                                                                     \
-    if (rc != FAMI_OK) return rc;                                                                                      \
-    FAMI_REQUIRE(d.part, nm, "no reduce recorded");                                                                    \
-    memcpy(desc_out, &d, sizeof(d));                                                                                   \
-    const int pr = fami_pair_launch(pc, s);                                                                            \
-    FAMI_REQUIRE(pr >= 0, nm, "a recorded launch has no kernel instance");                                             \
-    FAMI_CHECK_LAUNCH(nm);                                                                                             \
-    return FAMI_OK;                                                                                                    \
+    return bwd_pair_h<HT>("fami_conv2d_bwd_pair_" #sfx, x, dy, wpd, dx, dw, workspace, ws_bytes, N, H, W, Ci, Co, kh,  \
+                          kw, stride, pad, dil, acc_dx, acc_dw, desc_out, z, yrelu, mean, invstd, gamma, beta, relu,   \
+                          slots, s);                                                                                   \
   }
 FAMI_CONV_H_ABI(bf16, bf16_t)
 FAMI_CONV_H_ABI(f16, f16_t)
-FAMI_CONV_PAIR_ABI(bf16, bf16_t)
-FAMI_CONV_PAIR_ABI(f16, f16_t)
 #undef FAMI_CONV_H_ABI
-#undef FAMI_CONV_PAIR_ABI
 
 }  // extern "C"

@@ -28,6 +28,25 @@ static inline EpiBN epi_none() {
   e.mean = e.invstd = e.gamma = e.beta = nullptr;
   return e;
 }
+// mode 1: statistics of the forward output y [.., Co] into `slots` (null: plain epilogue)
+static inline EpiBN epi_fwd_stats(void* slots, int Co, const float* pivot_src) {
+  EpiBN e = epi_none();
+  if (!slots) return e;
+  e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Co); e.mode = 1; e.C = Co; e.pivot_src = pivot_src;
+  return e;
+}
+// mode 2: what an entry point must hold before it asks for the backward statistics, and the epilogue itself (dx has Ci channels)
+static inline bool epi_bwd_stats_ok(const void* z, const void* yrelu, const float* mean, const float* invstd, const float* gamma,
+                                    const float* beta, int relu) {
+  return z && mean && invstd && gamma && beta && (relu != 1 || yrelu) && relu >= 0 && relu <= 2;
+}
+static inline EpiBN epi_bwd_stats(void* slots, int Ci, const void* z, const void* yrelu, const float* mean, const float* invstd,
+                                  const float* gamma, const float* beta, int relu) {
+  EpiBN e = epi_none();
+  e.slots = reinterpret_cast<double*>(slots); e.ns = bn_slots(Ci); e.mode = 2; e.relu = relu; e.C = Ci;
+  e.z = z; e.yr = yrelu; e.mean = mean; e.invstd = invstd; e.gamma = gamma; e.beta = beta;
+  return e;
+}
 // The EpiBN block of a kernel's argument struct, read in the EPILOGUE through the kernarg segment pointer instead of
 // through the by-value parameter: the compiler preloads every referenced kernel argument into SGPRs at the top of the
 // kernel and keeps it there (+28 SGPRs through the main loop, one resident workgroup per CU less on the dgrad form).
@@ -73,6 +92,21 @@ static inline XBN xbn_none() {
   XBN x;
   x.slots = nullptr; x.gamma = x.beta = nullptr; x.mean = x.invstd = x.running_mean = x.running_var = nullptr;
   x.P = 0; x.momentum = 0.f; x.eps = 0.f; x.C = 0; x.ns = 0; x.on = 0; x.out = nullptr;
+  return x;
+}
+// forward: z [.., Ci] with its statistics in xslots, taken over xP pixels; out (optional): the normalised tensor is stored too
+static inline XBN xbn_fwd(const void* xslots, long xP, int Ci, const float* gamma, const float* beta, float* mean, float* invstd,
+                          float* running_mean, float* running_var, float momentum, float eps, void* out = nullptr) {
+  XBN x = xbn_none();
+  x.on = 1; x.slots = reinterpret_cast<const double*>(xslots); x.ns = bn_slots(Ci); x.C = Ci; x.P = xP;
+  x.gamma = gamma; x.beta = beta; x.mean = mean; x.invstd = invstd; x.running_mean = running_mean;
+  x.running_var = running_var; x.momentum = momentum; x.eps = eps; x.out = out;
+  return x;
+}
+// weight gradient: mean / invstd are read, never written (the struct's pointers are non-const for the forward form)
+static inline XBN xbn_wgrad(int Ci, const float* mean, const float* invstd, const float* gamma, const float* beta) {
+  XBN x = xbn_none();
+  x.on = 1; x.C = Ci; x.gamma = gamma; x.beta = beta; x.mean = const_cast<float*>(mean); x.invstd = const_cast<float*>(invstd);
   return x;
 }
 // scale / shift of channel c into (sc, sf); forward form also publishes mean / invstd / running statistics when `publish`.

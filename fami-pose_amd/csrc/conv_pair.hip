@@ -103,20 +103,12 @@ static void pair_launch_one(const PairCapture& c, const PairGeo& g, unsigned blo
   if constexpr (K == 6) {
     ConvT6Args a;
     memcpy(&a, c.a.args, sizeof(a));
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)bwd_pair_t6_kernel<HT, MT, EX, ACC, EM, KS, CIT, COT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
+    fami_lds_limit<bwd_pair_t6_kernel<HT, MT, EX, ACC, EM, KS, CIT, COT>>(160 * 1024);
     hipLaunchKernelGGL((bwd_pair_t6_kernel<HT, MT, EX, ACC, EM, KS, CIT, COT>), dim3(blocks), dim3(T6_THREADS), lds, s, a, b, g);
   } else {
     ConvT7Args a;
     memcpy(&a, c.a.args, sizeof(a));
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)bwd_pair_t7_kernel<HT, SG, NT, MT, EX, ACC, EM, KS, CIT, COT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
+    fami_lds_limit<bwd_pair_t7_kernel<HT, SG, NT, MT, EX, ACC, EM, KS, CIT, COT>>(160 * 1024);
     hipLaunchKernelGGL((bwd_pair_t7_kernel<HT, SG, NT, MT, EX, ACC, EM, KS, CIT, COT>), dim3(blocks), dim3(T6_THREADS), lds, s, a, b, g);
   }
 }
@@ -156,11 +148,7 @@ static bool pair_launch_f32(const PairCapture& c, const PairGeo& g, unsigned blo
   memcpy(&b, c.b.args, sizeof(b));
 #define X(nt, cit, cot, nys)                                                                                                         \
   if (c.a.v[0] == nt && c.b.v[0] == cit && c.b.v[1] == cot && c.b.v[2] == nys) {                                                    \
-    static bool attr = false;                                                                                                        \
-    if (!attr) {                                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)bwd_pair_t5_kernel<nt, cit, cot, nys>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                                   \
-    }                                                                                                                                \
+    fami_lds_limit<bwd_pair_t5_kernel<nt, cit, cot, nys>>(160 * 1024);                                                    \
     hipLaunchKernelGGL((bwd_pair_t5_kernel<nt, cit, cot, nys>), dim3(blocks), dim3(T5_THREADS), lds, s, a, b, g);                    \
     return true;                                                                                                                     \
   }

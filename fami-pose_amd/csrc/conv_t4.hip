@@ -586,12 +586,11 @@ static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, v
       const size_t lds = 2 * ((size_t)a.patch_bytes + (size_t)3 * 9 * NT * 16 * T4_S3_ROW) + (xbn.on ? (size_t)2 * Ci * sizeof(float) : 0);
       const dim3 grid(N * a.bands, cblocks);
       const int PMp = (int)((npos * 4 + 255) / 256);
-      static bool attr4 = false, attr6 = false;
       if (PMp <= 4) {
-        if (!attr4) { (void)hipFuncSetAttribute((const void*)conv3x3_t4_kernel<float, 3, 4, true, 8, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap); attr4 = true; }
+        fami_lds_limit<conv3x3_t4_kernel<float, 3, 4, true, 8, 2, true>>((int)lds_cap);
         hipLaunchKernelGGL((conv3x3_t4_kernel<float, 3, 4, true, 8, 2, true>), grid, dim3(512), lds, s, a);
       } else {
-        if (!attr6) { (void)hipFuncSetAttribute((const void*)conv3x3_t4_kernel<float, 3, 6, true, 8, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap); attr6 = true; }
+        fami_lds_limit<conv3x3_t4_kernel<float, 3, 6, true, 8, 2, true>>((int)lds_cap);
         hipLaunchKernelGGL((conv3x3_t4_kernel<float, 3, 6, true, 8, 2, true>), grid, dim3(512), lds, s, a);
       }
       hipError_t err = hipGetLastError();
@@ -643,11 +642,7 @@ static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, v
   bool ok = false;
 #define FAMI_T4S3_CASE(nt, pm, mt)                                                                                        \
   if (NT == nt && MTs == mt && PM <= pm && !ok) {                                                                         \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t4_kernel<float, nt, pm, true, 8, mt>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t4_kernel<float, nt, pm, true, 8, mt>>((int)lds_cap);                                          \
     hipLaunchKernelGGL((conv3x3_t4_kernel<float, nt, pm, true, 8, mt>), grid, dim3(WVs * 64), lds, s, a);                 \
     ok = true;                                                                                                            \
   }
@@ -718,11 +713,7 @@ static int try_conv3x3_t4(const void* x, const void* wp, const float* bias, void
   bool ok = false;
 #define FAMI_T4_CASE(nt, pm)                                                                                              \
   if (NT == nt && PM <= pm && !ok) {                                                                                      \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t4_kernel<HT, nt, pm>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t4_kernel<HT, nt, pm>>(100 * 1024);                                                            \
     hipLaunchKernelGGL((conv3x3_t4_kernel<HT, nt, pm>), grid, dim3(T4_THREADS), lds, s, a);                               \
     ok = true;                                                                                                            \
   }

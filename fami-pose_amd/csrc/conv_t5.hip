@@ -184,11 +184,7 @@ static int t5_dispatch(const ConvT5Args& a, int G, size_t lds, int NT, hipStream
   bool ok = false;
 #define FAMI_T5_CASE(nt)                                                                                                  \
   if (NT == nt) {                                                                                                         \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t5_kernel<HT, nt, S3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t5_kernel<HT, nt, S3>>(160 * 1024);                                                            \
     hipLaunchKernelGGL((conv3x3_t5_kernel<HT, nt, S3>), dim3(G), dim3(T5_THREADS), lds, s, a);                            \
     ok = true;                                                                                                            \
   }

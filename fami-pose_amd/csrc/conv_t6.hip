@@ -90,11 +90,7 @@ static int t6_dispatch(const ConvT6Args& a, dim3 grid, size_t lds, int MT, int e
   if (xb) {      // the input-BatchNorm instances (forward: never accumulating, no backward-statistics epilogue)
 #define FAMI_T6X_CASE(mt, ex, em)                                                                                         \
   if (!ok && MT == mt && ex_ == ex && !acc_ && a.emode == em) {                                                           \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t6_kernel<HT, 6, 3, mt, ex, false, em, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t6_kernel<HT, 6, 3, mt, ex, false, em, true>>(160 * 1024);                                     \
     hipLaunchKernelGGL((conv3x3_t6_kernel<HT, 6, 3, mt, ex, false, em, true>), grid, dim3(T6_THREADS), lds, s, a);        \
     ok = true;                                                                                                            \
   }
@@ -105,11 +101,7 @@ static int t6_dispatch(const ConvT6Args& a, dim3 grid, size_t lds, int MT, int e
   }
 #define FAMI_T6_CASE(mt, ex, ac, em)                                                                                      \
   if (!ok && MT == mt && ex_ == ex && acc_ == ac && a.emode == em) {                                                   \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t6_kernel<HT, 6, 3, mt, ex, ac, em>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t6_kernel<HT, 6, 3, mt, ex, ac, em>>(160 * 1024);                                              \
     hipLaunchKernelGGL((conv3x3_t6_kernel<HT, 6, 3, mt, ex, ac, em>), grid, dim3(T6_THREADS), lds, s, a);                 \
     ok = true;                                                                                                            \
   }
@@ -200,11 +192,7 @@ static int t7_dispatch(const ConvT7Args& a, dim3 grid, size_t lds, int SG, int M
   bool ok = false;
 #define FAMI_T7_CASE_G(sg, nt, mt, ex, ac, em)                                                                            \
   if (!ok && SG == sg && MT == mt && EX == ex && acc_ == ac && a.emode == em) {                                        \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv3x3_t7_kernel<HT, sg, nt, mt, ex, ac, em>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv3x3_t7_kernel<HT, sg, nt, mt, ex, ac, em>>(160 * 1024);                                            \
     hipLaunchKernelGGL((conv3x3_t7_kernel<HT, sg, nt, mt, ex, ac, em>), grid, dim3(T6_THREADS), lds, s, a);               \
     ok = true;                                                                                                            \
   }

@@ -738,11 +738,7 @@ static int wg16_launch(const Wg16Plan& q, const void* x, const void* dy, float* 
   bool ok = false;
 #define FAMI_WG16_CASE(cit, cot, TP)                                                                                    \
   if (q.CIT == cit && q.COT == cot && q.taps == TP) {                                                                   \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad16_kernel<HT, cit, cot, TP>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv_wgrad16_kernel<HT, cit, cot, TP>>(152 * 1024);                                                    \
     hipLaunchKernelGGL((conv_wgrad16_kernel<HT, cit, cot, TP>), grid, dim3(WG16_THREADS), q.lds, s, a);                 \
     ok = true;                                                                                                            \
   }
@@ -760,12 +756,8 @@ static int wg6_dispatch(const Wg6Args& a, dim3 grid, size_t lds, int half_kind, 
   bool ok6 = false;
 #define FAMI_WG6_CASE(ks, cit, cot, xj)                                                                                   \
   if (!ok6 && KS == ks && CIT == cit && COT == cot && XJ == xj) {                                                         \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad6_kernel<bf16_t, ks, cit, cot, xj>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad6_kernel<f16_t, ks, cit, cot, xj>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv_wgrad6_kernel<bf16_t, ks, cit, cot, xj>>(160 * 1024);                                             \
+    fami_lds_limit<conv_wgrad6_kernel<f16_t, ks, cit, cot, xj>>(160 * 1024);                                              \
     if (half_kind == 1) hipLaunchKernelGGL((conv_wgrad6_kernel<f16_t, ks, cit, cot, xj>), grid, dim3(WG16_THREADS), lds, s, a);         \
     else hipLaunchKernelGGL((conv_wgrad6_kernel<bf16_t, ks, cit, cot, xj>), grid, dim3(WG16_THREADS), lds, s, a);                       \
     ok6 = true;                                                                                                           \
@@ -800,12 +792,8 @@ int fami_try_wgrad16(int half_kind, const void* x, const void* dy, float* part, 
       WgsArgs a;
       a.x = x; a.dy = dy; a.part = part; a.N = N; a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
       a.UR = qs.UR; a.upf = qs.upf; a.nunits = qs.nunits; a.NU = (int)qs.NU;
-      static bool attrs = false;
-      if (!attrs) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_stem_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_stem_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attrs = true;
-      }
+      fami_lds_limit<conv_wgrad_stem_kernel<bf16_t>>(160 * 1024);
+      fami_lds_limit<conv_wgrad_stem_kernel<f16_t>>(160 * 1024);
       const size_t ldss = (size_t)2 * (288 * 64 + 288 * 128);
       if (half_kind == 1) hipLaunchKernelGGL((conv_wgrad_stem_kernel<f16_t>), dim3(qs.G), dim3(WG16_THREADS), ldss, s, a);
       else hipLaunchKernelGGL((conv_wgrad_stem_kernel<bf16_t>), dim3(qs.G), dim3(WG16_THREADS), ldss, s, a);
@@ -823,12 +811,8 @@ int fami_try_wgrad16(int half_kind, const void* x, const void* dy, float* part, 
       Wg1Args a;
       a.x = x; a.dy = dy; a.part = part; a.P = (long)N * H * W; a.Ci = Ci; a.Co = Co; a.coBlocks = Co / 64;
       a.nunits = q1.nunits; a.NU = (int)q1.NU;
-      static bool attr1 = false;
-      if (!attr1) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad1_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_wgrad1_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr1 = true;
-      }
+      fami_lds_limit<conv_wgrad1_kernel<bf16_t>>(160 * 1024);
+      fami_lds_limit<conv_wgrad1_kernel<f16_t>>(160 * 1024);
       const dim3 grid1(q1.G, q1.blocks);
       const size_t lds1 = (size_t)4 * WG1_I * 1024;
       if (half_kind == 1) hipLaunchKernelGGL((conv_wgrad1_kernel<f16_t>), grid1, dim3(WG16_THREADS), lds1, s, a);

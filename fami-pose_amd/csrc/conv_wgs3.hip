@@ -80,11 +80,7 @@ static int wgs3_dispatch(const Wgs3Args& a, dim3 grid, size_t lds, int CIT, int 
   bool ok = false;
 #define FAMI_WS3_CASE(cit, cot, nys)                                                                                    \
   if (!ok && CIT == cit && COT == cot && NYS == nys) {                                                                  \
-    static bool attr = false;                                                                                             \
-    if (!attr) {                                                                                                          \
-      (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_kernel<cit, cot, nys>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                        \
-    }                                                                                                                     \
+    fami_lds_limit<conv_wgrad_s3_kernel<cit, cot, nys>>(160 * 1024);                                                      \
     hipLaunchKernelGGL((conv_wgrad_s3_kernel<cit, cot, nys>), grid, dim3(WS3_THREADS), lds, s, a);                      \
     ok = true;                                                                                                            \
   }

@@ -225,11 +225,7 @@ static long dark_lds_bytes(int H, int W, int k) {
 template <int K>
 static void dark_launch(const float* hm, const float* center, const float* scale, const float* taps, float* preds,
                         float* maxvals, int B, int J, int H, int W, size_t lds, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {  // a dynamic allocation above 64 KiB needs the function attribute
-    (void)hipFuncSetAttribute((const void*)dark_preds_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, DARK_LDS_MAX);
-    attr = true;
-  }
+  fami_lds_limit<dark_preds_kernel<K>>(DARK_LDS_MAX);  // a dynamic allocation above 64 KiB needs the function attribute
   hipLaunchKernelGGL(dark_preds_kernel<K>, dim3(B * J), dim3(DARK_THREADS), lds, s, hm, center, scale, taps, preds,
                      maxvals, J, H, W);
 }

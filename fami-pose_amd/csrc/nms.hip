@@ -215,12 +215,7 @@ int fami_pose_nms_f32(const float* kpts, const float* area, const float* box_sco
                "fami_pose_nms_f32", "a threshold is NaN");
   FAMI_REQUIRE(!soft || (oks_thre > 0.0 && max_dets >= 1), "fami_pose_nms_f32",
                "soft mode needs oks_thre > 0 and max_dets >= 1");
-  static bool attr = false;
-  if (!attr) {  // a dynamic allocation above 64 KiB (J = 32) needs the function attribute
-    (void)hipFuncSetAttribute((const void*)pose_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)nms_lds_bytes(NMS_JMAX));
-    attr = true;
-  }
+  fami_lds_limit<pose_nms_kernel>((int)nms_lds_bytes(NMS_JMAX));  // a dynamic allocation above 64 KiB (J = 32) needs the function attribute
   hipLaunchKernelGGL(pose_nms_kernel, dim3(M), dim3(NMS_THREADS), nms_lds_bytes(J), s, kpts, area, box_score, sigmas,
                      index, seg, score, rank, kept, N, J, in_vis_thre, oks_thre, soft ? 1 : 0, max_dets, vis_thre,
                      use_vis ? 1 : 0);

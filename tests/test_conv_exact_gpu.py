@@ -342,6 +342,68 @@ def test_backward_pair_is_exact(dev, dt):
     drive(dev, dt, 'backward-pair', knobs, cases, query=lambda L, g: getattr(L.cdll, ok)(*g[:5], 3, 3, 1, 1, 1) == 1, passes=_pair_passes)
 
 
+# ------------------------------------------------------------------------------------------------- refusals leave no capture
+def _refused(L, name, *args):
+    from fami_pose_amd._lib import FamiError
+    with pytest.raises(FamiError) as ei:
+        L.call(name, *args)
+    return str(ei.value)
+
+
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_refused_deferred_wgrad_leaves_no_reduce_capture(dev, dt):
+    """A fami_conv2d_wgrad_defer_* call refused AFTER its reduce capture was installed (a workspace one byte short of a single
+    [kh][kw][Ci][Co] slab: less than any route's plan needs, while one byte short of fami_conv2d_wgrad_workspace -- the largest
+    of the plans -- can still satisfy the route that takes the call), then the immediate form: dW is exact, so its reduce
+    was launched and not recorded into a capture nobody reads."""
+    geo = g3(1, 8, 8, 16, 16)
+    tune([])
+    r = Runner(dev, dt, make_case(geo))
+    slab = 16 * 16 * 9 * 4
+    assert r.ws_bytes >= slab
+    r._begin()
+    dw = r.A.output((16, 16, 3, 3), torch.float32, None, 'dw')
+    ws, _ = r._workspace()
+    desc = (ctypes.c_long * r.L.cdll.fami_wgrad_reduce_desc_longs())()
+    msg = _refused(r.L, 'fami_conv2d_wgrad_defer' + r.sfx, r.x.data_ptr(), r.dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), slab - 1,
+                   *r.g10, 0, desc, r.st)
+    assert '(-1)' in msg and 'workspace too small' in msg, msg
+    fails = r.wgrad(0) + r.wgrad(1)
+    assert not fails, 'after a refused deferred call, storage %s:\n  %s' % (dt, '\n  '.join(fails))
+
+
+@pytest.mark.parametrize('dt', ['f32', 'bf16'])
+def test_refused_backward_pair_leaves_no_launch_capture(dev, dt):
+    """A fami_conv2d_bwd_pair_* call refused inside its input gradient (kernel size 8) on the smallest geometry of the pair
+    tables that fami_conv2d_bwd_pair_ok* takes, then the plain input gradient of that geometry under the same knobs: dx is
+    exact, so the kernel was launched and not recorded into a pair capture nobody launches."""
+    if dt == 'f32':
+        knobs, cases, ok = [('lds', 7001), ('lds', 7600), ('lds', 7401)], PAIR_32, 'fami_conv2d_bwd_pair_ok_f32'
+    else:
+        knobs, cases, ok = [('lds', 8001), ('lds', 8501), ('lds', 8400)], PAIR_16, 'fami_conv2d_bwd_pair_ok'
+    L = _lib()
+    try:
+        tune(knobs)
+        taken = [g for g, _ in cases if getattr(L.cdll, ok)(*g[:5], 3, 3, 1, 1, 1) == 1]
+        assert taken, 'no geometry of the pair table is combined'
+        geo = min(taken, key=lambda g: g[0] * g[1] * g[2] * (g[3] + g[4]))
+        r = Runner(dev, dt, make_case(geo))
+        N, H, W, Ci, Co = geo[:5]
+        r._begin()
+        dx = r._act((N, H, W, Ci), None, 'dx')
+        dw = r.A.output((Co, Ci, 3, 3), torch.float32, None, 'dw')
+        ws, wsb = r._workspace()
+        desc = (ctypes.c_long * L.cdll.fami_wgrad_reduce_desc_longs())()
+        head = (r.x.data_ptr(), r.dy.data_ptr(), r.wp[1].data_ptr(), dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), wsb)
+        tail = (None, None, None, None, None, None, 0, None) if r.half else (None, None, None, None)
+        msg = _refused(L, 'fami_conv2d_bwd_pair' + r.sfx, *head, N, H, W, Ci, Co, 8, 8, 1, 1, 1, 0, 0, desc, *tail, r.st)
+        assert '(-2)' in msg and 'unsupported geometry' in msg, msg
+        fails = r.dgrad(0, 0) + r.dgrad(0, 1)
+        assert not fails, 'after a refused pair call, storage %s, geometry %s:\n  %s' % (dt, geo, '\n  '.join(fails))
+    finally:
+        L.cdll.fami_tune_reset()
+
+
 # ------------------------------------------------------------------------------------------------- dense tier
 @pytest.mark.parametrize('dt', TYPES)
 def test_dense_tier_pins_the_store_conversion(dev, dt):
