@@ -38,14 +38,24 @@
   (datasets/process/structure/data_format.py:12-49), empty frames filled in, one `{'annolist': [...]}` file per video
   named after the annotation file (posetrack_utils.py:13-56).
 
-Out of scope: the vendored poseval AP/MOTA computation (`evaluate_simple.evaluate`: needs shapely and the PoseTrack
-ground truth).  The files written here are its input.
+* `pack_posetrack_frames` / `load_posetrack_dirs` / `posetrack_ap` / `evaluate_posetrack_ap` -- the pose half of the
+  vendored poseval (`evaluate_simple.evaluate(gt_dir, pred_dir, eval_track=False)`, posetrack_utils/poseval/py/
+  evaluate_simple.py:13-50): per frame the greedy PCKh matching of predicted to annotated poses (assignGTmulti,
+  eval_helpers.py:453-668), per joint one precision / recall curve over the set and its VOC AP (computeRPC / VOCap
+  :192-228, computeMetrics evaluateAP.py:8-47), the summary row of getCum (:133-147).  In-process, in fp64 on the device:
+  one workgroup per frame for the matching and one per joint for the curve (csrc/posetrack_ap.hip), a stable
+  `torch.sort` between them; one upload, one download.  The ignore-region point filter, for which the reference needs
+  shapely, is an even-odd crossing test in the first kernel.  The files `write_posetrack_results` wrote are its input.
+
+Out of scope: poseval's tracking metrics (`evaluateTracking`, MOTA: needs motmetrics), the PoseTrack18 `images` /
+`annotations` file layout (poseval's convert.py), per-sequence AP files and PCKh (evaluatePCKh.py).
 
 The reference imports its joint-name lists from modules that are missing from the released tree
 (`datasets.zoo.coco`, `datasets.zoo.posetrack.pose_topology`, keypoints_ord.py:10-11); COCO_JOINT / POSETRACK_JOINT
 below are the standard COCO-17 and PoseTrack-15 orders of DCPose / Detect-and-Track, which the README defers to.
 """
 import json
+import math
 import os
 import os.path as osp
 
@@ -64,6 +74,11 @@ COCO_JOINT = ['nose', 'left_eye', 'right_eye', 'left_ear', 'right_ear', 'left_sh
 COCO_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 NMS_MAX_PER_IMAGE = 256         # csrc/nms.hip: one thread per detection of an image
 NMS_MAX_JOINTS = 32             # ... and one mask bit per joint
+AP_JOINTS = 15                  # csrc/posetrack_ap.hip: the PoseTrack joints, one mask bit each
+AP_MAX_PRED = 256               # ... one thread per predicted pose of a frame
+AP_MAX_GT = 64                  # ... the annotated poses of a frame are LDS-resident
+AP_MAX_SET = 458752             # ... one label bit per predicted pose of the set in 56 KiB of LDS
+AP_MIN_SCORE = -9999            # eval_helpers.MIN_SCORE: a predicted point without a score
 POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_knee', 'left_ankle', 'right_wrist',
                    'right_elbow', 'right_shoulder', 'left_shoulder', 'left_elbow', 'left_wrist', 'neck', 'nose',
                    'head_top']
@@ -548,3 +563,229 @@ def write_posetrack_results(preds, boxes, filenames_map, annot_dir, output_dir, 
             json.dump({'annolist': vdata}, f)
         written[path] = vname
     return written
+
+
+# ---------------------------------------------------------------------------------------- PoseTrack AP (poseval)
+def _rect_has_points(rect):
+    """eval_helpers.rectHasPoints (:370-373)."""
+    a = rect.get('annopoints')
+    return a is not None and len(a) > 0 and len(a[0]) > 0 and 'point' in a[0]
+
+
+def _num(v, what, where):
+    try:
+        x = float(v)
+    except (TypeError, ValueError):
+        raise ValueError('pack_posetrack_frames: %s of %s is not a number (%r)' % (what, where, v))
+    if not math.isfinite(x):
+        raise ValueError('pack_posetrack_frames: %s of %s is not finite (%r)' % (what, where, v))
+    return x
+
+
+def _pack_points(points, where, with_score, unique_ids):
+    """-> (row: 15 x (x, y, score) as a flat list; has mask).  The first occurrence of a joint id counts (getPointGTbyID,
+    :72-79).  Plain lists: a numpy store per point would double the time of the pack."""
+    row = [0.0] * (AP_JOINTS * 3)
+    has = 0
+    for pt in points:
+        pid = pt.get('id')
+        if pid is None:
+            continue
+        j = pid[0]
+        if isinstance(j, (bool, np.bool_)) or not isinstance(j, (int, np.integer)) or not 0 <= j < AP_JOINTS:
+            raise ValueError('pack_posetrack_frames: joint id %r of %s is outside 0 .. %d' % (j, where, AP_JOINTS - 1))
+        x, y = _num(pt['x'][0], 'x', where), _num(pt['y'][0], 'y', where)
+        sc = _num(pt['score'][0], 'score', where) if with_score and 'score' in pt else float(AP_MIN_SCORE)
+        if (has >> j) & 1:
+            if unique_ids:
+                raise ValueError('pack_posetrack_frames: joint id %d is listed twice in %s, a frame with ignore regions '
+                                 '(the reference filters before it picks the first)' % (j, where))
+            continue
+        has |= 1 << j
+        row[3 * j:3 * j + 3] = (x, y, sc)
+    return row, has
+
+
+def pack_posetrack_frames(gt_annolists, pr_annolists):
+    """The frames of an evaluation set as the flat fp64 / int32 arrays `posetrack_ap` uploads.  gt_annolists and
+    pr_annolists are the `annolist` frames of all sequences, one entry per frame, in the same order (what
+    `load_posetrack_dirs` returns).  Frame selection is the reference's (eval_helpers.load_data_dir -> cleanupData ->
+    removeIgnoredPoints, :305-367, 442-444): a ground-truth frame with an empty `annorect` is dropped with its
+    predictions; a rect without a `point` list is dropped; a frame's `ignore_regions` become its polygons (the point
+    filter itself runs on the device).  The first occurrence of a joint id in a point list counts; a prediction without a
+    `score` gets MIN_SCORE = -9999.
+    -> dict: pr_xys [P,15,3] (x, y, score), pr_has [P], gt_xy [G,15,2], gt_has [G], gt_head [G,4] (x1, y1, x2, y2),
+    pr_seg / gt_seg / poly_seg [F+1], vert_seg [NP+1], verts [NV,2], frame_index [F] (the position of every kept frame
+    in the inputs).  A rect that the ignore filter empties stays in the arrays with an empty mask -- it matches nothing,
+    which is what removing it does in the reference -- so `assigned` of `posetrack_ap` counts the annotated poses as
+    packed here.
+    ValueError for: unequal frame counts, a joint id outside 0 .. 14, non-finite coordinates or scores, more than 256
+    predicted or 64 annotated poses in a frame (the frame is named), an annotated pose without its head rectangle, an
+    ignore region of fewer than three points, and a joint id listed twice in a frame WITH ignore regions (the reference
+    filters first and then takes the first that is left; that order is not restated).  Neither input is modified (the
+    reference's assignGTmulti filters its prediction frames in place)."""
+    if len(gt_annolists) != len(pr_annolists):
+        raise ValueError('pack_posetrack_frames: %d ground-truth frames, %d prediction frames'
+                         % (len(gt_annolists), len(pr_annolists)))
+    pr_rows, pr_has, gt_rows, gt_has, gt_head = [], [], [], [], []
+    pr_seg, gt_seg, poly_seg, vert_seg, verts, kept = [0], [0], [0], [0], [], []
+    for idx, (gf, pf) in enumerate(zip(gt_annolists, pr_annolists)):
+        if len(gf['annorect']) == 0:
+            continue
+        where = 'frame %d' % idx
+        regions = gf.get('ignore_regions') or []
+        for reg in regions:
+            pts = reg['point']
+            if len(pts) < 3:
+                raise ValueError('pack_posetrack_frames: an ignore region of %s has %d points, a polygon needs 3'
+                                 % (where, len(pts)))
+            verts.extend((_num(p['x'][0], 'ignore-region x', where), _num(p['y'][0], 'ignore-region y', where)) for p in pts)
+            vert_seg.append(len(verts))
+        g_rects = [r for r in gf['annorect'] if _rect_has_points(r)]
+        p_rects = [r for r in pf['annorect'] if _rect_has_points(r)]
+        if len(p_rects) > AP_MAX_PRED or len(g_rects) > AP_MAX_GT:
+            raise ValueError('pack_posetrack_frames: %s has %d predicted and %d annotated poses, the limits are %d and %d'
+                             % (where, len(p_rects), len(g_rects), AP_MAX_PRED, AP_MAX_GT))
+        for r in g_rects:
+            row, has = _pack_points(r['annopoints'][0]['point'], where + ' (ground truth)', False, bool(regions))
+            try:
+                head = [_num(r[k][0], k, where) for k in ('x1', 'y1', 'x2', 'y2')]
+            except KeyError as e:
+                raise ValueError('pack_posetrack_frames: an annotated pose of %s has no %s (head rectangle)' % (where, e))
+            gt_rows.append(row)
+            gt_has.append(has)
+            gt_head.append(head)
+        for r in p_rects:
+            row, has = _pack_points(r['annopoints'][0]['point'], where + ' (prediction)', True, bool(regions))
+            pr_rows.append(row)
+            pr_has.append(has)
+        pr_seg.append(len(pr_rows))
+        gt_seg.append(len(gt_rows))
+        poly_seg.append(len(vert_seg) - 1)
+        kept.append(idx)
+    i32 = lambda a: np.asarray(a, dtype=np.int32)  # noqa: E731
+    return {'pr_xys': np.asarray(pr_rows, dtype=np.float64).reshape(-1, AP_JOINTS, 3), 'pr_has': i32(pr_has),
+            'gt_xy': np.ascontiguousarray(np.asarray(gt_rows, dtype=np.float64).reshape(-1, AP_JOINTS, 3)[:, :, :2]),
+            'gt_has': i32(gt_has),
+            'gt_head': np.asarray(gt_head, dtype=np.float64).reshape(-1, 4), 'pr_seg': i32(pr_seg), 'gt_seg': i32(gt_seg),
+            'poly_seg': i32(poly_seg), 'vert_seg': i32(vert_seg), 'verts': np.asarray(verts, dtype=np.float64).reshape(-1, 2),
+            'frame_index': np.asarray(kept, dtype=np.int64)}
+
+
+def load_posetrack_dirs(gt_dir, pred_dir):
+    """-> (gt_annolists, pr_annolists) for `pack_posetrack_frames`: the `annolist` frames of every *.json file of gt_dir
+    (sorted by name; the reference takes glob's order) and of the file of the same base name in pred_dir
+    (eval_helpers.load_data_dir, :385-440).  IOError for a missing prediction file and ValueError for a prediction file
+    with another number of frames, as the reference raises; ValueError for a file in the PoseTrack18 `images` /
+    `annotations` layout: its conversion (poseval's convert.py) is out of scope."""
+    gt_frames, pr_frames = [], []
+    for name in sorted(f for f in os.listdir(gt_dir) if f.endswith('.json')):
+        pair = []
+        for d in (gt_dir, pred_dir):
+            path = osp.join(d, name)
+            if not osp.exists(path):
+                raise IOError('Prediction file ' + path + ' does not exist')
+            with open(path) as fin:
+                data = json.load(fin)
+            if 'annolist' not in data:
+                raise ValueError('load_posetrack_dirs: %s is not in the annolist layout; converting the PoseTrack18 '
+                                 'images / annotations layout is out of scope' % path)
+            pair.append(data['annolist'])
+        if len(pair[0]) != len(pair[1]):
+            raise ValueError('# prediction frames %d != # GT frames %d for %s'
+                             % (len(pair[1]), len(pair[0]), osp.join(pred_dir, name)))
+        gt_frames += pair[0]
+        pr_frames += pair[1]
+    return gt_frames, pr_frames
+
+
+def _get_cum(vals):
+    """eval_helpers.getCum (:133-147): Head = mean(head_top, neck, nose), Shou, Elb, Wri, Hip, Knee, Ankl, Total."""
+    groups = ((14, 12, 13), (8, 9), (7, 10), (6, 11), (2, 3), (1, 4), (0, 5))
+    return [float(vals[list(g)].mean()) for g in groups] + [float(vals[AP_JOINTS])]
+
+
+def posetrack_ap(frames, dist_thresh=0.5, device='cuda'):
+    """PoseTrack AP of a packed set (`pack_posetrack_frames`) on the device: poseval's assignGTmulti + computeMetrics
+    (csrc/posetrack_ap.hip; include/fami.h has the arithmetic).  Per frame the predicted poses are matched greedily to
+    the annotated ones by PCKh at dist_thresh (after the ignore-region filter), per joint one precision / recall curve
+    over the whole set gives the VOC AP.  All arithmetic is fp64.  Equal scores keep frame order, then pose order within
+    the frame (a stable descending sort; the reference's `argsort()[::-1]` leaves them open).
+    -> dict: 'ap', 'pre', 'rec' float64 [16] (per joint in PoseTrack order, x 100; entry 15 the mean over the non-NaN
+    joints; a joint nobody predicts gives 0 and counts in the mean, one predicted but never annotated gives NaN and does
+    not -- both as in the reference), 'names' [16], 'cum' (the 8 values of getCum of `ap`: Head, Shou, Elb, Wri, Hip,
+    Knee, Ankl, Total), and for inspection 'label' [P] (bit j: joint j of the pose counts as a true positive), 'assigned'
+    [P] (frame-local index of the annotated pose it took, -1 for none), 'ngt' [15], 'pr_has' [P] / 'gt_has' [G] (the masks
+    left by the ignore-region filter).  One upload, two entry-point calls with one stable `torch.sort` between them, one
+    download.  An empty set returns the reference's values (all zeros) without device work.  ValueError for more than
+    458752 predicted poses in the set (the curve kernel's cap)."""
+    F = len(frames['pr_seg']) - 1
+    P, G = len(frames['pr_has']), len(frames['gt_has'])
+    names = POSETRACK_JOINT + ['total']
+    if F <= 0:
+        z = np.zeros(AP_JOINTS + 1)
+        return {'ap': z.copy(), 'pre': z.copy(), 'rec': z.copy(), 'names': names, 'cum': _get_cum(z),
+                'label': np.zeros(0, np.int32), 'assigned': np.zeros(0, np.int32), 'ngt': np.zeros(AP_JOINTS, np.int32),
+                'pr_has': np.zeros(0, np.int32), 'gt_has': np.zeros(0, np.int32)}
+    dist_thresh = float(dist_thresh)
+    if not np.isfinite(dist_thresh):
+        raise ValueError('posetrack_ap: dist_thresh must be finite')
+    if P > AP_MAX_SET:
+        raise ValueError('posetrack_ap: %d predicted poses, the limit is %d per set' % (P, AP_MAX_SET))
+    counts = np.diff(frames['pr_seg']), np.diff(frames['gt_seg'])
+    if counts[0].max() > AP_MAX_PRED or counts[1].max() > AP_MAX_GT:
+        m = int(np.argmax((counts[0] > AP_MAX_PRED) | (counts[1] > AP_MAX_GT)))
+        raise ValueError('posetrack_ap: kept frame %d has %d predicted and %d annotated poses, the limits are %d and %d'
+                         % (m, counts[0][m], counts[1][m], AP_MAX_PRED, AP_MAX_GT))
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('posetrack_ap runs on the HIP path only (device is %s)' % dev)
+    NP, NV = len(frames['vert_seg']) - 1, len(frames['verts'])
+    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), the int inputs, the int outputs, then (on an even
+    # word) ap / pre / rec -- one upload; everything from the first output on comes back in one download
+    f64 = [frames[k] for k in ('pr_xys', 'gt_xy', 'gt_head', 'verts')]
+    i32 = [frames[k] for k in ('pr_has', 'gt_has', 'pr_seg', 'gt_seg', 'poly_seg', 'vert_seg')]
+    sizes = [2 * a.size for a in f64] + [a.size for a in i32] + [P, G, P, P, F * AP_JOINTS, AP_JOINTS]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tail = int(off[-1] + (off[-1] & 1))
+    buf = np.zeros(tail + 2 * 3 * (AP_JOINTS + 1), dtype=np.int32)
+    for a, o in zip(f64, off):
+        buf[o:o + 2 * a.size] = np.ascontiguousarray(a, dtype=np.float64).reshape(-1).view(np.int32)
+    for a, o in zip(i32, off[4:]):
+        buf[o:o + a.size] = a
+    d = torch.from_numpy(buf).to(dev)
+    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]] + [d.data_ptr() + 4 * tail]
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        lib().call('fami_posetrack_assign_f64', p[0], p[4], p[1], p[5], p[2], p[6], p[7], p[8], p[9], p[3], P, G, F, NP, NV,
+                   dist_thresh, p[10], p[11], p[12], p[13], p[14], s)
+        # plumbing between the two kernels: per joint, the predictions that still have it, by descending score
+        if P:
+            bits = torch.arange(AP_JOINTS, dtype=torch.int32, device=dev)[:, None]
+            has_out, label = d[int(off[10]):int(off[10]) + P], d[int(off[12]):int(off[12]) + P]
+            present = ((has_out[None, :] >> bits) & 1).bool()
+            score = d[:2 * P * AP_JOINTS * 3].view(torch.float64).view(P, AP_JOINTS, 3)[:, :, 2].t()
+            order = torch.sort(torch.where(present, score, score.new_tensor(float('-inf'))), dim=1, descending=True,
+                               stable=True).indices
+            lab = ((label[order] >> bits) & 1).to(torch.uint8).contiguous()
+            n_valid = present.sum(1, dtype=torch.int32).contiguous()
+        else:                                                        # annotated poses only: 15 empty lists
+            lab = torch.zeros(AP_JOINTS, dtype=torch.uint8, device=dev)
+            n_valid = torch.zeros(AP_JOINTS, dtype=torch.int32, device=dev)
+        lib().call('fami_posetrack_curve_f64', lab.data_ptr(), n_valid.data_ptr(), p[14], P, F, p[16], p[15], s)
+    out = d[int(off[10]):].cpu().numpy()
+    o = [int(x - off[10]) for x in off[10:]]
+    pr_has_out, gt_has_out, label, assigned = (out[o[i]:o[i + 1]].copy() for i in range(4))
+    ngt_frame, ngt = out[o[4]:o[5]].reshape(F, AP_JOINTS), out[o[5]:o[6]].copy()
+    if (ngt_frame < 0).any():
+        raise RuntimeError('posetrack_ap: the kernel refused kept frame %d' % int(np.argmax((ngt_frame < 0).any(1))))
+    res = out[tail - int(off[10]):].view(np.float64).reshape(3, AP_JOINTS + 1)
+    return {'ap': res[0].copy(), 'pre': res[1].copy(), 'rec': res[2].copy(), 'names': names, 'cum': _get_cum(res[0]),
+            'label': label, 'assigned': assigned, 'ngt': ngt, 'pr_has': pr_has_out, 'gt_has': gt_has_out}
+
+
+def evaluate_posetrack_ap(gt_dir, pred_dir, device='cuda'):
+    """-> the 8 AP values Head, Shou, Elb, Wri, Hip, Knee, Ankl, Total: what the reference's
+    `evaluate_simple.evaluate(gt_dir, pred_dir, eval_track=False)[0]` returns, in-process.  gt_dir holds the annolist
+    ground-truth files, pred_dir the files of the same names -- the directory `write_posetrack_results` wrote to."""
+    return posetrack_ap(pack_posetrack_frames(*load_posetrack_dirs(gt_dir, pred_dir)), device=device)['cum']

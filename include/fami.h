@@ -526,6 +526,48 @@ int fami_pose_nms_f32(const float* kpts, const float* area, const float* box_sco
                       int soft, int max_dets, double vis_thre, int use_vis, float* score, int* rank, int* kept,
                       fami_stream_t stream);
 
+/* PoseTrack AP, the pose half of the evaluation tool the reference vendors (poseval/py/eval_helpers.py:322-367
+ * removeIgnoredPoints, :453-668 assignGTmulti, :192-228 computeRPC / VOCap; evaluateAP.py:8-47 computeMetrics;
+ * csrc/posetrack_ap.hip).  All pointers are DEVICE memory; fp64 arrays 8-byte, int arrays 4-byte aligned.  15 joints.
+ * fami_posetrack_assign_f64: F frames; frame f owns the predicted poses pr_seg[f] .. pr_seg[f+1) (at most 256), the
+ *   annotated poses gt_seg[f] .. gt_seg[f+1) (at most 64) and the ignore polygons poly_seg[f] .. poly_seg[f+1); polygon
+ *   q owns the vertices vert_seg[q] .. vert_seg[q+1) of verts [NV,2] (NP and NV may be 0; vert_seg has NP + 1 entries).
+ *   pr_xys [P,15,3] (x, y, score), pr_has [P] (bit j: joint j is present), gt_xy [G,15,2], gt_has [G], gt_head [G,4]
+ *   (x1, y1, x2, y2).  Per frame, in fp64:
+ *     1. a present point (x, y) is dropped when it lies inside any polygon of ITS frame by the even-odd rule: over the
+ *        edges (i, j = i - 1 cyclically), `inside` toggles where (y_i > y) != (y_j > y) and
+ *        x < (x_j - x_i) * (y - y_i) / (y_j - y_i) + x_i.  A point exactly on an edge is unspecified.
+ *        pr_has_out / gt_has_out = the masks that remain (bits 0 .. 14).
+ *     2. head(g) = 0.6 * sqrt((x2-x1)^2 + (y2-y1)^2); for joints both have, dist = sqrt(dx^2 + dy^2) / head(g) and
+ *        match = dist <= dist_thresh (head 0: inf or NaN, no match).  pck[p,g] = #match / #joints(g), undivided when g
+ *        has none.  Every p keeps only its best g (the first on ties); every g then takes the p with the largest pck
+ *        among those that kept it (the first on ties; none when that is 0).
+ *     label[p] = the match bits of a taken p against its g, 0 otherwise; assigned[p] = that g counted from gt_seg[f],
+ *     or -1; ngt_frame[f,j] = the annotated poses of f that still have joint j.  Scores are not read here.
+ *   One workgroup per frame, no atomics, no workspace: bitwise reproducible.  Returns -1 before any launch for a null or
+ *   misaligned pointer (an array of extent 0 may be null), a negative extent, F < 1, P * 45, G * 30 or F * 15 >= 2^31,
+ *   a NaN threshold.  The segment tables live in device memory and are not checked here
+ *   (fami_pose_amd.evaluate.pack_posetrack_frames does): a frame over a cap, or with a segment that is no sub-range of
+ *   its array, gets ngt_frame[f,:] = -1 and nothing else written; other frames are not affected.
+ * fami_posetrack_curve_f64: lab [15,P] bytes, row j the labels (non-zero: true positive) of joint j's predictions in
+ *   descending-score order, the first n_valid[j] of them valid; ngt_frame [F,15] as written above.  Per joint, with
+ *   nGT = sum_f ngt_frame[f,j] and npos_k the positives among the first k + 1:
+ *     precision_k = npos_k / (k+1), recall_k = npos_k / nGT, envelope_k = max(precision_k, precision_(k+1), ...),
+ *     AP = sum over the k with recall_k != recall_(k-1) (recall_(-1) = 0) of (recall_k - recall_(k-1)) * envelope_k,
+ *     plus (1 - recall_last) * 0 where recall_last != 1 -- VOCap with its two sentinels.
+ *   out [3,16] fp64: rows ap, pre (last precision), rec (last recall), each x 100; n_valid[j] = 0 gives 0, nGT = 0 with
+ *   predictions gives NaN ap and rec (0 / 0) as in the reference; column 15 = the mean over the non-NaN joints (NaN when
+ *   there is none).  ngt [15] = nGT.  The AP terms are added in a fixed order (256 runs of descending k, then a binary
+ *   tree): bitwise reproducible; only that order differs from numpy's sum.  Returns -1 before any launch for a null or
+ *   misaligned pointer, P outside 0 .. 458752 (one label bit each in 56 KiB of LDS), F < 1. */
+int fami_posetrack_assign_f64(const double* pr_xys, const int* pr_has, const double* gt_xy, const int* gt_has,
+                              const double* gt_head, const int* pr_seg, const int* gt_seg, const int* poly_seg,
+                              const int* vert_seg, const double* verts, int P, int G, int F, int NP, int NV,
+                              double dist_thresh, int* pr_has_out, int* gt_has_out, int* label, int* assigned,
+                              int* ngt_frame, fami_stream_t stream);
+int fami_posetrack_curve_f64(const unsigned char* lab, const int* n_valid, const int* ngt_frame, int P, int F,
+                             double* out, int* ngt, fami_stream_t stream);
+
 /* ---- input pipeline on the device -------------------------------------------------------------
  * cv2.warpAffine(frame, trans, (Wd, Hd), flags=INTER_LINEAR) on the F 8-bit HWC frames of one clip (one transform
  * for key + supporting frames, datasets/zoo/posetrack/PoseTrack_Alignment.py:421-427; flip = source mirrored in x
