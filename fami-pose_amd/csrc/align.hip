@@ -18,6 +18,8 @@
 #include <type_traits>
 
 // ------------------------------------------------------------------ bilinear shift
+// Three kernels, three walks (gather forward, gather of the transposed weights, reduction over the frame): they share the
+// bilinear formula and nothing a helper could carry.
 template <typename T>
 __global__ __launch_bounds__(256) void shift_fwd_kernel(const T* __restrict__ src, const float* __restrict__ t,
                                                         T* __restrict__ out, int B, int H, int W, int C) {
@@ -232,6 +234,14 @@ __global__ void dcn_pack_w16_kernel(const float* __restrict__ w, H* __restrict__
 // a wave-uniform float kept in an SGPR (the scalar unit has no int->float conversion)
 __device__ __forceinline__ float sgpr_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
+// maximum over the 4 waves of a workgroup (red: 4 floats of LDS); the result is valid in every thread
+__device__ __forceinline__ float wg_max(float m, float* red) {
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
 // Tail shared by the two forward kernels: the 4 waves hold partial [16, Co] tiles over their K slices; they meet in
 // LDS, bias is added and the block is stored as one contiguous run.
 template <typename T, int NT>
@@ -279,8 +289,8 @@ __device__ __forceinline__ void dcn_contract(const DcnArgs<T>& p, const float* c
   dcn_reduce_store<T, NT>(p, acc, red, m0);
 }
 
-// Forward, LDS-column-tile form (the default until the register-fed kernel below; now the fallback and A/B
-// partner).  Two phases per workgroup of DCN_PIX consecutive output pixels:
+// Forward, LDS-column-tile form: the fallback for tensors of 4 GiB and more and the A/B partner of the register-fed
+// kernel below (fami_dcn_tune(0)).  Two phases per workgroup of DCN_PIX consecutive output pixels:
 //  1. gather: one work item per (pixel, tap*group, 4-channel block) in the tap-major column order of the weight
 //     image; each bilinear corner is one 16-byte load of the cg-contiguous NHWC channels.  The modulated samples
 //     land in an LDS column tile col[pixel][kidx].
@@ -421,6 +431,8 @@ __global__ __launch_bounds__(256, MINW) void dcn_fwd_direct_kernel(DcnArgs<T> p)
   const int m0 = bxl * DCN_PIX;
   const int rows = min(DCN_PIX, p.P - m0);
 
+  // The two copies stay written out: as one inlined helper the same instructions come out in another register order and
+  // the <f16, 5, 1, 7> instance spills one more dword (scratch 24 -> 28 bytes)
   {  // offsets (/ + masks) of the tile: contiguous runs, 16-byte copies
     const int nb = rows * lo * (int)sizeof(T);
     const char* src = reinterpret_cast<const char*>(p.off + (long)m0 * p.ostr);
@@ -437,6 +449,8 @@ __global__ __launch_bounds__(256, MINW) void dcn_fwd_direct_kernel(DcnArgs<T> p)
     for (int i = (nb & ~15) + tid * (int)sizeof(T); i < nb; i += 256 * (int)sizeof(T))
       *reinterpret_cast<T*>(dst + i) = *reinterpret_cast<const T*>(src + i);
   }
+  // (group, tap) decode table.  Not shared with dcn_bwd2_kernel's: the items here are tap-major over ALL groups and carry
+  // the q4 channel blocks of a group, there they are tap-major within one chunk of groups
   for (int it = tid; it < nitem; it += 256) {
     int4 e = {0, 0, 0, 0};
     if (it * 4 < CK) {
@@ -877,8 +891,9 @@ __global__ __launch_bounds__(512 * KSPLIT) void dcn_fwd_win_kernel(DcnWinArgs<T>
 //   B. one work item per (pixel, group*tap): coalesced offset/mask stream, four 16-byte corner loads, then
 //        gmask = <gcol, sample>, goffset = <gcol*mask, d sample / d(y,x)>  (stored, 1 contiguous run / pixel)
 //        col   = sample*mask  (overwrites gcol in LDS; flushed for the weight gradient)
-//        gx   += gcol*mask*bilinear weights, scattered with LDS compare-and-swap adds (lds_add_f32) into a privatised input-gradient
-//                region (tile + dilation halo + DCN_RO pixels of offset reach); samples that leave the region
+//        gx   += gcol*mask*bilinear weights, scattered into a privatised input-gradient region in LDS (tile + dilation
+//                halo + DCN_RO pixels of offset reach) with fixed-point integer adds (MODE 1 / 2 / 3; the f32
+//                compare-and-swap adds of lds_add_f32 are MODE 0, opt-in); samples that leave the region
 //                fall back to global atomics, so any offset magnitude stays correct;
 //   C. the col tile is flushed in contiguous runs.
 // At the end the region is added to gx with coalesced global atomics: ~6x fewer atomics than scattering from
@@ -947,6 +962,24 @@ __device__ __forceinline__ void lds_fix_add(long long* a, float v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(a), (unsigned long long)(long long)i);
 }
 
+// Exponent of the per-workgroup fixed-point scale of the LDS region, from a bound on |gcol * mask|: bound = m * 2^e, m in
+// [0.5, 1), so every contribution is below 2^e.  The region's scale is 2^(FIXB - e), undone by 2^(e - FIXB) at the flush.
+__device__ __forceinline__ int dcn_bound_exp(float bound) {
+  int e = -60;
+  if (bound > 0.f && bound < 3.0e38f) (void)frexpf(bound, &e);
+  return e < -60 ? -60 : (e > 90 ? 90 : e);
+}
+
+// One item's offset-gradient pair / mask gradient, = or += per acc
+template <typename T>
+__device__ __forceinline__ void dcn_store_goff(T* qo, float gpy, float gpx, int acc) {
+  f32x2 go = {gpy, gpx};
+  if (acc) go += ld2(qo);
+  st2(qo, go);
+}
+template <typename T>
+__device__ __forceinline__ void dcn_store_gmsk(T* qm, float gm, int acc) { st1(qm, acc ? ld1(qm) + gm : gm); }
+
 // max |x| over a tensor as a float bit pattern (max is order independent: atomicMax on the bits of non-negative floats)
 template <typename T>
 __global__ __launch_bounds__(256) void absmax_kernel(const T* __restrict__ x, long n, unsigned* __restrict__ out) {
@@ -958,13 +991,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const T* __restrict__ x, lo
   // one atomic per workgroup (the host launches <= 256 of them): one per wave of a 2048-workgroup grid serialised 8192
   // same-address atomics, 95 us for a 1.3 M-element tensor
   __shared__ float red[4];
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if (m > 0.f) atomicMax(out, __float_as_uint(fminf(m, 3.0e38f)));
-  }
+  m = wg_max(m, red);
+  if (threadIdx.x == 0 && m > 0.f) atomicMax(out, __float_as_uint(fminf(m, 3.0e38f)));
 }
 __global__ void zero_u64_kernel(unsigned long long* p, long n, unsigned* amax) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0ull;
@@ -1015,10 +1043,8 @@ __global__ __launch_bounds__(256) void dcn_wnorm_kernel(const float* __restrict_
     for (int co = 0; co < Co; ++co) sum += fabsf(w[(long)co * CK + k]);
     m = fmaxf(m, sum);
   }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x < 4) out[threadIdx.x] = threadIdx.x == 0 ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : 0.f;
+  m = wg_max(m, red);
+  if (threadIdx.x < 4) out[threadIdx.x] = threadIdx.x == 0 ? m : 0.f;
 }
 
 template <typename T, int KSO, int MODE>
@@ -1078,10 +1104,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_kernel(DcnBwdArgs<T> p) {
       }
     }
     mdy = wave_max(mdy);
-    const float bound = mdy * (p.msk ? DCN_MASK_BOUND : 1.f) * p.wnorm[0];
-    int e = -60;
-    if (bound > 0.f && bound < 3.0e38f) (void)frexpf(bound, &e);   // bound = m * 2^e, m in [0.5, 1): every |gcol * mask| < 2^e
-    e = e < -60 ? -60 : (e > 90 ? 90 : e);
+    const int e = dcn_bound_exp(mdy * (p.msk ? DCN_MASK_BOUND : 1.f) * p.wnorm[0]);
     fscale = ldexpf(1.f, FIXB - e);
     finv = ldexpf(1.f, e - FIXB);
   }
@@ -1266,16 +1289,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_kernel(DcnBwdArgs<T> p) {
           }
         }
       }
-      if (p.goff) {
-        T* qo = p.goff + m * p.ostr + gt * 2;
-        f32x2 go = {gpy, gpx};
-        if (p.acc_off) go += ld2(qo);
-        st2(qo, go);
-      }
-      if (p.gmsk) {
-        T* qm = p.gmsk + m * p.mstr + gt;
-        st1(qm, p.acc_off ? ld1(qm) + gm : gm);
-      }
+      if (p.goff) dcn_store_goff(p.goff + m * p.ostr + gt * 2, gpy, gpx, p.acc_off);
+      if (p.gmsk) dcn_store_gmsk(p.gmsk + m * p.mstr + gt, gm, p.acc_off);
     }
     __syncthreads();
     // ---- C: flush the modulated samples (weight-gradient operand)
@@ -1292,7 +1307,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_kernel(DcnBwdArgs<T> p) {
     }
     __syncthreads();
   }
-  // ---- region -> gx
+  // ---- region -> gx.  Not shared with dcn_bwd2_kernel's flush: this one walks dense [RH][RW][Cc] cells with integer
+  // divisions, that one cells padded to a stride of CS with reciprocal multiplies
   if (DET) {
     if (gfb) {
       for (int e = tid; e < p.RH * p.RW * Cc; e += 256) {
@@ -1495,16 +1511,9 @@ __global__ __launch_bounds__(256, 3) void dcn_bwd2_kernel(DcnBwd2Args<T> p) {
   mdy = wave_max(mdy);
   if (lane == 0) wmax[wave] = mdy;
   __syncthreads();
-  float fscale, finv;
-  {
-    mdy = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    const float bound = mdy * (p.msk ? DCN_MASK_BOUND : 1.f) * p.wnorm[0];
-    int e = -60;
-    if (bound > 0.f && bound < 3.0e38f) (void)frexpf(bound, &e);   // every |gcol * mask| < 2^e
-    e = e < -60 ? -60 : (e > 90 ? 90 : e);
-    fscale = ldexpf(1.f, FIXB - e);
-    finv = ldexpf(1.f, e - FIXB);
-  }
+  mdy = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  const int fexp = dcn_bound_exp(mdy * (p.msk ? DCN_MASK_BOUND : 1.f) * p.wnorm[0]);
+  const float fscale = ldexpf(1.f, FIXB - fexp), finv = ldexpf(1.f, fexp - FIXB);
 
   const char* xbase = reinterpret_cast<const char*>(p.x) + (long)b * p.H * p.W * p.C * sizeof(T);
   float* gxb = p.gx ? p.gx + (long)b * p.H * p.W * p.C : nullptr;
@@ -1531,7 +1540,8 @@ __global__ __launch_bounds__(256, 3) void dcn_bwd2_kernel(DcnBwd2Args<T> p) {
     const f32x2 o = ov;
     const float mk = iv ? mv : 0.f;
     // ---- the item's sample position and its four corner loads FIRST: they do not depend on the column gradient, so the matrix
-    // instructions below run while the loads are in flight
+    // instructions below run while the loads are in flight.  (The clamped-address set-up of dcn_fwd_direct_kernel's gather,
+    // written out again: this kernel's register count moved with every helper tried in it -- docs/HISTORY.md, align fold.)
     const float sy = (float)(sy0 + tc.y) + o.x, sx = (float)(sx0 + tc.z) + o.y;
     const float fy = floorf(sy), fx = floorf(sx);
     const float ly = sy - fy, lx = sx - fx, hy = 1.f - ly, hx = 1.f - lx;
@@ -1601,16 +1611,8 @@ __global__ __launch_bounds__(256, 3) void dcn_bwd2_kernel(DcnBwd2Args<T> p) {
         st1(gst + px * grun + 2 * nli + gtl, gm);
       }
     } else if (iv) {
-      if (goffp) {
-        T* qo = goffp + tc.w * 2;
-        f32x2 go = {gpy, gpx};
-        if (p.acc_off) go += ld2(qo);
-        st2(qo, go);
-      }
-      if (gmskp) {
-        T* qm = gmskp + tc.w;
-        st1(qm, p.acc_off ? ld1(qm) + gm : gm);
-      }
+      if (goffp) dcn_store_goff(goffp + tc.w * 2, gpy, gpx, p.acc_off);
+      if (gmskp) dcn_store_gmsk(gmskp + tc.w, gm, p.acc_off);
     }
     // ---- input gradient
     if (gxb && iv) {
@@ -1693,39 +1695,40 @@ __global__ __launch_bounds__(256, 3) void dcn_bwd2_kernel(DcnBwd2Args<T> p) {
   }
 }
 
-// ------------------------------------------------------------------ host side (templates over the storage type)
-template <typename T>
-static int shift_fwd_impl(const T* src, const float* t, T* out, int B, int H, int W, int C, hipStream_t s,
-                          const char* nm) {
-  FAMI_REQUIRE(src && t && out && B > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0, nm, "bad argument");
-  hipLaunchKernelGGL(shift_fwd_kernel<T>, dim3(fami_ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, s, src, t, out, B, H, W, C);
-  FAMI_CHECK_LAUNCH(nm);
-  return FAMI_OK;
+// ================================================================== host side (templates over the storage type)
+// Layouts and plans, launchers, implementations, one extern "C" block.  The fami_dcn_tune codes that write the
+// [fami_route_t] fields named below are listed in include/fami.h.
+// Output size, channels per group, pixel count (and whether it fits an int) and the per-pixel strides of the offset / mask
+// tensors of one DCN call.  merged: off / goff are ONE tensor each, [P][2GK offsets | GK masks] (the merged predictor's output
+// and its gradient): the masks of a pixel then start moff elements behind its offsets.
+struct DcnGeom { int Ho, Wo, cg, ostr, mstr, moff; long P; bool P_ok; };
+static DcnGeom dcn_geom(int B, int H, int W, int C, int G, int kh, int kw, int stride, int pad, int dil, bool merged) {
+  DcnGeom g;
+  const int GK = G * kh * kw;
+  g.ostr = (merged ? 3 : 2) * GK, g.mstr = (merged ? 3 : 1) * GK, g.moff = 2 * GK;
+  g.Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
+  g.Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+  g.cg = G > 0 ? C / G : 0;
+  g.P = (long)B * g.Ho * g.Wo;
+  g.P_ok = g.P < (1L << 31);
+  return g;
 }
 
-template <typename T>
-static int shift_bwd_impl(const T* gout, const T* src, const float* t, T* gsrc, float* gt, int B, int H, int W, int C,
-                          int acc_src, int acc_t, float* ws, hipStream_t s, const char* nm) {
-  FAMI_REQUIRE(gout && src && t && B > 0 && (C % 4) == 0, nm, "bad argument");
-  if (gsrc) {
-    hipLaunchKernelGGL(shift_bwd_src_kernel<T>, dim3(fami_ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, s, gout, t, gsrc, B, H, W, C, acc_src);
-    FAMI_CHECK_LAUNCH(nm);
-  }
-  if (gt) {
-    FAMI_REQUIRE(ws, nm, "workspace required for gt");
-    long g = ((long)H * W * (C / 4) + 255) / 256;
-    if (g > 256) g = 256;
-    hipLaunchKernelGGL(shift_bwd_t_kernel<T>, dim3((int)g, B), dim3(256), 0, s, gout, src, t, ws, H, W, C);
-    FAMI_CHECK_LAUNCH(nm);
-    hipLaunchKernelGGL(shift_bwd_t_finalize_kernel, dim3(fami_cdiv(B * 2, 64)), dim3(64), 0, s, ws, (int)g, B, gt, acc_t);
-    FAMI_CHECK_LAUNCH(nm);
-  }
-  return FAMI_OK;
+// The forward weight buffer (fami_dcn_pack_weight_*), offsets in floats: the tap-major fp32 image at 0 (dcn_fwd_kernel /
+// dcn_fwd_direct_kernel), the quad-group fp32 image (dcn_fwd_win_kernel), then the 16-bit tap-major image of the 16-bit modes
+// (512 values = 256 floats' worth per 32-step and channel tile).
+struct DcnFwdImages { int KS, NTt, NQ, KS32; long wq, w16, total; };
+static DcnFwdImages dcn_fwd_images(int Co, int C, int kh, int kw, int G) {
+  DcnFwdImages L;
+  L.KS = fami_cdiv((long)C * kh * kw, 16);
+  L.NTt = fami_cdiv(Co, 16);
+  L.NQ = fami_cdiv((long)G * kh * kw, 16);
+  L.KS32 = fami_cdiv(L.KS, 2);
+  L.wq = (long)L.KS * L.NTt * 256;
+  L.w16 = L.wq + (long)L.NQ * 4 * L.NTt * 256;
+  L.total = L.w16 + (long)L.KS32 * L.NTt * 256;
+  return L;
 }
-
-// [fami_route_t] g_dcn_gather (default -1)  // fami_dcn_tune: 0 = dcn_fwd_kernel (LDS column tile), 1 = dcn_fwd_direct_kernel, 2 = dcn_fwd_win_kernel where eligible, -1 default (= 1)
-// [fami_route_t] g_dcn_abl (default 0)
-// [fami_route_t] g_dcn_win_r (default 0)  // fami_dcn_tune(32 + r): force the window's offset reach (benchmarks); 0 = largest that fits, up to 4
 
 // LDS-window forward: tile / window plan.  Eligible: stride 1, 4 channels per offset group (every HRNet width),
 // G*K a multiple of 4, C a multiple of 16 bytes' worth of elements, window (+ decode table) within 156 KB.
@@ -1737,6 +1740,7 @@ static unsigned dcn_div_mul(int d, int n) {
   if ((m * d - (1ul << 24)) * (unsigned long)n >= (1ul << 24)) return 0;   // error term stays below one quotient step
   return (unsigned)m;
 }
+// [fami_route_t] g_dcn_win_r (default 0)  // force the window's offset reach (benchmarks); 0 = largest that fits, up to 4
 static DcnWinPlan dcn_win_plan(int B, int Ho, int Wo, int C, int G, int kh, int kw, int stride, int dil, int esz) {
   DcnWinPlan q;
   q.ok = 0;
@@ -1772,139 +1776,16 @@ static DcnWinPlan dcn_win_plan(int B, int Ho, int Wo, int C, int G, int kh, int 
   return q;
 }
 
-template <typename T, int NT, bool ABL, int KSPLIT>
-static void dcn_fwd_win_launch1(const DcnWinArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  fami_lds_limit<dcn_fwd_win_kernel<T, NT, ABL, KSPLIT>>(156 * 1024);
-  hipLaunchKernelGGL((dcn_fwd_win_kernel<T, NT, ABL, KSPLIT>), grid, dim3(512 * KSPLIT), lds, s, a);
-}
-// [fami_route_t] g_dcn_ksplit (default 1)  // fami_dcn_tune(256 + k): 2 = the 16-wave K-split build (measured slower: 35.5 vs 29.8 us)
-template <typename T, int NT>
-static void dcn_fwd_win_launch(const DcnWinArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (NT == 3 && sizeof(T) == 4 && a.abl) {   // tools/bench_dcn_win.py
-    if (g_dcn_ksplit == 2) dcn_fwd_win_launch1<T, NT == 3 ? NT : 3, sizeof(T) == 4, 2>(a, grid, lds, s);
-    else dcn_fwd_win_launch1<T, NT == 3 ? NT : 3, sizeof(T) == 4, 1>(a, grid, lds, s);
-  } else if (g_dcn_ksplit == 2) dcn_fwd_win_launch1<T, NT, false, 2>(a, grid, lds, s);
-  else dcn_fwd_win_launch1<T, NT, false, 1>(a, grid, lds, s);
-}
-// [fami_route_t] g_dcn_pf (default 0)  // fami_dcn_tune(16 + 2): the 2-k-groups-in-flight x 4-waves-per-SIMD build of the direct kernel (benchmarks)
-
-template <typename T, int NT, int PF, int MINW>
-static void dcn_fwd_direct_launch(const DcnArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  fami_lds_limit<dcn_fwd_direct_kernel<T, NT, PF, MINW>>(150 * 1024);
-  hipLaunchKernelGGL((dcn_fwd_direct_kernel<T, NT, PF, MINW>), grid, dim3(256), lds, s, a);
-}
-
-template <typename T, int NT>
-static void dcn_fwd_launch(const DcnArgs<T>& a, dim3 grid, size_t lds, size_t lds_direct, bool direct, hipStream_t s) {
-  fami_lds_limit<dcn_fwd_kernel<T, NT>>(150 * 1024);
-  if (!direct) {
-    hipLaunchKernelGGL((dcn_fwd_kernel<T, NT>), grid, dim3(256), lds, s, a);
-    return;
-  }
-  // Measured (tools/bench_dcn.py, B=4 96x72 48 ch): 1 or 2 k groups in flight x 4..7 waves per SIMD all land within
-  // +-1.5 us in f32 (31-34 us: the corner loads run at the L1's one-line-per-cycle rate), bf16 25.0 (1 x 7) vs 27.6 us
-  // (2 x 4).  Default: one k group per wave in flight, 7 workgroups per CU (62 VGPRs, 22.5 KB LDS) -- the 6.75 tiles a
-  // CU owns at B=4 are then all resident at once.  Wide outputs (NT > 3) carry 4*NT accumulator + 4*NT weight registers.
-  if (NT > 3)
-    dcn_fwd_direct_launch<T, NT, 1, 4>(a, grid, lds_direct, s);
-  else if (g_dcn_pf == 2)
-    dcn_fwd_direct_launch<T, NT, 2, 4>(a, grid, lds_direct, s);
-  else
-    dcn_fwd_direct_launch<T, NT, 1, 7>(a, grid, lds_direct, s);
-}
-
-static inline long dcn_f32_image_elems(int Co, int C, int kh, int kw, int G) {
-  const long nt = fami_cdiv(Co, 16);
-  return (long)fami_cdiv((long)C * kh * kw, 16) * nt * 256 + (long)fami_cdiv((long)G * kh * kw, 16) * 4 * nt * 256;
-}
-template <typename T>
-static int dcn_fwd_impl(const T* x, const T* off, const T* msk, const float* wp, const float* bias, T* y, int B, int H,
-                        int W, int C, int Co, int G, int kh, int kw, int stride, int pad, int dil, hipStream_t s,
-                        const char* nm, bool merged = false) {
-  FAMI_REQUIRE(x && off && wp && y && B > 0 && G > 0 && C % G == 0, nm, "bad argument");
-  DcnArgs<T> a;
-  // merged: `off` is ONE tensor [P][2GK offsets | GK masks] (the merged predictor's output); msk is derived here
-  a.ostr = (merged ? 3 : 2) * G * kh * kw;
-  a.mstr = (merged ? 3 : 1) * G * kh * kw;
-  if (merged) msk = off + 2 * G * kh * kw;
-  a.x = x; a.off = off; a.msk = msk; a.wp = wp; a.bias = bias; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.Co = Co; a.G = G; a.kh = kh; a.kw = kw;
-  a.stride = stride; a.pad = pad; a.dil = dil;
-  // the 16-bit image follows the two fp32 images (fami_dcn_packed_weight_elems); written by fami_dcn_pack_weight_bf16/_f16
-  a.wp16 = wp + dcn_f32_image_elems(Co, C, kh, kw, G);
-  a.Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  a.Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-  a.cg = C / G;
-  if ((a.cg % 4) != 0 || Co > 96) {
-    fami_set_error(nm, "channels per offset group must be a multiple of 4 and Co <= 96");
-    return FAMI_ESHAPE;
-  }
-  a.KS = fami_cdiv((long)C * kh * kw, 16);
-  a.NTt = fami_cdiv(Co, 16);
-  const long P = (long)B * a.Ho * a.Wo;
-  FAMI_REQUIRE(P < (1L << 31), nm, "size out of range");
-  a.P = (int)P;
-  if (g_dcn_gather == 2) {
-    const DcnWinPlan q = dcn_win_plan(B, a.Ho, a.Wo, C, G, kh, kw, stride, dil, (int)sizeof(T));
-    if (q.ok && a.NTt <= 4 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(off) | reinterpret_cast<uintptr_t>(msk)) & 15) == 0) {
-      DcnWinArgs<T> w;
-      w.x = x; w.off = off; w.msk = msk; w.bias = bias; w.y = y;
-      w.wq = wp + (long)a.KS * a.NTt * 256;      // the quad-order image follows the tap-major one
-      w.B = B; w.H = H; w.W = W; w.C = C; w.Ho = a.Ho; w.Wo = a.Wo; w.Co = Co; w.G = G; w.K = kh * kw; w.kw = kw;
-      w.pad = pad; w.dil = dil;
-      w.TH = q.TH; w.TW = q.TW; w.tilesX = q.tilesX; w.tilesY = q.tilesY; w.R = q.R; w.WR = q.WR; w.WC = q.WC; w.PS = q.PS;
-      w.NQ = q.NQ; w.NTt = a.NTt; w.nsub = q.nsub; w.mul_row = q.mul_row; w.mul_px = q.mul_px; w.abl = g_dcn_abl;
-      w.ostr = a.ostr; w.mstr = a.mstr;
-      const dim3 grid(q.tilesX * q.tilesY * B);
-      switch (a.NTt) {
-        case 1: dcn_fwd_win_launch<T, 1>(w, grid, q.lds, s); break;
-        case 2: dcn_fwd_win_launch<T, 2>(w, grid, q.lds, s); break;
-        case 3: dcn_fwd_win_launch<T, 3>(w, grid, q.lds, s); break;
-        default: dcn_fwd_win_launch<T, 4>(w, grid, q.lds, s); break;
-      }
-      FAMI_CHECK_LAUNCH(nm);
-      return FAMI_OK;
-    }
-  }
-  const dim3 grid(fami_cdiv(P, DCN_PIX));
-  // the direct kernel addresses x with 32-bit byte offsets (24-bit row / column products)
-  const size_t lds = ((size_t)DCN_PIX * (a.KS * 16 + 4) + 4 * (size_t)a.NTt * 256) * sizeof(float);
-  size_t lds_direct = (((size_t)DCN_PIX * G * kh * kw * 3 * sizeof(T) + 15) & ~(size_t)15) + (size_t)a.KS * 4 * sizeof(int4);
-  if (lds_direct < 4 * (size_t)a.NTt * 256 * sizeof(float)) lds_direct = 4 * (size_t)a.NTt * 256 * sizeof(float);
-  const bool direct = g_dcn_gather != 0 && (long)B * H * W * C * sizeof(T) < (1L << 32) &&
-                      (long)H * W * C * sizeof(T) < (1L << 24) && lds_direct <= 150 * 1024;
-  if (!direct && lds > 150 * 1024) {
-    fami_set_error(nm, "C*kh*kw too large for the LDS column tile");
-    return FAMI_ESHAPE;
-  }
-  switch (a.NTt) {
-    case 1: dcn_fwd_launch<T, 1>(a, grid, lds, lds_direct, direct, s); break;
-    case 2: dcn_fwd_launch<T, 2>(a, grid, lds, lds_direct, direct, s); break;
-    case 3: dcn_fwd_launch<T, 3>(a, grid, lds, lds_direct, direct, s); break;
-    case 4: dcn_fwd_launch<T, 4>(a, grid, lds, lds_direct, direct, s); break;
-    case 5: dcn_fwd_launch<T, 5>(a, grid, lds, lds_direct, direct, s); break;
-    default: dcn_fwd_launch<T, 6>(a, grid, lds, lds_direct, direct, s); break;
-  }
-  FAMI_CHECK_LAUNCH(nm);
-  return FAMI_OK;
-}
-
 // ---- register-fed backward (dcn_bwd2_kernel): plan shared by the weight pack, the launch and the callers' `col` width
-// [fami_route_t] g_dcn_bwd2 (default 1)  // fami_dcn_tune(2048 / 2049): off / on
-// [fami_route_t] g_dcn_bwd2_cap (default 36)  // fami_dcn_tune(4096 + KB): LDS budget of the fixed-point region (decides the groups per workgroup; benchmarks -- set BEFORE the weight pack)
-// [fami_route_t] g_dcn_bwd_abl (default 0)  // fami_dcn_tune(1024 + bits): ablations of the general backward kernel (benchmarks)
-// [fami_route_t] g_dcn_bwd_scatter (default -1)  // fami_dcn_tune(512 + m): 0 = f32 compare-and-swap LDS adds, 1 / default = fixed-point LDS adds (64-bit for f32, 32-bit for 16-bit storage), 2 = 64-bit for every type
-// the register-fed kernel takes the default scatter (64-bit cells for f32 storage, 32-bit for the 16-bit types); every other
-// setting of the knobs above selects a form only the general kernel has
-static inline bool dcn_bwd2_on(int esz) {
-  return g_dcn_bwd2 && g_dcn_bwd_scatter != 0 && !(esz == 2 && g_dcn_bwd_scatter == 2) && !g_dcn_bwd_abl;
-}
+// [fami_route_t] g_dcn_bwd2_cap (default 36)  // LDS budget in KB of the fixed-point region (decides the groups per workgroup; benchmarks -- set BEFORE the weight pack)
+// [fami_route_t] g_dcn_bwd2_stage (default 1)  // offset / mask gradients staged in LDS (STG instances of the kernel)
 struct DcnBwd2Plan { int ok, GC, nchunk, NQ, colw, NJ, RH, RW, CS, stg; size_t lds; };
-static DcnBwd2Plan dcn_bwd2_plan(int C, int Co, int G, int kh, int kw, int stride, int dil, int esz) {
+// on: the g_dcn_bwd2 switch as the caller sees it (a parameter, so that asking for the plan never writes routing state)
+static DcnBwd2Plan dcn_bwd2_plan_for(bool on, int C, int Co, int G, int kh, int kw, int stride, int dil, int esz) {
   DcnBwd2Plan q;
   q.ok = 0; q.colw = C * kh * kw;
   const int K = kh * kw;
-  if (!g_dcn_bwd2 || stride != 1 || G <= 0 || C != 4 * G || (Co % 16) != 0 || Co > 96 || K > 64) return q;
+  if (!on || stride != 1 || G <= 0 || C != 4 * G || (Co % 16) != 0 || Co > 96 || K > 64) return q;
   q.RH = 7 + (kh - 1) * dil + 2 + 2 * DCN2_RO;
   q.RW = 7 + (kw - 1) * dil + 2 + 2 * DCN2_RO;
   // groups per workgroup: the largest divisor of G whose fixed-point region (64-bit cells for f32 storage, 32-bit for the
@@ -1933,23 +1814,44 @@ static DcnBwd2Plan dcn_bwd2_plan(int C, int Co, int G, int kh, int kw, int strid
   if (!q.ok) q.colw = C * kh * kw;
   return q;
 }
-static inline long dcn_bwd_old_image_elems(int Co, int C, int kh, int kw) {
-  return (long)fami_cdiv((long)C * kh * kw, 16) * fami_cdiv(Co, 16) * 256 + 4;
+// [fami_route_t] g_dcn_bwd2 (default 1)  // the register-fed backward kernel off / on
+static DcnBwd2Plan dcn_bwd2_plan(int C, int Co, int G, int kh, int kw, int stride, int dil, int esz) {
+  return dcn_bwd2_plan_for(g_dcn_bwd2 != 0, C, Co, G, kh, kw, stride, dil, esz);
 }
-// image of the register-fed kernel for storage size esz (4 | 2): floats
-static inline long dcn_bwd2_image_elems(const DcnBwd2Plan& q, int esz) {
-  return q.ok ? (long)q.nchunk * q.NQ * q.NJ * (esz == 4 ? 256 : 512) : 0;
+// The plan the weight images are packed and sized for: the head's geometry (stride 1, dilation 3), whatever the switch says.
+// The images are packed before any launch and must not depend on the actual dilation; what they do depend on (groups per
+// workgroup, quads, Co tiles) the plan chooses without looking at it.
+static DcnBwd2Plan dcn_bwd2_head_plan(int C, int Co, int G, int kh, int kw, int esz) {
+  return dcn_bwd2_plan_for(true, C, Co, G, kh, kw, 1, 3, esz);
 }
-template <typename T, int NCO, bool STG>
-static void dcn_bwd2_launch1(const DcnBwd2Args<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  constexpr bool F32 = sizeof(T) == 2;       // 16-bit storage: 32-bit fixed-point region
-  fami_lds_limit<dcn_bwd2_kernel<T, NCO, F32, STG>>(64 * 1024);
-  hipLaunchKernelGGL((dcn_bwd2_kernel<T, NCO, F32, STG>), grid, dim3(256), lds, s, a);
+// [fami_route_t] g_dcn_bwd_abl (default 0)  // ablations of the general backward kernel (benchmarks)
+// [fami_route_t] g_dcn_bwd_scatter (default -1)  // 0 = f32 compare-and-swap LDS adds, 1 / default = fixed-point LDS adds (64-bit for f32, 32-bit for 16-bit storage), 2 = 64-bit for every type
+// the register-fed kernel takes the default scatter (64-bit cells for f32 storage, 32-bit for the 16-bit types); every other
+// setting of the knobs above selects a form only the general kernel has
+static inline bool dcn_bwd2_on(int esz) {
+  return g_dcn_bwd2 && g_dcn_bwd_scatter != 0 && !(esz == 2 && g_dcn_bwd_scatter == 2) && !g_dcn_bwd_abl;
 }
-template <typename T, int NCO>
-static void dcn_bwd2_launch(const DcnBwd2Args<T>& a, dim3 grid, size_t lds, hipStream_t s, int stg) {
-  if (stg) dcn_bwd2_launch1<T, NCO, true>(a, grid, lds, s);
-  else dcn_bwd2_launch1<T, NCO, false>(a, grid, lds, s);
+// The plan that decides the layout of `col` for a caller (fami_dcn_bwd_col_width / _col_permuted): the register-fed kernel's
+// where the non-deterministic backward takes it (ok = 1, its own column order, colw wide), else ok = 0 and colw = C*kh*kw.
+static DcnBwd2Plan dcn_bwd_col_plan(int C, int Co, int G, int kh, int kw, int stride, int dil, int esz, int deterministic) {
+  return dcn_bwd2_plan_for(!deterministic && dcn_bwd2_on(esz), C, Co, G, kh, kw, stride, dil, esz);
+}
+
+// The backward weight buffer (fami_dcn_pack_weight_bwd_f32), offsets in floats: the general image of dcn_pack_wb_kernel at 0,
+// 4 floats of which [0] = max_k sum_co |W[co][k]| (dcn_wnorm_kernel: the fixed-point scale bound), then the register-fed
+// kernel's image for f32 storage and the one for 16-bit storage (other chunking, other MFMA shape; fp32 values both).
+struct DcnBwdImages { int NT, KSo; long wnorm, img32, img16, total; DcnBwd2Plan q32, q16; };
+static DcnBwdImages dcn_bwd_images(int Co, int C, int kh, int kw, int G) {
+  DcnBwdImages L;
+  L.NT = fami_cdiv((long)C * kh * kw, 16);
+  L.KSo = fami_cdiv(Co, 16);
+  L.q32 = dcn_bwd2_head_plan(C, Co, G, kh, kw, 4);
+  L.q16 = dcn_bwd2_head_plan(C, Co, G, kh, kw, 2);
+  L.wnorm = (long)L.NT * L.KSo * 256;
+  L.img32 = L.wnorm + 4;
+  L.img16 = L.img32 + (L.q32.ok ? (long)L.q32.nchunk * L.q32.NQ * L.q32.NJ * 256 : 0);
+  L.total = L.img16 + (L.q16.ok ? (long)L.q16.nchunk * L.q16.NQ * L.q16.NJ * 512 : 0);
+  return L;
 }
 
 static int dcn_bwd_chunk_groups(int G, int cg, int K) {
@@ -1959,18 +1861,157 @@ static int dcn_bwd_chunk_groups(int G, int cg, int K) {
   return 0;
 }
 
-template <typename T, int KSO, int MODE>
-static void dcn_bwd_launch1(const DcnBwdArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  fami_lds_limit<dcn_bwd_kernel<T, KSO, MODE>>(150 * 1024);
-  hipLaunchKernelGGL((dcn_bwd_kernel<T, KSO, MODE>), grid, dim3(256), lds, s, a);
+// ------------------------------------------------------------------ launchers
+// f(std::integral_constant<int, n>) for a tile count n in 1 .. MAX; anything else takes the largest instance
+template <int MAX, int N = 1, typename F>
+static inline void dcn_dispatch(int n, F&& f) {
+  if constexpr (N < MAX) {
+    if (n == N) f(std::integral_constant<int, N>{});
+    else dcn_dispatch<MAX, N + 1>(n, f);
+  } else {
+    f(std::integral_constant<int, MAX>{});
+  }
 }
+
+// one launch of a kernel instance whose dynamic LDS may pass the 64 KiB default (limit: what the instance may be given)
+template <auto Kernel, typename Args>
+static void dcn_launch(const Args& a, dim3 grid, int threads, size_t lds, int limit, hipStream_t s) {
+  fami_lds_limit<Kernel>(limit);
+  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, s, a);
+}
+
+// [fami_route_t] g_dcn_ksplit (default 1)  // 2 = the 16-wave K-split build (measured slower: 35.5 vs 29.8 us)
+template <typename T, int NT>
+static void dcn_fwd_win_launch(const DcnWinArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
+  constexpr int NA = NT == 3 ? NT : 3;        // the ablation build (tools/bench_dcn_win.py) exists for <float, 3> only
+  constexpr bool F4 = sizeof(T) == 4;
+  if (NT == 3 && F4 && a.abl) {
+    if (g_dcn_ksplit == 2) dcn_launch<dcn_fwd_win_kernel<T, NA, F4, 2>>(a, grid, 1024, lds, 156 * 1024, s);
+    else dcn_launch<dcn_fwd_win_kernel<T, NA, F4, 1>>(a, grid, 512, lds, 156 * 1024, s);
+  } else if (g_dcn_ksplit == 2) dcn_launch<dcn_fwd_win_kernel<T, NT, false, 2>>(a, grid, 1024, lds, 156 * 1024, s);
+  else dcn_launch<dcn_fwd_win_kernel<T, NT, false, 1>>(a, grid, 512, lds, 156 * 1024, s);
+}
+
+// [fami_route_t] g_dcn_pf (default 0)  // 2 = the 2-k-groups-in-flight x 4-waves-per-SIMD build of the direct kernel (benchmarks)
+template <typename T, int NT>
+static void dcn_fwd_launch(const DcnArgs<T>& a, dim3 grid, size_t lds, size_t lds_direct, bool direct, hipStream_t s) {
+  fami_lds_limit<dcn_fwd_kernel<T, NT>>(150 * 1024);
+  if (!direct) {
+    hipLaunchKernelGGL((dcn_fwd_kernel<T, NT>), grid, dim3(256), lds, s, a);
+    return;
+  }
+  // Measured (tools/bench_dcn.py, B=4 96x72 48 ch): 1 or 2 k groups in flight x 4..7 waves per SIMD all land within
+  // +-1.5 us in f32 (31-34 us: the corner loads run at the L1's one-line-per-cycle rate), bf16 25.0 (1 x 7) vs 27.6 us
+  // (2 x 4).  Default: one k group per wave in flight, 7 workgroups per CU (62 VGPRs, 22.5 KB LDS) -- the 6.75 tiles a
+  // CU owns at B=4 are then all resident at once.  Wide outputs (NT > 3) carry 4*NT accumulator + 4*NT weight registers.
+  if (NT > 3) dcn_launch<dcn_fwd_direct_kernel<T, NT, 1, 4>>(a, grid, 256, lds_direct, 150 * 1024, s);
+  else if (g_dcn_pf == 2) dcn_launch<dcn_fwd_direct_kernel<T, NT, 2, 4>>(a, grid, 256, lds_direct, 150 * 1024, s);
+  else dcn_launch<dcn_fwd_direct_kernel<T, NT, 1, 7>>(a, grid, 256, lds_direct, 150 * 1024, s);
+}
+
+template <typename T, int NCO>
+static void dcn_bwd2_launch(const DcnBwd2Args<T>& a, dim3 grid, size_t lds, hipStream_t s, int stg) {
+  constexpr bool F32 = sizeof(T) == 2;       // 16-bit storage: 32-bit fixed-point region
+  if (stg) dcn_launch<dcn_bwd2_kernel<T, NCO, F32, true>>(a, grid, 256, lds, 64 * 1024, s);
+  else dcn_launch<dcn_bwd2_kernel<T, NCO, F32, false>>(a, grid, 256, lds, 64 * 1024, s);
+}
+
 template <typename T, int KSO>
 static void dcn_bwd_launch(const DcnBwdArgs<T>& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (a.gfix) dcn_bwd_launch1<T, KSO, 1>(a, grid, lds, s);
+  if (a.gfix) dcn_launch<dcn_bwd_kernel<T, KSO, 1>>(a, grid, 256, lds, 150 * 1024, s);
   else if (a.fixl == 2) {
-    if constexpr (sizeof(T) == 2) dcn_bwd_launch1<T, KSO, 3>(a, grid, lds, s);
-  } else if (a.fixl) dcn_bwd_launch1<T, KSO, 2>(a, grid, lds, s);
-  else dcn_bwd_launch1<T, KSO, 0>(a, grid, lds, s);
+    if constexpr (sizeof(T) == 2) dcn_launch<dcn_bwd_kernel<T, KSO, 3>>(a, grid, 256, lds, 150 * 1024, s);
+  } else if (a.fixl) dcn_launch<dcn_bwd_kernel<T, KSO, 2>>(a, grid, 256, lds, 150 * 1024, s);
+  else dcn_launch<dcn_bwd_kernel<T, KSO, 0>>(a, grid, 256, lds, 150 * 1024, s);
+}
+
+// ------------------------------------------------------------------ implementations
+template <typename T>
+static int shift_fwd_impl(const T* src, const float* t, T* out, int B, int H, int W, int C, hipStream_t s,
+                          const char* nm) {
+  FAMI_REQUIRE(src && t && out && B > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0, nm, "bad argument");
+  hipLaunchKernelGGL(shift_fwd_kernel<T>, dim3(fami_ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, s, src, t, out, B, H, W, C);
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
+}
+
+template <typename T>
+static int shift_bwd_impl(const T* gout, const T* src, const float* t, T* gsrc, float* gt, int B, int H, int W, int C,
+                          int acc_src, int acc_t, float* ws, hipStream_t s, const char* nm) {
+  FAMI_REQUIRE(gout && src && t && B > 0 && (C % 4) == 0, nm, "bad argument");
+  if (gsrc) {
+    hipLaunchKernelGGL(shift_bwd_src_kernel<T>, dim3(fami_ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, s, gout, t, gsrc, B, H, W, C, acc_src);
+    FAMI_CHECK_LAUNCH(nm);
+  }
+  if (gt) {
+    FAMI_REQUIRE(ws, nm, "workspace required for gt");
+    long g = ((long)H * W * (C / 4) + 255) / 256;
+    if (g > 256) g = 256;
+    hipLaunchKernelGGL(shift_bwd_t_kernel<T>, dim3((int)g, B), dim3(256), 0, s, gout, src, t, ws, H, W, C);
+    FAMI_CHECK_LAUNCH(nm);
+    hipLaunchKernelGGL(shift_bwd_t_finalize_kernel, dim3(fami_cdiv(B * 2, 64)), dim3(64), 0, s, ws, (int)g, B, gt, acc_t);
+    FAMI_CHECK_LAUNCH(nm);
+  }
+  return FAMI_OK;
+}
+
+// [fami_route_t] g_dcn_gather (default -1)  // 0 = dcn_fwd_kernel (LDS column tile), 1 = dcn_fwd_direct_kernel, 2 = dcn_fwd_win_kernel where eligible, -1 default (= 1)
+// [fami_route_t] g_dcn_abl (default 0)  // ablation bits of the window kernel (DcnWinArgs.abl; tools/bench_dcn_win.py)
+template <typename T>
+static int dcn_fwd_impl(const T* x, const T* off, const T* msk, const float* wp, const float* bias, T* y, int B, int H,
+                        int W, int C, int Co, int G, int kh, int kw, int stride, int pad, int dil, hipStream_t s,
+                        const char* nm, bool merged = false) {
+  FAMI_REQUIRE(x && off && wp && y && B > 0 && G > 0 && C % G == 0, nm, "bad argument");
+  const DcnGeom g = dcn_geom(B, H, W, C, G, kh, kw, stride, pad, dil, merged);
+  if (merged) msk = off + g.moff;
+  const DcnFwdImages L = dcn_fwd_images(Co, C, kh, kw, G);
+  DcnArgs<T> a;
+  a.ostr = g.ostr; a.mstr = g.mstr;
+  a.x = x; a.off = off; a.msk = msk; a.wp = wp; a.bias = bias; a.y = y;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.Co = Co; a.G = G; a.kh = kh; a.kw = kw;
+  a.stride = stride; a.pad = pad; a.dil = dil;
+  a.wp16 = wp + L.w16;
+  a.Ho = g.Ho; a.Wo = g.Wo; a.cg = g.cg;
+  if ((a.cg % 4) != 0 || Co > 96) {
+    fami_set_error(nm, "channels per offset group must be a multiple of 4 and Co <= 96");
+    return FAMI_ESHAPE;
+  }
+  a.KS = L.KS;
+  a.NTt = L.NTt;
+  FAMI_REQUIRE(g.P_ok, nm, "size out of range");
+  const long P = g.P;
+  a.P = (int)P;
+  if (g_dcn_gather == 2) {
+    const DcnWinPlan q = dcn_win_plan(B, a.Ho, a.Wo, C, G, kh, kw, stride, dil, (int)sizeof(T));
+    if (q.ok && a.NTt <= 4 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(off) | reinterpret_cast<uintptr_t>(msk)) & 15) == 0) {
+      DcnWinArgs<T> w;
+      w.x = x; w.off = off; w.msk = msk; w.bias = bias; w.y = y;
+      w.wq = wp + L.wq;
+      w.B = B; w.H = H; w.W = W; w.C = C; w.Ho = a.Ho; w.Wo = a.Wo; w.Co = Co; w.G = G; w.K = kh * kw; w.kw = kw;
+      w.pad = pad; w.dil = dil;
+      w.TH = q.TH; w.TW = q.TW; w.tilesX = q.tilesX; w.tilesY = q.tilesY; w.R = q.R; w.WR = q.WR; w.WC = q.WC; w.PS = q.PS;
+      w.NQ = q.NQ; w.NTt = a.NTt; w.nsub = q.nsub; w.mul_row = q.mul_row; w.mul_px = q.mul_px; w.abl = g_dcn_abl;
+      w.ostr = a.ostr; w.mstr = a.mstr;
+      const dim3 grid(q.tilesX * q.tilesY * B);
+      dcn_dispatch<4>(a.NTt, [&](auto nt) { dcn_fwd_win_launch<T, decltype(nt)::value>(w, grid, q.lds, s); });
+      FAMI_CHECK_LAUNCH(nm);
+      return FAMI_OK;
+    }
+  }
+  const dim3 grid(fami_cdiv(P, DCN_PIX));
+  // the direct kernel addresses x with 32-bit byte offsets (24-bit row / column products)
+  const size_t lds = ((size_t)DCN_PIX * (a.KS * 16 + 4) + 4 * (size_t)a.NTt * 256) * sizeof(float);
+  size_t lds_direct = (((size_t)DCN_PIX * G * kh * kw * 3 * sizeof(T) + 15) & ~(size_t)15) + (size_t)a.KS * 4 * sizeof(int4);
+  if (lds_direct < 4 * (size_t)a.NTt * 256 * sizeof(float)) lds_direct = 4 * (size_t)a.NTt * 256 * sizeof(float);
+  const bool direct = g_dcn_gather != 0 && (long)B * H * W * C * sizeof(T) < (1L << 32) &&
+                      (long)H * W * C * sizeof(T) < (1L << 24) && lds_direct <= 150 * 1024;
+  if (!direct && lds > 150 * 1024) {
+    fami_set_error(nm, "C*kh*kw too large for the LDS column tile");
+    return FAMI_ESHAPE;
+  }
+  dcn_dispatch<6>(a.NTt, [&](auto nt) { dcn_fwd_launch<T, decltype(nt)::value>(a, grid, lds, lds_direct, direct, s); });
+  FAMI_CHECK_LAUNCH(nm);
+  return FAMI_OK;
 }
 
 template <typename T>
@@ -1981,21 +2022,9 @@ static int dcn_bwd_impl(const T* x, const T* off, const T* msk, const T* dy, con
   // general: the caller sized `col` for dcn_bwd_kernel ([P][C K], tap-major: what fami_dcn_bwd_col_width / _col_permuted report
   // for the deterministic mode) -- the register-fed kernel, which writes its own column order q.colw wide, must not take it
   FAMI_REQUIRE(x && off && dy && wpb && B > 0 && G > 0 && C % G == 0, nm, "bad argument");
-  DcnBwdArgs<T> a;
-  // merged: off / goff are ONE tensor each, [P][2GK offsets | GK masks] (merged predictor output and its gradient)
-  a.ostr = (merged ? 3 : 2) * G * kh * kw;
-  a.mstr = (merged ? 3 : 1) * G * kh * kw;
-  if (merged) {
-    msk = off + 2 * G * kh * kw;
-    gmsk = goff ? goff + 2 * G * kh * kw : nullptr;
-  }
-  a.gfix = gfix; a.amax_bits = amax_bits;
-  a.x = x; a.off = off; a.msk = msk; a.dy = dy; a.wpb = wpb; a.col = col; a.gx = gx; a.goff = goff; a.gmsk = gmsk;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.Co = Co; a.G = G; a.kh = kh; a.kw = kw;
-  a.stride = stride; a.pad = pad; a.dil = dil; a.acc_off = acc_off;
-  a.Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  a.Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-  a.cg = C / G;
+  const DcnGeom g = dcn_geom(B, H, W, C, G, kh, kw, stride, pad, dil, merged);
+  if (merged) msk = off + g.moff, gmsk = goff ? goff + g.moff : nullptr;
+  const DcnBwdImages L = dcn_bwd_images(Co, C, kh, kw, G);
   const int K = kh * kw;
   {
     // register-fed kernel (default): the non-deterministic fixed-point scatter on the shapes it is built for
@@ -2005,29 +2034,27 @@ static int dcn_bwd_impl(const T* x, const T* off, const T* msk, const T* dy, con
       FAMI_REQUIRE((long)H * W * C * sizeof(T) < (1L << 32) && (long)W * C * sizeof(T) < (1L << 24), nm, "frame too large");
       DcnBwd2Args<T> n;
       n.x = x; n.off = off; n.msk = msk; n.dy = dy; n.col = col; n.gx = gx; n.goff = goff; n.gmsk = gmsk;
-      const long oldn = dcn_bwd_old_image_elems(Co, C, kh, kw);
-      n.wnorm = wpb + oldn - 4;
-      const DcnBwd2Plan q4 = dcn_bwd2_plan(C, Co, G, kh, kw, stride, dil, 4);
-      n.wimg = wpb + oldn + (sizeof(T) == 4 ? 0 : dcn_bwd2_image_elems(q4, 4));
-      n.B = B; n.H = H; n.W = W; n.C = C; n.Ho = a.Ho; n.Wo = a.Wo; n.Co = Co; n.G = G; n.K = K; n.kw = kw;
-      n.pad = pad; n.dil = dil; n.ostr = a.ostr; n.mstr = a.mstr; n.acc_off = acc_off;
+      n.wnorm = wpb + L.wnorm;
+      n.wimg = wpb + (sizeof(T) == 4 ? L.img32 : L.img16);
+      n.B = B; n.H = H; n.W = W; n.C = C; n.Ho = g.Ho; n.Wo = g.Wo; n.Co = Co; n.G = G; n.K = K; n.kw = kw;
+      n.pad = pad; n.dil = dil; n.ostr = g.ostr; n.mstr = g.mstr; n.acc_off = acc_off;
       n.GC = q.GC; n.nchunk = q.nchunk; n.NQ = q.NQ; n.colw = q.colw;
-      n.tilesX = fami_cdiv(a.Wo, 8); n.tilesY = fami_cdiv(a.Ho, 8); n.RH = q.RH; n.RW = q.RW; n.CS = q.CS;
+      n.tilesX = fami_cdiv(g.Wo, 8); n.tilesY = fami_cdiv(g.Ho, 8); n.RH = q.RH; n.RW = q.RW; n.CS = q.CS;
       const dim3 grid(n.tilesX * n.tilesY * B, q.nchunk);
-      switch (Co / 16) {
-        case 1: dcn_bwd2_launch<T, 1>(n, grid, q.lds, s, q.stg); break;
-        case 2: dcn_bwd2_launch<T, 2>(n, grid, q.lds, s, q.stg); break;
-        case 3: dcn_bwd2_launch<T, 3>(n, grid, q.lds, s, q.stg); break;
-        case 4: dcn_bwd2_launch<T, 4>(n, grid, q.lds, s, q.stg); break;
-        case 5: dcn_bwd2_launch<T, 5>(n, grid, q.lds, s, q.stg); break;
-        default: dcn_bwd2_launch<T, 6>(n, grid, q.lds, s, q.stg); break;
-      }
+      dcn_dispatch<6>(Co / 16, [&](auto nco) { dcn_bwd2_launch<T, decltype(nco)::value>(n, grid, q.lds, s, q.stg); });
       FAMI_CHECK_LAUNCH(nm);
       return FAMI_OK;
     }
   }
+  DcnBwdArgs<T> a;
+  a.ostr = g.ostr; a.mstr = g.mstr;
+  a.gfix = gfix; a.amax_bits = amax_bits;
+  a.x = x; a.off = off; a.msk = msk; a.dy = dy; a.wpb = wpb; a.col = col; a.gx = gx; a.goff = goff; a.gmsk = gmsk;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.Co = Co; a.G = G; a.kh = kh; a.kw = kw;
+  a.stride = stride; a.pad = pad; a.dil = dil; a.acc_off = acc_off;
+  a.Ho = g.Ho; a.Wo = g.Wo; a.cg = g.cg;
   a.GC = (a.cg % 4 == 0) ? dcn_bwd_chunk_groups(G, a.cg, K) : 0;
-  a.KSo = fami_cdiv(Co, 16);
+  a.KSo = L.KSo;
   if (a.GC == 0 || a.KSo > 6) {
     fami_set_error(nm, "unsupported channel grouping (need cg % 4 == 0, a 16-aligned group chunk, Co <= 96)");
     return FAMI_ESHAPE;
@@ -2036,7 +2063,7 @@ static int dcn_bwd_impl(const T* x, const T* off, const T* msk, const T* dy, con
   a.tilesX = fami_cdiv(a.Wo, DCN_TILE); a.tilesY = fami_cdiv(a.Ho, DCN_TILE);
   a.RH = (DCN_TILE - 1) * stride + (kh - 1) * dil + 2 + 2 * DCN_RO;
   a.RW = (DCN_TILE - 1) * stride + (kw - 1) * dil + 2 + 2 * DCN_RO;
-  a.wnorm = wpb + (long)fami_cdiv((long)C * K, 16) * a.KSo * 256;       // written by fami_dcn_pack_weight_bwd_f32 behind the image
+  a.wnorm = wpb + L.wnorm;
   a.fixl = (!gfix && gx && g_dcn_bwd_scatter != 0) ? 1 : 0;
   // 16-bit storage: a 32-bit fixed-point region (20 bits per contribution at the bound: ~2^-17 of the largest one, far
   // below bf16 / fp16 resolution) -- half the LDS (4 workgroups per CU instead of 2) and ds_add_u32 (4.7 against 2.5
@@ -2053,14 +2080,7 @@ static int dcn_bwd_impl(const T* x, const T* off, const T* msk, const T* dy, con
     return FAMI_ESHAPE;
   }
   const dim3 grid(a.tilesX * a.tilesY * B, G / a.GC);
-  switch (a.KSo) {
-    case 1: dcn_bwd_launch<T, 1>(a, grid, lds, s); break;
-    case 2: dcn_bwd_launch<T, 2>(a, grid, lds, s); break;
-    case 3: dcn_bwd_launch<T, 3>(a, grid, lds, s); break;
-    case 4: dcn_bwd_launch<T, 4>(a, grid, lds, s); break;
-    case 5: dcn_bwd_launch<T, 5>(a, grid, lds, s); break;
-    default: dcn_bwd_launch<T, 6>(a, grid, lds, s); break;
-  }
+  dcn_dispatch<6>(a.KSo, [&](auto kso) { dcn_bwd_launch<T, decltype(kso)::value>(a, grid, lds, s); });
   FAMI_CHECK_LAUNCH(nm);
   return FAMI_OK;
 }
@@ -2077,10 +2097,10 @@ static int dcn_bwd_det_impl(const T* x, const T* off, const T* msk, const T* dy,
   long long* gfix = gx ? reinterpret_cast<long long*>(ws) : nullptr;
   unsigned* amax = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + n * 8);
   if (!gx) return dcn_bwd_impl<T>(x, off, msk, dy, wpb, col, nullptr, goff, gmsk, B, H, W, C, Co, G, kh, kw, stride, pad, dil, acc_off, s, nm, nullptr, nullptr, merged, true);      // (no input gradient: nothing order-dependent is left, but `col` keeps the deterministic mode's layout)
-  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+  const DcnGeom g = dcn_geom(B, H, W, C, G, kh, kw, stride, pad, dil, merged);
   hipLaunchKernelGGL(zero_u64_kernel, dim3(fami_ew_grid(n)), dim3(256), 0, s, reinterpret_cast<unsigned long long*>(gfix), n, amax);
   FAMI_CHECK_LAUNCH(nm);
-  const long ndy = (long)B * Ho * Wo * Co;
+  const long ndy = g.P * Co;
   hipLaunchKernelGGL(absmax_kernel<T>, dim3(fami_ew_grid(ndy) < 256 ? fami_ew_grid(ndy) : 256), dim3(256), 0, s, dy, ndy, amax);
   FAMI_CHECK_LAUNCH(nm);
   const int rc = dcn_bwd_impl<T>(x, off, msk, dy, wpb, col, nullptr, goff, gmsk, B, H, W, C, Co, G, kh, kw, stride, pad, dil, acc_off, s, nm, gfix, amax, merged);
@@ -2090,43 +2110,43 @@ static int dcn_bwd_det_impl(const T* x, const T* off, const T* msk, const T* dy,
   return FAMI_OK;
 }
 
-extern "C" int fami_dcn_pack_weight_f32(const float* w_oihw, float* wp, int Co, int C, int kh, int kw, int G, hipStream_t s);
+// forward weight images: the two fp32 ones (for every activation type: the f32 contraction runs on the exact f32 MFMA)
+// (one name in the refusals and launch errors, whichever entry point packs)
+static int dcn_pack_w32_impl(const float* w_oihw, float* wp, int Co, int C, int kh, int kw, int G, hipStream_t s) {
+  FAMI_REQUIRE(w_oihw && wp && G > 0 && C % G == 0 && ((C / G) % 4) == 0, "fami_dcn_pack_weight_f32", "channels per offset group must be a multiple of 4");
+  const DcnFwdImages L = dcn_fwd_images(Co, C, kh, kw, G);
+  const int K = kh * kw;
+  hipLaunchKernelGGL(dcn_pack_w_kernel, dim3(fami_ew_grid(L.wq)), dim3(256), 0, s, w_oihw, wp, Co, C, K, C / G, L.KS, L.NTt);
+  FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_f32");
+  hipLaunchKernelGGL(dcn_pack_wq_kernel, dim3(fami_ew_grid(L.w16 - L.wq)), dim3(256), 0, s, w_oihw, wp + L.wq, Co, C, K, G, L.NQ, L.NTt);
+  FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_f32/quad");
+  return FAMI_OK;
+}
+// ... plus the 16-bit image the bf16 / fp16 forward contracts with
 template <typename H>
 static int dcn_pack_w16_impl(const char* nm, const float* w_oihw, float* wp, int Co, int C, int kh, int kw, int G, hipStream_t s) {
-  const int rc = fami_dcn_pack_weight_f32(w_oihw, wp, Co, C, kh, kw, G, s);
+  const int rc = dcn_pack_w32_impl(w_oihw, wp, Co, C, kh, kw, G, s);
   if (rc != FAMI_OK) return rc;
-  const int K = kh * kw, KS32 = fami_cdiv(fami_cdiv((long)C * K, 16), 2), NTt = fami_cdiv(Co, 16);
-  H* w16 = reinterpret_cast<H*>(wp + dcn_f32_image_elems(Co, C, kh, kw, G));
-  hipLaunchKernelGGL(dcn_pack_w16_kernel<H>, dim3(fami_ew_grid((long)KS32 * NTt * 512)), dim3(256), 0, s, w_oihw, w16, Co, C, K, C / G, KS32, NTt);
+  const DcnFwdImages L = dcn_fwd_images(Co, C, kh, kw, G);
+  hipLaunchKernelGGL(dcn_pack_w16_kernel<H>, dim3(fami_ew_grid((long)L.KS32 * L.NTt * 512)), dim3(256), 0, s, w_oihw,
+                     reinterpret_cast<H*>(wp + L.w16), Co, C, kh * kw, C / G, L.KS32, L.NTt);
   FAMI_CHECK_LAUNCH(nm);
   return FAMI_OK;
 }
+
+// ------------------------------------------------------------------ C ABI
 extern "C" {
 
 long fami_dcn_bwd_det_workspace(int B, int H, int W, int C) { return (long)B * H * W * C * 8 + 16; }
 
 long fami_shift_workspace(int B) { return (long)B * 256 * 2 * (long)sizeof(float); }
 
-// two fp32 images: tap-major (dcn_fwd_kernel / dcn_fwd_direct_kernel) followed by quad-group order (dcn_fwd_win_kernel);
-// behind them the 16-bit tap-major image of the 16-bit modes (256 floats' worth per 32-step and channel tile)
-long fami_dcn_packed_weight_elems(int Co, int C, int kh, int kw, int G) {
-  const long nt = fami_cdiv(Co, 16);
-  return dcn_f32_image_elems(Co, C, kh, kw, G) + (long)fami_cdiv(fami_cdiv((long)C * kh * kw, 16), 2) * nt * 256;
-}
+long fami_dcn_packed_weight_elems(int Co, int C, int kh, int kw, int G) { return dcn_fwd_images(Co, C, kh, kw, G).total; }
 
-// forward weight image (fp32 for both activation types: the contraction runs on the exact f32 MFMA)
 int fami_dcn_pack_weight_f32(const float* w_oihw, float* wp, int Co, int C, int kh, int kw, int G, hipStream_t s) {
-  FAMI_REQUIRE(w_oihw && wp && G > 0 && C % G == 0 && ((C / G) % 4) == 0, "fami_dcn_pack_weight_f32", "channels per offset group must be a multiple of 4");
-  const int K = kh * kw, cg = C / G, KS16 = fami_cdiv((long)C * K, 16), NTt = fami_cdiv(Co, 16);
-  const long total = (long)KS16 * NTt * 256;
-  hipLaunchKernelGGL(dcn_pack_w_kernel, dim3(fami_ew_grid(total)), dim3(256), 0, s, w_oihw, wp, Co, C, K, cg, KS16, NTt);
-  FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_f32");
-  const int NQ = fami_cdiv((long)G * K, 16);
-  hipLaunchKernelGGL(dcn_pack_wq_kernel, dim3(fami_ew_grid((long)NQ * 4 * NTt * 256)), dim3(256), 0, s, w_oihw, wp + total, Co, C, K, G, NQ, NTt);
-  FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_f32/quad");
-  return FAMI_OK;
+  return dcn_pack_w32_impl(w_oihw, wp, Co, C, kh, kw, G, s);
 }
-// the fp32 images plus the 16-bit image the bf16 / fp16 forward contracts with (wp: fami_dcn_packed_weight_elems floats)
+// (wp: fami_dcn_packed_weight_elems floats for all three)
 int fami_dcn_pack_weight_bf16(const float* w_oihw, float* wp, int Co, int C, int kh, int kw, int G, hipStream_t s) {
   return dcn_pack_w16_impl<bf16_t>("fami_dcn_pack_weight_bf16", w_oihw, wp, Co, C, kh, kw, G, s);
 }
@@ -2134,51 +2154,34 @@ int fami_dcn_pack_weight_f16(const float* w_oihw, float* wp, int Co, int C, int 
   return dcn_pack_w16_impl<f16_t>("fami_dcn_pack_weight_f16", w_oihw, wp, Co, C, kh, kw, G, s);
 }
 
-// benchmarks / tests: 0 = dcn_fwd_kernel (LDS column tile), 1 = dcn_fwd_direct_kernel (register-fed MFMA), -1 = default;
-// 16 + 2 / 16 + 0 = the (2 k groups in flight, 4 waves per SIMD) build of the direct kernel / the default build
+// benchmarks / tests; the table of codes is in include/fami.h
 int fami_dcn_tune(int gather) {
-  if (gather < 0) {   // every DCN knob back to its default
-    g_dcn_bwd_abl = 0; g_dcn_bwd_scatter = -1; g_dcn_ksplit = 1; g_dcn_abl = 0; g_dcn_win_r = 0; g_dcn_pf = 0; g_dcn_gather = -1; g_dcn_bwd2 = 1; g_dcn_bwd2_cap = 36; g_dcn_bwd2_stage = 1;
-    return FAMI_OK;
-  }
-  if (gather >= 8192) g_dcn_bwd2_stage = gather - 8192;
-  else if (gather >= 4096) g_dcn_bwd2_cap = gather - 4096;
-  else if (gather >= 2048) g_dcn_bwd2 = gather - 2048;
-  else if (gather >= 1024) g_dcn_bwd_abl = gather - 1024;
-  else if (gather >= 512) g_dcn_bwd_scatter = gather - 512;
-  else if (gather >= 256) g_dcn_ksplit = gather - 256;
-  else if (gather >= 64) g_dcn_abl = gather - 64;
-  else if (gather >= 32) g_dcn_win_r = gather - 32;       // benchmarks: offset reach of the window kernel (0 = automatic)
-  else if (gather >= 16) g_dcn_pf = gather - 16;
-  else g_dcn_gather = gather;
+  fami_route_t* r = fami_rt();
+  if (gather < 0) fami_route_set_dcn_defaults(r);   // every DCN knob back to its default
+  else if (gather >= 8192) r->dcn_bwd2_stage = gather - 8192;
+  else if (gather >= 4096) r->dcn_bwd2_cap = gather - 4096;
+  else if (gather >= 2048) r->dcn_bwd2 = gather - 2048;
+  else if (gather >= 1024) r->dcn_bwd_abl = gather - 1024;
+  else if (gather >= 512) r->dcn_bwd_scatter = gather - 512;
+  else if (gather >= 256) r->dcn_ksplit = gather - 256;
+  else if (gather >= 64) r->dcn_abl = gather - 64;
+  else if (gather >= 32) r->dcn_win_r = gather - 32;
+  else if (gather >= 16) r->dcn_pf = gather - 16;
+  else r->dcn_gather = gather;
   return FAMI_OK;
 }
 
-// the image of dcn_pack_wb_kernel + 4 floats: [0] = max_k sum_co |W[co][k]| (fixed-point scale bound of dcn_bwd_kernel)
-long fami_dcn_packed_weight_bwd_elems(int Co, int C, int kh, int kw, int G) {
-  // + the two images of the register-fed kernel (f32 storage / 16-bit storage: other chunking, other MFMA shape); sized for the
-  // head's geometry (stride 1, dilation = padding): the plan does not depend on anything else
-  long n = dcn_bwd_old_image_elems(Co, C, kh, kw);
-  for (int esz = 4; esz >= 2; esz -= 2) {
-    const int keep = g_dcn_bwd2;
-    g_dcn_bwd2 = 1;
-    n += dcn_bwd2_image_elems(dcn_bwd2_plan(C, Co, G, kh, kw, 1, 3, esz), esz);
-    g_dcn_bwd2 = keep;
-  }
-  return n;
-}
+long fami_dcn_packed_weight_bwd_elems(int Co, int C, int kh, int kw, int G) { return dcn_bwd_images(Co, C, kh, kw, G).total; }
 /* columns of the `col` matrix fami_dcn_bwd_* writes for this geometry and storage size: C*kh*kw (weight.view(Co, C*K) order) on
  * the general kernel, more (the register-fed kernel's own column order, padded) otherwise -- then the 1x1 weight gradient over
  * col is [Co][cols] and fami_dcn_col_dw_unpermute_f32 brings it into OIHW order */
 long fami_dcn_bwd_col_width(int C, int Co, int G, int kh, int kw, int stride, int dil, int elem_bytes, int deterministic) {
-  if (deterministic || !dcn_bwd2_on(elem_bytes)) return (long)C * kh * kw;
-  return dcn_bwd2_plan(C, Co, G, kh, kw, stride, dil, elem_bytes).colw;
+  return dcn_bwd_col_plan(C, Co, G, kh, kw, stride, dil, elem_bytes, deterministic).colw;
 }
 /* 1: col is in the register-fed kernel's column order (fami_dcn_col_dw_unpermute_f32 needed), 0: weight.view(Co, C*K) order.  (The
  * widths alone do not tell: with four groups per workgroup the permuted matrix is exactly C*K wide.) */
 int fami_dcn_bwd_col_permuted(int C, int Co, int G, int kh, int kw, int stride, int dil, int elem_bytes, int deterministic) {
-  if (deterministic || !dcn_bwd2_on(elem_bytes)) return 0;
-  return dcn_bwd2_plan(C, Co, G, kh, kw, stride, dil, elem_bytes).ok ? 1 : 0;
+  return dcn_bwd_col_plan(C, Co, G, kh, kw, stride, dil, elem_bytes, deterministic).ok ? 1 : 0;
 }
 int fami_dcn_col_dw_unpermute_f32(const float* dwp, float* dw, int Co, int C, int G, int kh, int kw, int stride, int dil,
                                   int elem_bytes, int accumulate, hipStream_t s) {
@@ -2191,29 +2194,23 @@ int fami_dcn_col_dw_unpermute_f32(const float* dwp, float* dw, int Co, int C, in
   return FAMI_OK;
 }
 
-// weight image of the backward column-gradient GEMM (see dcn_pack_wb_kernel)
+// every image of the backward weight buffer (DcnBwdImages)
 int fami_dcn_pack_weight_bwd_f32(const float* w_oihw, float* wpb, int Co, int C, int kh, int kw, int G,
                                  hipStream_t s) {
   FAMI_REQUIRE(w_oihw && wpb && G > 0 && C % G == 0 && ((C / G) % 4) == 0, "fami_dcn_pack_weight_bwd_f32", "channels per offset group must be a multiple of 4");
-  const int K = kh * kw, cg = C / G, NT = fami_cdiv((long)C * K, 16), KSo = fami_cdiv(Co, 16);
-  const long total = (long)NT * KSo * 256;
-  hipLaunchKernelGGL(dcn_pack_wb_kernel, dim3(fami_ew_grid(total)), dim3(256), 0, s, w_oihw, wpb, Co, C, K, cg, NT, KSo);
+  const DcnBwdImages L = dcn_bwd_images(Co, C, kh, kw, G);
+  const int K = kh * kw;
+  hipLaunchKernelGGL(dcn_pack_wb_kernel, dim3(fami_ew_grid(L.wnorm)), dim3(256), 0, s, w_oihw, wpb, Co, C, K, C / G, L.NT, L.KSo);
   FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_bwd_f32");
-  hipLaunchKernelGGL(dcn_wnorm_kernel, dim3(1), dim3(256), 0, s, w_oihw, wpb + total, Co, C * K);
+  hipLaunchKernelGGL(dcn_wnorm_kernel, dim3(1), dim3(256), 0, s, w_oihw, wpb + L.wnorm, Co, C * K);
   FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_bwd_f32/norm");
-  float* img = wpb + total + 4;
-  for (int esz = 4; esz >= 2; esz -= 2) {
-    const int keep = g_dcn_bwd2;
-    g_dcn_bwd2 = 1;
-    const DcnBwd2Plan q = dcn_bwd2_plan(C, Co, G, kh, kw, 1, 3, esz);
-    g_dcn_bwd2 = keep;
-    const long n = dcn_bwd2_image_elems(q, esz);
-    if (n > 0) {
-      hipLaunchKernelGGL(dcn_pack_wb2_kernel, dim3(fami_ew_grid(n)), dim3(256), 0, s, w_oihw, img, Co, C, K, q.GC, q.nchunk, q.NQ, q.NJ,
-                         esz == 2 ? 1 : 0);
-      FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_bwd_f32/register-fed image");
-      img += n;
-    }
+  const struct { const DcnBwd2Plan& q; long at, n; int half; } imgs[2] = {{L.q32, L.img32, L.img16 - L.img32, 0},
+                                                                        {L.q16, L.img16, L.total - L.img16, 1}};
+  for (const auto& im : imgs) {
+    if (im.n <= 0) continue;
+    hipLaunchKernelGGL(dcn_pack_wb2_kernel, dim3(fami_ew_grid(im.n)), dim3(256), 0, s, w_oihw, wpb + im.at, Co, C, K, im.q.GC,
+                       im.q.nchunk, im.q.NQ, im.q.NJ, im.half);
+    FAMI_CHECK_LAUNCH("fami_dcn_pack_weight_bwd_f32/register-fed image");
   }
   return FAMI_OK;
 }

@@ -371,12 +371,25 @@ int fami_dcn_pack_weight_f16(const float* w_oihw, float* wp, int Co, int C, int 
 int fami_dcn_fwd_f32(const float* x, const float* off, const float* msk, const float* wp, const float* bias, float* y,
                      int B, int H, int W, int C, int Co, int G, int kh, int kw, int stride, int pad, int dil,
                      fami_stream_t stream);
-int fami_dcn_tune(int mode);            /* benchmarks / tests: forward kernel 0 = dcn_fwd_kernel (LDS column tile), 1 = dcn_fwd_direct_kernel
-                                           (samples fed to the MFMA from registers), -1 = default (direct below 4 GiB);
-                                           16 + 2 / 16 + 0 = direct kernel built for 2 k groups in flight x 4 waves per SIMD / default build;
-                                           2 = LDS-window forward kernel where eligible; 512 + m = backward input-gradient scatter: 0 f32
-                                           compare-and-swap LDS region, 1 fixed-point region (64-bit for f32, 32-bit for 16-bit storage; default),
-                                           2 64-bit region for every type; 1024 + bits = backward ablations (benchmarks) */
+/* Benchmarks / tests: one integer code per call, each writing one align.hip field of the route bound to the calling thread
+ * (include/fami_route.h).  Always returns 0.
+ *   any negative  every DCN field back to its default
+ *   0 / 1 / 2     dcn_gather: forward on dcn_fwd_kernel (LDS column tile) / dcn_fwd_direct_kernel (samples fed to the MFMA from
+ *                 registers; the default below 4 GiB) / dcn_fwd_win_kernel (LDS window) where eligible, else the direct kernel
+ *   16 + n        dcn_pf: n = 2 the direct kernel built for 2 k groups in flight x 4 waves per SIMD, n = 0 the default build
+ *   32 + r        dcn_win_r: force the window kernel's offset reach to r pixels (0 = the largest that fits, up to 4)
+ *   64 + bits     dcn_abl: ablation bits of the window kernel (1 no MFMA, 2 no LDS gather, 4 no offset stream, 8 no window
+ *                 fill, 16 constant weights, 32 no loop; f32 with Co in 33..48 only)
+ *   256 + k       dcn_ksplit: k = 2 the 16-wave K-split build of the window kernel, k = 1 the default 8-wave build
+ *   512 + m       dcn_bwd_scatter, the backward's input-gradient scatter: m = 0 f32 compare-and-swap LDS region, 1 fixed-point
+ *                 region (64-bit for f32, 32-bit for 16-bit storage; the default), 2 64-bit region for every type.  Only the
+ *                 default runs on the register-fed backward kernel; the others select the general kernel
+ *   1024 + bits   dcn_bwd_abl: ablations of the general backward kernel (1 no region flush, 2 no LDS adds, 4 constant scale)
+ *   2048 + n      dcn_bwd2: the register-fed backward kernel off (n = 0) / on (n = 1, default)
+ *   4096 + KB     dcn_bwd2_cap: LDS budget of the register-fed kernel's region (default 36; decides the groups per workgroup
+ *                 and with them the weight image: set BEFORE fami_dcn_pack_weight_bwd_f32)
+ *   8192 + n      dcn_bwd2_stage: offset / mask gradients of the register-fed kernel staged in LDS off (0) / on (1, default) */
+int fami_dcn_tune(int mode);
 long fami_dcn_packed_weight_bwd_elems(int Co, int C, int kh, int kw, int G);
 int fami_dcn_pack_weight_bwd_f32(const float* w_oihw, float* wpb, int Co, int C, int kh, int kw, int G,
                                  fami_stream_t stream);
