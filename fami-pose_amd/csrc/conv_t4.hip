@@ -35,6 +35,7 @@ struct ConvT4Args {
   int sgn, relu, accumulate, out_f32;
   int dil;            // dilation (= padding: the centred 3x3 kernels of the path; 1 for the HRNet blocks, 3 for the DCN predictors)
   int patch_bytes;
+  const void* wsp;    // WD instances: the pre-split weight image [tap][KC][NTt] blocks of 1536 bytes (conv_t5.hip), behind the fragment image
   long long* dbg;     // FAMI_T4_TRACE builds: phase timestamps of one workgroup (null otherwise)
 };
 
@@ -87,6 +88,12 @@ template <> struct T4Traits<float> {
 // one 8-wave workgroup changed nothing.  With 100 KiB of LDS per workgroup there is one workgroup and two waves per
 // SIMD on a CU, and the phases of a chunk (loads -> split -> LDS stores -> barrier -> LDS reads -> MFMAs) add up instead of
 // overlapping: MFMA floor 13.7 us + LDS reads 12 us + LDS stores 4 us + staging.
+// The weight side of that staging -- fetch, split and store of 9 * NT * 64 pieces per chunk, 57 % (24x18 maps) to 74 % (12x9 maps) of
+// what a chunk stages, repeated by every workgroup of a channel block -- is gone in the WD instances (below): the pre-split image
+// by LDS DMA.  Per launch, persistent kernel off, register -> DMA form (tools/bench_band_wdma.py, profiles/band_wdma/): 192 ch
+// @24x18 53.6 -> 49.3 us, 384 ch @12x9 69.3 -> 61.0, the head's 4-frame 48 ch @96x72 12.9 -> 12.0; in the f32 step's trace the band
+// kernel's launches 13.56 -> 12.83 ms per step, the step 44.07-44.25 -> 43.08-43.76 ms (six alternating pairs).  What remains per
+// chunk is the patch: loads, XBN, split, 3 ds_write per piece, and the two barriers around them.
 typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 struct T4Split { bf16x4v h[3]; };
 __device__ __forceinline__ T4Split t4_split(u32x4 raw) {
@@ -113,20 +120,30 @@ __device__ __forceinline__ void t4_split_store(char* dst, int plane_bytes, const
 // (tools/bench_t4.py "s3pc"): two buffers leave room for 8-tile bands only -- 1080 workgroups at 48 channels @96x72, each
 // paying its prologue and the 41 KB weight staging for 128 pixels -- 65 us against 44-52; 59-62 against 68 us on the 12x9
 // maps (one band, 24 chunks); f32 step equal with it on the one-band maps.  Off (fami_conv_tune_lds(61 / 62) to try).
-template <typename H, int NT, int PM, bool S3 = false, int WV = 8, int MTT = 2, bool PC = false>
+// WD (split-product instance, not PC): the weights come PRE-SPLIT from the packed image (fami_split_image_elems: the three bf16
+// planes of every weight, written once per step by the weight pack) and go global -> LDS by DMA (global_load_lds_dwordx4, 1 KiB per
+// wave instruction) into one of TWO weight buffers: no registers (wr), no split arithmetic and no ds_write for the weight side of
+// a chunk -- 57-74 % of the 16-byte pieces a chunk stages on the low-resolution maps, repeated by each of the 20-40 workgroups
+// that share a channel block.  A (tap, channel tile) block keeps the image's layout in LDS (1536 bytes: plane p at p * 512, row
+// n at n * 32 -- conv_t5_dev.h's), the same 32-byte rows as the register form's planes, so the fragment reads, the MFMA sequence
+// and every accumulator's order are the register form's: bitwise the same results (the pack kernel's split is t4_split's three
+// roundings).  Chunk c multiplies out of buffer c & 1 while the DMA of chunk c + 1 fills the other one (see the chunk loop).
+template <typename H, int NT, int PM, bool S3 = false, int WV = 8, int MTT = 2, bool PC = false, bool WD = false>
 __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t4_kernel(ConvT4Args p) {
   constexpr int THREADS = WV * 64;
   static_assert(!PC || (S3 && MTT == 2), "producer / consumer waves: split-product instance, 2 tiles per wave");
+  static_assert(!WD || (S3 && !PC), "weights by DMA: split-product instance, not the producer / consumer form");
   constexpr int CW = PC ? WV / 2 : WV;                 // waves that multiply
   constexpr int STH = PC ? (WV - CW) * 64 : THREADS;   // threads that stage
   typedef typename T4Traits<H>::frag frag;
   static_assert(!S3 || sizeof(H) == 4, "the split instance takes f32 storage");
   constexpr int SZ = (int)sizeof(H), CHN = 64 / SZ, PCN = 16 / SZ;   // bytes per element, channels per chunk / per piece
-  constexpr int WBLK = S3 ? 16 * T4_S3_ROW : 1024;                   // LDS bytes of one (tap, channel tile) weight block (S3: per plane)
-  constexpr int WPL = 9 * NT * WBLK;                                 // S3: bytes of one weight plane
+  constexpr int WBLK = WD ? 3 * 16 * T4_S3_ROW : (S3 ? 16 * T4_S3_ROW : 1024);   // LDS bytes of one (tap, channel tile) weight block (S3: per plane; WD: its three planes)
+  constexpr int WPL = WD ? 16 * T4_S3_ROW : 9 * NT * WBLK;           // S3: plane stride of the weights (WD: inside a block)
+  constexpr int WSLAB = 9 * NT * 3 * 16 * T4_S3_ROW;                 // S3: bytes of a chunk's weights (WD: of one of the two buffers)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int WPC = 9 * NT * 64;               // 16-byte weight pieces per chunk
-  constexpr int WR = (WPC + STH - 1) / STH;
+  constexpr int WR = WD ? 0 : (WPC + STH - 1) / STH;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool producer = PC && wave >= CW;              // wave-uniform
@@ -190,7 +207,7 @@ __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t
   }
   const int nchunk = (p.Ci + CHN - 1) / CHN;
   // (PC: two register sets, so that chunk c + 2 is requested BEFORE chunk c + 1 is split and stored)
-  u32x4 pr[PC ? 2 : 1][PM], wr[PC ? 2 : 1][WR];
+  u32x4 pr[PC ? 2 : 1][PM], wr[PC ? 2 : 1][WR ? WR : 1];
   typedef std::integral_constant<int, 0> Set0;
   typedef std::integral_constant<int, (PC ? 1 : 0)> Set1;
   auto fetch = [&](int c, auto setc) {
@@ -217,9 +234,42 @@ __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t
     }
   };
   if (!PC || producer) fetch(0, Set0());
+  // WD: DMA plan of a chunk's weights.  This wave copies the 1 KiB pieces wave, wave + WV, ... of the buffer (the nine taps' NT
+  // blocks back to back); a tap's NT blocks are contiguous in the image.  Lanes past the buffer's end and lanes of a channel
+  // tile past the weight's last one (Co = 216 / 108) are predicated off: those blocks are zeroed once, here, in both buffers
+  // (the register form stored zeros there).  Issued AFTER the patch loads: the patch store waits for the older requests only.
+  constexpr int WPW = ((WSLAB + 1023) / 1024 + WV - 1) / WV;
+  int wsrc[WD ? WPW : 1];
+  auto dma_w = [&](int c, char* slab) {
+    const char* src = reinterpret_cast<const char*>(p.wsp) + ((long)c * p.NTt + ntg0) * WBLK;
+#pragma unroll
+    for (int k = 0; k < WPW; ++k) {
+      if ((wave + WV * k) * 1024 < WSLAB) {           // wave-uniform
+        if (wsrc[k] >= 0)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + wsrc[k]),
+                                           (__attribute__((address_space(3))) void*)(slab + (wave + WV * k) * 1024), 16, 0, 0);
+      }
+    }
+  };
+  if constexpr (WD) {
+#pragma unroll
+    for (int k = 0; k < WPW; ++k) {
+      const int b = (wave + WV * k) * 1024 + lane * 16;
+      const int blk = b / WBLK, within = b - blk * WBLK;
+      const int tap = blk / NT, nt = blk - tap * NT;
+      wsrc[k] = (b < WSLAB && ntg0 + nt < p.NTt) ? (tap * p.KC * p.NTt + nt) * WBLK + within : -1;
+    }
+    dma_w(0, wbuf);
+    if (ntg0 + NT > p.NTt) {                          // workgroup-uniform: the weight's last, partial channel block
+      for (int i = tid; i < 2 * WSLAB / 16; i += THREADS) {
+        const int b = i * 16 - (i * 16 >= WSLAB ? WSLAB : 0);
+        if (ntg0 + (b / WBLK) % NT >= p.NTt) *reinterpret_cast<u32x4*>(wbuf + i * 16) = u32x4{0u, 0u, 0u, 0u};
+      }
+    }
+  }
   // XBN: per-channel scale / shift of the input's BatchNorm in LDS (behind the weight slab), computed while the first
   // chunk's loads are in flight; workgroup (0, 0) publishes mean / invstd / running statistics
-  float* xsc = reinterpret_cast<float*>(wbuf + (S3 ? 3 : 1) * 9 * NT * WBLK + (PC ? p.patch_bytes + 3 * WPL : 0));      // (16-bit and split-product instances; PC: behind the second buffer)
+  float* xsc = reinterpret_cast<float*>(wbuf + (WD ? 2 * WSLAB : (S3 ? 3 : 1) * 9 * NT * WBLK) + (PC ? p.patch_bytes + 3 * WPL : 0));      // (16-bit and split-product instances; PC, WD: behind the second buffer)
   float* xsf = xsc + p.Ci;
   const bool xon = (SZ == 2 || S3) && p.xb.on;
   if (xon) {
@@ -297,17 +347,23 @@ __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t
       if (producer) break;      // (its loop is above; same number of barriers)
     } else {
       T4_STAMP(0);
-      if (c > 0) __syncthreads();   // the previous chunk has been multiplied by every wave
+      // WD: every wave waits for its own share of the DMA in front of a barrier (vmcnt(0), stated rather than left to the
+      // compiler's fence), so behind the barrier the weights of chunk c have landed as a whole
+      if constexpr (WD) __builtin_amdgcn_s_waitcnt(0x0f70);
+      if (c > 0) __syncthreads();   // the previous chunk has been multiplied by every wave (WD: and this chunk's weights have landed)
       T4_STAMP(1);
       store(c, patch, wbuf, Set0());
       T4_STAMP(2);
       __syncthreads();
       T4_STAMP(3);
-      if (c + 1 < nchunk) fetch(c + 1, Set0());   // in flight while this chunk is multiplied
+      if (c + 1 < nchunk) {
+        fetch(c + 1, Set0());   // in flight while this chunk is multiplied
+        if constexpr (WD) dma_w(c + 1, wbuf + ((c + 1) & 1) * WSLAB);   // ... and its weights, into the buffer chunk c - 1 was multiplied out of
+      }
     }
     char* const cbuf = PC ? smem + (c & 1) * (p.patch_bytes + BUFSZ_W) : smem;
     const char* const patch = cbuf;
-    const char* const wbuf = cbuf + p.patch_bytes;
+    const char* const wbuf = cbuf + p.patch_bytes + (WD ? (c & 1) * WSLAB : 0);
     // the nine taps of this chunk for a wave with MW live pixel tiles (compile-time: a per-tile "is it live" branch cut the
     // loop into 3-MFMA blocks, each behind its own LDS wait -- now a tap's fragments are requested while the previous
     // tap's MFMAs issue)
@@ -521,10 +577,16 @@ __global__ __launch_bounds__(WV * 64, S3 ? 2 : (NT == 3 ? 4 : 3)) void conv3x3_t
 static long long* g_t4_dbg = nullptr;   // fami_conv_t4_debug (FAMI_T4_TRACE builds)
 // [fami_route_t] g_t4_s3_narrow (default 0)  // fami_conv_tune_lds(102030 / 102031): two channel tiles per workgroup on launches of < 200 workgroups off / on.
                                     // Per launch 55 -> 43 us (24x18 @192 ch) and 70 -> 57 (12x9 @384 ch); f32 step 49.0 -> 49.7 and 48.9 -> 49.6 ms: off.
+                                    // Again with the weights by DMA (every extra workgroup no longer pays a weight split): per launch 49.3 -> 38.8 and
+                                    // 61.0 -> 49.4 us, f32 step 44.40 -> 45.02 ms (ab_env medians): still off.
+// [fami_route_t] g_t4_s3_wdma (default 1)  // fami_conv_tune_lds(102040 / 102041): weights of the split-product instance from the pre-split image by LDS DMA (the kernel's WD form) off / on.
+                                    // Inside the f32 step (tools/ab_env.py, eight alternating rounds on one box) 44.61-44.85 -> 44.29-44.49 ms; bench.py 44.07-44.25 -> 43.08-43.76 ms: on.
 // [fami_route_t] g_t4_s3_fill (default 2)  // fami_conv_tune_lds(102000 / 102001 / 102002): more, smaller bands on launches that leave CUs empty: off / all / tiny ones.
                                     // Per launch it wins (24x18 @192 ch 55 -> 45 us, 48x36 @96 ch 40.6 -> 35.6); inside the step other lanes
                                     // already fill those CUs and the smaller bands only add staging: 50.8 -> 51.4 and 49.5 -> 50.4 ms.  2 = only launches of
                                     // < 128 workgroups: the head's 4-frame convolutions (72 workgroups), which the trace shows running alone.
+                                    // Again with the weights by DMA: per launch 24x18 @192 ch 49.3 -> 38.5 us with 1, the head's 4-frame launch 12.0 -> 23.6
+                                    // with 0; f32 step (ab_env medians) 2: 44.40, 1: 44.87, 0: 44.68 ms: 2 stays.
 // [fami_route_t] g_t4_s3_pc (default 0)  // fami_conv_tune_lds(60 / 61): producer / consumer form of the split-product instance off / on
 // [fami_route_t] g_t4_s3_mt_minft (default 64)  // ... only for frames of at least this many tiles (24x18 maps: 27 tiles = one band of 24 + one of 3)
 // [fami_route_t] g_t4_s3_mt (default 3)  // fami_conv_tune_lds(52 / 53): pixel tiles per wave of the split-product instance.  3 (bands of <= 24 tiles, 15 LDS
@@ -536,9 +598,28 @@ static long long* g_t4_dbg = nullptr;   // fami_conv_t4_debug (FAMI_T4_TRACE bui
 // [fami_route_t] g_use_t4_s3 (default 1)  // fami_conv_tune_lds(30 / 31): f32 storage on the bf16 matrix pipe (split products, see the kernel) off / on
 
 // ---- the split-product f32 instance: plan + launch
+// Is there a weight-DMA (WD) instance for mt pixel tiles per wave and pm patch pieces per thread?  All of FAMI_T4S3_CASE's table but
+// three tiles per wave with more than 5 pieces (96x72 bands of more than 20 tiles): that one spills in the DMA form too, 12 bytes
+// against the register form's 64, and is not built; such launches keep the register form.  The one copy of the rule: the plan
+// asks it with the launch's PM, the dispatch with the instance's.
+static constexpr bool t4_s3_wd_built(int mt, int pm) { return !(mt == 3 && pm > 5); }
+// one instance of the table: its DMA form where the plan chose it (wd) and it is built, else its register form
+template <int NT, int PM, int MTT>
+static void t4_s3_launch(bool wd, dim3 grid, size_t lds, hipStream_t s, const ConvT4Args& a) {
+  const int lds_cap = 160 * 1024;
+  if constexpr (t4_s3_wd_built(MTT, PM)) {
+    if (wd) {
+      fami_lds_limit<conv3x3_t4_kernel<float, NT, PM, true, 8, MTT, false, true>>(lds_cap);
+      hipLaunchKernelGGL((conv3x3_t4_kernel<float, NT, PM, true, 8, MTT, false, true>), grid, dim3(512), lds, s, a);
+      return;
+    }
+  }
+  fami_lds_limit<conv3x3_t4_kernel<float, NT, PM, true, 8, MTT>>(lds_cap);
+  hipLaunchKernelGGL((conv3x3_t4_kernel<float, NT, PM, true, 8, MTT>), grid, dim3(512), lds, s, a);
+}
 static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
                              int KC, int NTt, int sgn, int relu, int accumulate, hipStream_t s, const char* name,
-                             const EpiBN& epi, const XBN& xbn, int dil = 1) {
+                             const EpiBN& epi, const XBN& xbn, int dil = 1, long* plan = nullptr) {
   if (!g_use_t4 || !g_use_t4_s3 || (Ci % 4) != 0 || (x && (reinterpret_cast<uintptr_t>(x) & 15) != 0)) return 0;
   int NT = Co % 48 == 0 ? 3 : (Co % 64 == 0 ? 4 : 0);
   // dilated form (round 4: the DCN offset / mask predictors, 48 -> 216 / 108 and their input gradients): the last 48-wide
@@ -573,7 +654,10 @@ static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, v
       if (positions(bt) * 4 <= 6 * 256 && 2 * ((size_t)positions(bt) * 3 * T4_S3_ROW + (wbytes - (xbn.on ? (size_t)2 * Ci * sizeof(float) : 0))) + (xbn.on ? (size_t)2 * Ci * sizeof(float) : 0) <= lds_cap) BTp = bt;
     if (BTp) {
       if (BTp > FT) BTp = FT;
-      if (!x) return 1;
+      if (!x) {
+        if (plan) plan[0] = 3;
+        return 1;
+      }
       ConvT4Args a;
       a.e = epi; a.emode = epi.slots ? epi.mode : 0; a.xb = xbn;
       a.x = x; a.wp = wp; a.y = y; a.bias = bias;
@@ -582,6 +666,7 @@ static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, v
       a.dil = 1;
       const long npos = positions(BTp);
       a.patch_bytes = (int)(npos * 3 * a.PS);
+      a.wsp = nullptr;
       a.dbg = g_t4_dbg;
       const size_t lds = 2 * ((size_t)a.patch_bytes + (size_t)3 * 9 * NT * 16 * T4_S3_ROW) + (xbn.on ? (size_t)2 * Ci * sizeof(float) : 0);
       const dim3 grid(N * a.bands, cblocks);
@@ -625,25 +710,40 @@ static int try_conv3x3_t4_s3(const void* x, const void* wp, const float* bias, v
   if (g_t4_bt > 0 && g_t4_bt <= BT) BT = g_t4_bt;
   if (BT > FT) BT = FT;
   if (BT <= 16) MTs = 2;
-  if (!x) return 1;      // eligibility query (fami_conv_t4_eligible_s3)
+  const long npos = positions(BT);
+  const int PM = (int)((npos * 4 + WVs * 64 - 1) / (WVs * 64));
+  size_t lds = (size_t)npos * 3 * T4_S3_ROW + wbytes;
+  // Weights by DMA from the pre-split image behind the fragment image (the kernel's WD form; conv_t5.hip locates the image the
+  // same way): wherever that image exists and a second weight buffer fits beside the band ALREADY chosen -- the plan above is
+  // not touched, a launch that cannot take the DMA form is the register form's, bit for bit.
+  const size_t wslab = (size_t)9 * NT * 3 * 16 * T4_S3_ROW;
+  const bool wd = g_t4_s3_wdma && (Ci % 16) == 0 && KC * 16 == Ci && fami_split_image_elems(Ci, Co, 9) > 0 && lds + wslab <= lds_cap &&
+                  t4_s3_wd_built(MTs, PM);
+  if (plan) {            // fami_conv_t4_s3_plan: form, LDS bytes of the register form, LDS bytes the DMA form needs, BT, MTs, PM
+    plan[0] = wd ? 2 : 1;
+    plan[1] = (long)lds;
+    plan[2] = (long)(lds + wslab);
+    plan[3] = BT;
+    plan[4] = MTs;
+    plan[5] = PM;
+  }
+  if (!x) return 1;      // eligibility query (fami_conv_t4_eligible_s3, fami_conv_t4_s3_plan)
   ConvT4Args a;
   a.e = epi; a.emode = epi.slots ? epi.mode : 0; a.xb = xbn;
   a.x = x; a.wp = wp; a.y = y; a.bias = bias;
   a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.BT = BT; a.bands = (FT + BT - 1) / BT;
   a.PW = W + 2 * dil; a.PS = T4_S3_ROW; a.KC = KC; a.NTt = NTt; a.sgn = sgn; a.relu = relu; a.accumulate = accumulate; a.out_f32 = 1;
   a.dil = dil;
-  const long npos = positions(BT);
   a.patch_bytes = (int)(npos * 3 * a.PS);     // three planes
   a.dbg = g_t4_dbg;
-  size_t lds = (size_t)a.patch_bytes + wbytes;
+  a.wsp = wd ? reinterpret_cast<const char*>(wp) + (size_t)9 * KC * NTt * 1024 : nullptr;
+  if (wd) lds += wslab;
   const dim3 grid(N * a.bands, cblocks);
   if ((long)N * a.bands * cblocks < g_t4_s3_minwg) return 0;
-  const int PM = (int)((npos * 4 + WVs * 64 - 1) / (WVs * 64));
   bool ok = false;
 #define FAMI_T4S3_CASE(nt, pm, mt)                                                                                        \
   if (NT == nt && MTs == mt && PM <= pm && !ok) {                                                                         \
-    fami_lds_limit<conv3x3_t4_kernel<float, nt, pm, true, 8, mt>>((int)lds_cap);                                          \
-    hipLaunchKernelGGL((conv3x3_t4_kernel<float, nt, pm, true, 8, mt>), grid, dim3(WVs * 64), lds, s, a);                 \
+    t4_s3_launch<nt, pm, mt>(wd, grid, lds, s, a);                                                                        \
     ok = true;                                                                                                            \
   }
   FAMI_T4S3_CASE(3, 3, 2) FAMI_T4S3_CASE(3, 5, 2) FAMI_T4S3_CASE(4, 3, 2) FAMI_T4S3_CASE(4, 5, 2) FAMI_T4S3_CASE(2, 3, 2) FAMI_T4S3_CASE(2, 5, 2)
@@ -703,6 +803,7 @@ static int try_conv3x3_t4(const void* x, const void* wp, const float* bias, void
   a.dil = dil;
   const long npos = positions(BT);
   a.patch_bytes = (int)(npos * a.PS);
+  a.wsp = nullptr;
   a.dbg = g_t4_dbg;
   const size_t wbytes = (size_t)9 * NT * 1024;
   size_t lds = (size_t)a.patch_bytes + wbytes + (xbn.on ? (size_t)2 * Ci * sizeof(float) : 0);
@@ -794,6 +895,22 @@ int fami_conv_t4_eligible_s3(int N, int H, int W, int Ci, int Co) {
   xb.on = 1;
   return try_conv3x3_t4_s3(nullptr, nullptr, nullptr, nullptr, N, H, W, Ci, Co, 0, 0, 1, 0, 0, nullptr, "", epi_none(), xb);
 }
+// which form of the split-product band kernel a 3x3 stride-1 f32 convolution [N,H,W,Ci] -> Co (pad = dil, sgn -1: input gradient, the
+// arguments as that launch takes them; xbn: with the input BatchNorm's tables) would launch: 0 none, 1 the register form, 2 the
+// weight-DMA form, 3 producer / consumer; out[0] / out[1]: LDS bytes of the register form / that the DMA form needs; out[2 .. 4]:
+// tiles per band, pixel tiles per wave (the instance's MTT), patch pieces per thread (tests)
+extern "C" int fami_conv_t4_s3_plan(int N, int H, int W, int Ci, int Co, int dil, int sgn, int xbn, long* out) {
+  XBN xb = xbn_none();
+  xb.on = xbn ? 1 : 0;
+  long plan[6] = {0, 0, 0, 0, 0, 0};
+  const int rc = try_conv3x3_t4_s3(nullptr, nullptr, nullptr, nullptr, N, H, W, Ci, Co, (Ci + 15) / 16, (Co + 15) / 16, sgn, 0, 0, nullptr, "",
+                                   epi_none(), xb, dil, plan);
+  if (out) {
+    for (int k = 0; k < 5; ++k) out[k] = plan[k + 1];
+  }
+  return rc == 1 ? (int)plan[0] : 0;
+}
+extern "C" int fami_conv_t4_eligible(int N, int H, int W, int Ci, int Co) { return fami_conv_t4_eligible_s3(N, H, W, Ci, Co); }
 extern "C" void fami_conv_t4_debug(void* buf) { g_t4_dbg = reinterpret_cast<long long*>(buf); }
 void fami_conv_t4_default_split(int on) { g_s3_default = on ? 1 : 0; }
 void fami_conv_t4_tune(int on) {
@@ -805,7 +922,8 @@ void fami_conv_t4_tune(int on) {
     fami_conv_t5_tune(on);
     if (on >= 0) return;
   }
-  if (on < 0) { g_use_t4 = 1; g_t4_dil = 1; g_t4_bt = 0; g_use_t4_f32 = 0; g_use_t4_s3 = g_s3_default; g_t4_s3_minwg = 0; g_t4_s3_mt = 3; g_t4_s3_pc = 0; g_t4_s3_fill = 2; g_t4_s3_narrow = 0; }
+  if (on < 0) { g_use_t4 = 1; g_t4_dil = 1; g_t4_bt = 0; g_use_t4_f32 = 0; g_use_t4_s3 = g_s3_default; g_t4_s3_minwg = 0; g_t4_s3_mt = 3; g_t4_s3_pc = 0; g_t4_s3_fill = 2; g_t4_s3_narrow = 0; g_t4_s3_wdma = 1; }
+  else if (on == 102040 || on == 102041) g_t4_s3_wdma = on - 102040;
   else if (on == 30 || on == 31) g_use_t4_s3 = on - 30;
   else if (on >= 40 && on <= 42) g_t4_dil = on - 40;
   else if (on == 102030 || on == 102031) g_t4_s3_narrow = on - 102030;

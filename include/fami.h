@@ -62,7 +62,8 @@ int fami_conv_tune_lds(int on);          /* 1 / 0 = route eligible 3x3 stride-1 
                                           * on; 20 / 21 its exact-f32-MFMA instance; 30 / 31 the split-product instance off / on (30 = exact
                                           * f32 MFMA kernels); 52 / 53 two / three pixel tiles per wave of it; 60 / 61 / 62 its producer-
                                           * consumer form off / one-band frames / always; 100 + bt tiles per band; 2000 + n only launches of
-                                          * >= n workgroups; 102000 / 102001 CU-filling band rule off / on */
+                                          * >= n workgroups; 102000 / 102001 CU-filling band rule off / on; 102040 / 102041 the
+                                          * split-product instance's weights from the pre-split image by LDS DMA off / on */
 int fami_conv_tune_wgrad_lds(int on);    /* 0 = weight gradients on the scalar-operand kernels, 1 = LDS-staged kernels wherever eligible,
                                           * 1 + n = the same with n sub-chunks per workgroup of the 16-bit kernel (default 2),
                                           * -1 = defaults (16-bit storage: LDS-staged; f32: linear-address per-tap kernel on stride-1
@@ -86,6 +87,16 @@ int fami_tune_reset(void);
 int fami_tune_defaults(int f32_split);
 /* would a 3x3 stride-1 pad-1 f32 convolution [N,H,W,Ci] -> Co take the persistent split-product kernel (conv_t5.hip)? (tests) */
 int fami_conv_t5_eligible(int N, int H, int W, int Ci, int Co);
+/* would a 3x3 stride-1 pad-1 f32 convolution [N,H,W,Ci] -> Co take the split-product band kernel (conv_t4.hip) with the input
+ * BatchNorm's tables in LDS (the f32 half of fami_conv2d_xbn_ok_f32)? (tests) */
+int fami_conv_t4_eligible(int N, int H, int W, int Ci, int Co);
+/* ... and which form of it would a launch be: 0 none, 1 the register form (every workgroup splits its f32 weight fragments),
+ * 2 the weight-DMA form (pre-split image -> LDS by DMA, two weight buffers; fami_conv_tune_lds(102040 / 102041) off / on),
+ * 3 producer / consumer.  dil: dilation = padding; sgn -1: the input gradient, with Ci / Co as that launch takes them (swapped);
+ * xbn: with the input BatchNorm's tables in LDS.  out (optional, 5 longs; forms 1 and 2): LDS bytes of the register form, LDS
+ * bytes the DMA form needs (it is taken only where they fit 160 KiB), 16-pixel tiles per band, pixel tiles per wave of the
+ * instance (2 | 3), patch pieces per thread. (tests) */
+int fami_conv_t4_s3_plan(int N, int H, int W, int Ci, int Co, int dil, int sgn, int xbn, long* out);
 /* ... and the LDS-DMA-staged kernels of conv_t6.hip (round 4: 16-bit storage; 48 input channels: whole weight image LDS-resident,
  * patch and weights copied by LDS DMA -- fami_conv_tune_lds(8000 / 8001) off / on, 8100 + rows per band, 8201 / 8202 units of two /
  * four rows, 8400 + minimum jobs; 96 / 192 / 384 input channels in phases of 48 -- 8500 / 8501 off / on, 8600 + rows per band,

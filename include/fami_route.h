@@ -51,6 +51,7 @@ typedef struct fami_route_t {
   int  use_t4_f32;            /* default 0.  fami_conv_tune_lds(20 / 21): the f32 instance off / on.  Off by default: per launch it wins where */
   int  t4_bt;                 /* default 0.  fami_conv_tune_lds(100 + bt): force the tiles per band (benchmarks) */
   int  t4_s3_narrow;          /* default 0.  fami_conv_tune_lds(102030 / 102031): two channel tiles per workgroup on launches of < 200 workgroups off / on. */
+  int  t4_s3_wdma;            /* default 1.  fami_conv_tune_lds(102040 / 102041): weights of the split-product band kernel from the pre-split image (fami_split_image_elems) by LDS DMA into two LDS buffers, instead of f32 fragments split by every workgroup, off / on; launches without that image or without room for the second buffer take the register form either way.  Per launch 192 ch @24x18 53.6 -> 49.3 us, 384 ch @12x9 69.3 -> 61.0; f32 step 44.07-44.25 -> 43.08-43.76 ms (profiles/band_wdma/) */
   int  t4_s3_fill;            /* default 2.  fami_conv_tune_lds(102000 / 102001 / 102002): more, smaller bands on launches that leave CUs empty: off / all / tiny ones. */
   int  t4_s3_pc;              /* default 0.  fami_conv_tune_lds(60 / 61): producer / consumer form of the split-product instance off / on */
   int  t4_s3_mt_minft;        /* default 64.  ... only for frames of at least this many tiles (24x18 maps: 27 tiles = one band of 24 + one of 3) */
