@@ -30,21 +30,21 @@
 //   * a wave none of whose detections remain skips the OKS of the round; it still meets the barrier.
 //   * the OKS of a round is J chains of two fp64 divisions and an exp, each several hundred cycles of dependent
 //     instructions; the joint loop runs four joints per trip without a branch (masked joints are computed and left out
-//     of the sum), so that four chains overlap.
+//     of the sum), so that four chains overlap (oks.h, shared with track.hip).
 // All LDS is dynamic and 16-byte aligned (nothing static in front of it); at J = 32 it exceeds 64 KiB, hence the function
 // attribute.  The visibility mask and the working score live in registers.
 #include "common.h"
+#include "oks.h"
 
 #define NMS_THREADS 256
 #define NMS_WAVES (NMS_THREADS / 64)
 #define NMS_CAP NMS_THREADS  // detections per image: one thread each
-#define NMS_JMAX 32          // joints: one bit each in the visibility mask
+#define NMS_JMAX OKS_JMAX    // joints: one bit each in the visibility mask
 #define NMS_NONE 0x7fffffff  // "no detection" in the argmax
-#define NMS_UNROLL 4         // joints per trip of the OKS loop
 
 // dynamic LDS: vars[32] f64 | argmax slots [2][4] f64 + [2][4] i32 | area[256] f32 | xy[J][256] float2
 #define NMS_LDS_FIXED (NMS_JMAX * 8 + 2 * NMS_WAVES * 8 + 2 * NMS_WAVES * 4 + NMS_CAP * 4)
-static_assert(NMS_WAVES == 4 && NMS_LDS_FIXED % 16 == 0, "the (x, y) array must start 16-byte aligned");
+static_assert(NMS_WAVES == 4 && NMS_CAP == OKS_CAP && NMS_LDS_FIXED % 16 == 0, "the (x, y) array must start 16-byte aligned");
 static inline size_t nms_lds_bytes(int J) { return NMS_LDS_FIXED + (size_t)J * NMS_CAP * 8; }
 
 // step 1 for one detection: k = its [J][3] keypoints, bs = its box score
@@ -106,10 +106,7 @@ __global__ __launch_bounds__(NMS_THREADS) void pose_nms_kernel(
     if ((unsigned)g >= (unsigned)N) g = -1;
   }
   const int bad = t < n && g < 0;
-  if (t < J) {
-    const double v = (double)sigmas[t] * 2.0;
-    vars[t] = v * v;
-  }
+  if (t < J) vars[t] = oks_var(sigmas[t]);
   double w = 0.0;      // the working score
   unsigned mask = 0u;  // joints of THIS detection that count when it is compared against a picked one
   if (g >= 0) {
@@ -171,22 +168,7 @@ __global__ __launch_bounds__(NMS_THREADS) void pose_nms_kernel(
     }
     ++count;
     if (remaining) {
-      const double a = ((double)s_area[p] + (double)s_area[t]) / 2.0 + 2.220446049250313e-16;  // np.spacing(1)
-      double sum = 0.0;
-      for (int j0 = 0; j0 < J; j0 += NMS_UNROLL) {  // NMS_UNROLL joints' chains of divisions and exp in flight at once
-        double ex[NMS_UNROLL];
-#pragma unroll
-        for (int u = 0; u < NMS_UNROLL; ++u) {
-          const int j = min(j0 + u, J - 1);
-          const float2 q = xy[j * NMS_CAP + p], d = xy[j * NMS_CAP + t];
-          const double dx = (double)d.x - (double)q.x, dy = (double)d.y - (double)q.y;
-          ex[u] = exp(-((dx * dx + dy * dy) / vars[j] / a / 2.0));
-        }
-#pragma unroll
-        for (int u = 0; u < NMS_UNROLL; ++u)  // summed in ascending j, masked joints (and the clamped tail) left out
-          if (j0 + u < J && ((mask >> (j0 + u)) & 1u)) sum += ex[u];
-      }
-      const double oks = nmask ? sum / (double)nmask : 0.0;
+      const double oks = oks_pair(xy + p, xy + t, vars, s_area[p], s_area[t], mask, nmask, J);
       if (soft)
         w = w * exp(-(oks * oks) / oks_thre);
       else if (oks > oks_thre)

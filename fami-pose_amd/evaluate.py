@@ -32,6 +32,15 @@
   box score).  There is no "run NMS" switch in the reference, so there is none here: the step runs when it is called,
   and `evaluate_loop`, `predict` and `write_posetrack_results` are unchanged.  Box-IoU NMS (nms.py:9-48, NMS_THRE) is a
   detector-stage step and stays out.
+* `pose_track` / `EvalAccumulator.pose_track` -- person identities, between `pose_nms` and the writer.  The reference declares
+  EVAL_TRACKING / TRACKING_THRESHOLD (posetimation/config/defaults.py:34-36), carries `eval_tracking` through
+  `convert_data_to_annorect_struct`, and writes track_id = position of the pose in its frame (PoseTrack_Alignment.py:998):
+  it has no association rule, so the rule is this project's (include/fami.h): per video, frames by ascending frame
+  number, every detection in list order takes the live track with the largest OKS (the arithmetic of `pose_nms`) if that
+  exceeds oks_thre, else starts a new one; a track unseen for more than max_gap frame numbers is retired.  One upload, ONE
+  launch with one workgroup per video (csrc/track.hip, `fami_pose_track_f32`), one download.  No cfg switch: the live
+  config tree has no tracking key.  `write_posetrack_results(..., tracks=)` carries the ids into the JSON; with
+  tracks=None it writes what it always wrote.
 * `write_posetrack_results` -- the PoseTrack JSON writer of
   datasets/zoo/posetrack/PoseTrack_Alignment.py:883-1017 (`evaluate` up to the poseval call): COCO->PoseTrack joint
   conversion (datasets/process/structure/keypoints_ord.py:14-73), the annorect structure
@@ -47,7 +56,8 @@
   `torch.sort` between them; one upload, one download.  The ignore-region point filter, for which the reference needs
   shapely, is an even-odd crossing test in the first kernel.  The files `write_posetrack_results` wrote are its input.
 
-Out of scope: poseval's tracking metrics (`evaluateTracking`, MOTA: needs motmetrics), the PoseTrack18 `images` /
+Out of scope: poseval's tracking metrics (`evaluateTracking`, MOTA: needs motmetrics; nothing scores the ids of
+`pose_track` yet), motion models and appearance re-identification, the PoseTrack18 `images` /
 `annotations` file layout (poseval's convert.py), per-sequence AP files and PCKh (evaluatePCKh.py).
 
 The reference imports its joint-name lists from modules that are missing from the released tree
@@ -250,6 +260,14 @@ class EvalAccumulator:
         boxes2[:, 5] = scores
         return boxes2, keep_map
 
+    def pose_track(self, filenames_map=None, **kw):
+        """Track ids for everything accumulated so far (module-level `pose_track`, same keywords) -> (tracks [idx] int32,
+        num_tracks {video: int}).  `filenames_map`: the frames to track, typically the keep_map of `pose_nms` (duplicates
+        removed, each frame in pick order); default the accumulator's own map.  `tracks` is the `tracks=` argument of
+        `write_posetrack_results`.  The accumulator itself is not modified."""
+        fmap = self.filenames_map if filenames_map is None else filenames_map
+        return pose_track(self.all_preds[:self.idx], self.all_boxes[:self.idx], fmap, **kw)
+
 
 @torch.no_grad()
 def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS,
@@ -311,7 +329,7 @@ def pose_nms_options(cfg, phase):
             'soft': bool(sub.get('SOFT_NMS', False))}
 
 
-def _nms_lists(filenames_map, N):
+def _nms_lists(filenames_map, N, who='pose_nms'):
     """-> (index [n] int32, seg [M+1] int32) of the lists of `filenames_map` in its order; ValueError for a list longer
     than the kernel's cap, an index outside [0, N), a non-integer index, or an index used twice.  The lists are checked
     as one array (a validation set has tens of thousands of them); the offending image is looked up only to be named."""
@@ -324,19 +342,19 @@ def _nms_lists(filenames_map, N):
 
     if len(lists) and np.diff(seg).max() > NMS_MAX_PER_IMAGE:
         m = int(np.diff(seg).argmax())
-        raise ValueError('pose_nms: image %r has %d detections, the limit is %d per image'
+        raise ValueError(who + ': image %r has %d detections, the limit is %d per image'
                          % (list(filenames_map)[m], len(lists[m]), NMS_MAX_PER_IMAGE))
     flat = np.asarray([i for v in lists for i in v])
     if flat.size == 0:
         return np.zeros(0, dtype=np.int32), seg.astype(np.int32)
     if flat.ndim != 1 or flat.dtype.kind not in 'iu':
-        raise ValueError('pose_nms: the lists of filenames_map must hold integer row indices (got %s)' % flat.dtype)
+        raise ValueError(who + ': the lists of filenames_map must hold integer row indices (got %s)' % flat.dtype)
     bad = np.flatnonzero((flat < 0) | (flat >= N))
     if bad.size:
-        raise ValueError('pose_nms: image %r lists row %d outside [0, %d)' % (image_of(bad[0]), flat[bad[0]], N))
+        raise ValueError(who + ': image %r lists row %d outside [0, %d)' % (image_of(bad[0]), flat[bad[0]], N))
     count = np.bincount(flat, minlength=N)
     if count.max() > 1:
-        raise ValueError('pose_nms: row %d is listed %d times' % (int(count.argmax()), int(count.max())))
+        raise ValueError(who + ': row %d is listed %d times' % (int(count.argmax()), int(count.max())))
     return flat.astype(np.int32), seg.astype(np.int32)
 
 
@@ -433,6 +451,136 @@ def pose_nms(preds, boxes, filenames_map, in_vis_thre=0.0, oks_thre=0.5, soft=Fa
     return scores, keep_map
 
 
+# ---------------------------------------------------------------------------------------- OKS pose tracking
+def posetrack_frame_of(key):
+    """The writer's own rule (`write_posetrack_results`): '.../<a>/<b>/<number>.<ext>' -> ('<a>/<b>', number)."""
+    parts = str(key).split('/')
+    try:
+        if len(parts) < 3:
+            raise ValueError
+        return parts[-3] + '/' + parts[-2], int(osp.splitext(parts[-1])[0])
+    except ValueError:
+        raise ValueError("pose_track: cannot read a video and a frame number from %r (expected '.../<video>/<number>.jpg'): "
+                         'pass frame_of' % (key,)) from None
+
+
+def _track_tables(filenames_map, N, frame_of=None):
+    """-> (index [n], fseg [M+1], fnum [M], vseg [V+1] int32, videos): the rows of `filenames_map` grouped by frame (each
+    list in its own order), the frames grouped by video (videos in the order of their first key) in ascending frame
+    number.  ValueError for what `_nms_lists` refuses, a key `frame_of` cannot place, a frame number that is no int32, and
+    two keys with the same (video, frame number)."""
+    index, seg = _nms_lists(filenames_map, N, 'pose_track')
+    frame_of = posetrack_frame_of if frame_of is None else frame_of
+    videos, vid, num, seen = {}, [], [], {}
+    for key in filenames_map:
+        where = frame_of(key)
+        if not isinstance(where, tuple) or len(where) != 2:
+            raise ValueError('pose_track: frame_of(%r) must return (video, frame_number), got %r' % (key, where))
+        video, f = where
+        if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, np.integer)) or not -2 ** 31 <= f < 2 ** 31:
+            raise ValueError('pose_track: the frame number of %r must be an integer that fits int32, got %r' % (key, f))
+        if (video, int(f)) in seen:
+            raise ValueError('pose_track: %r and %r are both frame %d of video %r' % (seen[(video, int(f))], key, f, video))
+        seen[(video, int(f))] = key
+        vid.append(videos.setdefault(video, len(videos)))
+        num.append(int(f))
+    M = len(vid)
+    vid, num = np.asarray(vid, dtype=np.int64), np.asarray(num, dtype=np.int64)
+    order = np.lexsort((num, vid))
+    lens = np.diff(seg.astype(np.int64))[order]
+    fseg = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(lens, out=fseg[1:])
+    take = np.repeat(seg[:-1].astype(np.int64)[order] - fseg[:-1], lens) + np.arange(int(fseg[-1]))
+    vseg = np.zeros(len(videos) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(vid, minlength=len(videos)), out=vseg[1:])
+    return (index[take].astype(np.int32), fseg.astype(np.int32), num[order].astype(np.int32), vseg.astype(np.int32),
+            list(videos))
+
+
+def pose_track(preds, boxes, filenames_map, oks_thre=0.3, max_gap=3, vis_thre=None, sigmas=None, frame_of=None,
+               device='cuda'):
+    """Person identities for a whole evaluation set in one launch (csrc/track.hip; include/fami.h has the rule, which is
+    this project's: the reference declares EVAL_TRACKING and writes the position in the frame as track_id).
+    preds [N,J,3], boxes [N,6] (column 4 the box area) and filenames_map {image -> [row indices]} as for `pose_nms`,
+    typically its keep_map: duplicates removed, each frame in pick order.  frame_of(key) -> (video, frame_number);
+    default the writer's rule, video = parts[-3] + '/' + parts[-2] and number = int(stem of parts[-1]) of key.split('/').
+    -> (tracks [N] int32, num_tracks {video: ids handed out}); tracks is -1 for a row that no image lists.
+    Per video, frames in ascending frame NUMBER (their order in filenames_map does not matter; frames without a
+    detection are simply absent).  A live track holds an id and the pose, box area and frame number of the last
+    detection matched to it.  Before frame f every track with f - last_frame > max_gap is retired (max_gap = 1:
+    consecutive frame numbers only).  The detections of f are walked in the order of filenames_map[image]: a detection
+    takes the live track with the largest OKS -- tracks already matched in this frame and tracks created in it do not
+    compete; equal OKS: the lowest id -- if that OKS is > oks_thre, receives its id, and the track takes its pose, area and
+    frame number; otherwise it is new.  After the walk the new detections get the next ids in list order and become
+    live.  Ids start at 0 in every video and are never reused.
+    OKS(track q, detection d) = mean_j exp(-(dx^2 + dy^2) / (2 sigma_j)^2 / ((a_q + a_d) / 2 + 2^-52) / 2), the arithmetic
+    of `pose_nms` (fp64 on the inputs rounded to fp32), over all joints, or with vis_thre over the joints whose
+    confidence in d exceeds it (an empty mask gives OKS 0).  sigmas: default COCO_SIGMAS for J = 17.
+    oks_thre = 0.3 and max_gap = 3 are STARTING VALUES, NOT TUNED: no PoseTrack data was available where this was built.
+    One upload, one launch (one workgroup per video), one download.  ValueError before any device work for: shape
+    errors, J outside 1 .. 32, J != 17 without sigmas, non-finite or non-positive sigmas, non-finite inputs or thresholds,
+    max_gap no integer >= 1, a key frame_of cannot place, two keys with the same (video, frame number), a frame with more
+    than 256 rows, a row outside [0, N) or listed twice.  ValueError naming the video after the download if it had more
+    than 256 live tracks at once (the other videos of the call are computed as if alone, but nothing is returned)."""
+    preds, boxes = np.asarray(preds), np.asarray(boxes)
+    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
+        raise ValueError('pose_track expects preds [N,J,3] and boxes [N,6], got %s and %s' % (preds.shape, boxes.shape))
+    N, J = preds.shape[:2]
+    if not 1 <= J <= NMS_MAX_JOINTS:
+        raise ValueError('pose_track: J = %d joints, supported 1 .. %d' % (J, NMS_MAX_JOINTS))
+    if sigmas is None:
+        if J != len(COCO_SIGMAS):
+            raise ValueError('pose_track: COCO_SIGMAS has %d joints, preds has %d: pass sigmas' % (len(COCO_SIGMAS), J))
+        sigmas = COCO_SIGMAS
+    sig32 = np.asarray(sigmas, dtype=np.float64).reshape(-1).astype(np.float32)
+    if sig32.shape != (J,) or not np.isfinite(sig32).all() or not (sig32 > 0).all():
+        raise ValueError('pose_track: sigmas must be %d finite positive values' % J)
+    if isinstance(max_gap, (bool, np.bool_)) or not isinstance(max_gap, (int, np.integer)) or not 1 <= max_gap < 2 ** 31:
+        raise ValueError('pose_track: max_gap must be an integer >= 1, got %r' % (max_gap,))
+    oks_thre = float(oks_thre)
+    vis = None if vis_thre is None else float(vis_thre)
+    if not (np.isfinite(oks_thre) and (vis is None or np.isfinite(vis))):
+        raise ValueError('pose_track: thresholds must be finite')
+    with np.errstate(over='ignore'):
+        k32 = np.ascontiguousarray(preds, dtype=np.float32)
+        a32 = np.ascontiguousarray(boxes[:, 4], dtype=np.float32)
+    if not (np.isfinite(k32).all() and np.isfinite(a32).all()):
+        raise ValueError('pose_track: preds and box areas must be finite (in fp32)')
+    index, fseg, fnum, vseg, videos = _track_tables(filenames_map, N, frame_of)
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('pose_track runs on the HIP path only (device is %s)' % dev)
+    M, V, n = len(fnum), len(videos), int(index.size)
+    if N == 0 or M == 0:
+        return np.full(N, -1, dtype=np.int32), {}
+    if N * J * 3 > 0x7fffffff:
+        raise ValueError('pose_track: N * J * 3 = %d exceeds 2^31 - 1' % (N * J * 3))
+    # ONE buffer of 4-byte words: the seven inputs, then the two outputs (track pre-filled with -1 for the rows that no
+    # image lists) -- one upload; the tail comes back in one download
+    sizes = [N * J * 3, N, J, n, M + 1, M, V + 1, N, V]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    buf = np.zeros(int(off[-1]), dtype=np.int32)
+    fbuf = buf.view(np.float32)
+    fbuf[off[0]:off[1]] = k32.reshape(-1)
+    fbuf[off[1]:off[2]] = a32
+    fbuf[off[2]:off[3]] = sig32
+    for k, a in zip(range(3, 7), (index, fseg, fnum, vseg)):
+        buf[off[k]:off[k + 1]] = a
+    buf[off[7]:off[8]] = -1
+    d = torch.from_numpy(buf).to(dev)
+    base = d.data_ptr()
+    p = [base + 4 * int(o) for o in off[:-1]]
+    with torch.cuda.device(dev):
+        lib().call('fami_pose_track_f32', p[0], p[1], p[2], p[3], p[4], p[5], p[6], N, J, n, M, V, oks_thre, int(max_gap),
+                   0.0 if vis is None else vis, 0 if vis is None else 1, p[7], p[8], torch.cuda.current_stream(dev).cuda_stream)
+    out = d[int(off[7]):].cpu().numpy()
+    tracks, count = out[:N].copy(), out[N:]
+    if (count < 0).any():
+        raise ValueError('pose_track: video %r has more than %d live tracks at once (the limit of one workgroup)'
+                         % (videos[int(np.argmax(count < 0))], NMS_MAX_PER_IMAGE))
+    return tracks, {video: int(c) for video, c in zip(videos, count)}
+
+
 # ---------------------------------------------------------------------------------------- PoseTrack JSON writer
 def coco2posetrack_ord(preds, global_score=1):
     """keypoints_ord.py:14-73.  preds: 4x17 (x, y, score, score) in COCO order -> list of 15 PoseTrack points."""
@@ -505,14 +653,27 @@ def video2filenames(annot_dir):
     return output, L
 
 
-def write_posetrack_results(preds, boxes, filenames_map, annot_dir, output_dir, is_posetrack18=False, phase='validate'):
+def write_posetrack_results(preds, boxes, filenames_map, annot_dir, output_dir, is_posetrack18=False, phase='validate',
+                            tracks=None):
     """PoseTrack_Alignment.evaluate up to the poseval call (:883-1017).  preds [N,17,3] (x, y, confidence in image
     coordinates), boxes [N,6] (center, scale, area, score), filenames_map {image path -> [row indices]}.
-    Writes one JSON file per video under output_dir/{val,test}_set_json_results and returns {file path: video}."""
+    Writes one JSON file per video under output_dir/{val,test}_set_json_results and returns {file path: video}.
+    tracks: None -- every pose gets its position in its frame as track_id, the reference's placeholder (:998) -- or an [N]
+    integer array, typically `pose_track`'s: the pose of row i gets tracks[i]; a listed row with a negative id is a
+    ValueError, raised before anything is written."""
+    if tracks is not None:
+        tracks = np.asarray(tracks)
+        if tracks.ndim != 1 or tracks.dtype.kind not in 'iu' or len(tracks) != len(preds):
+            raise ValueError('write_posetrack_results: tracks must be an integer array of %d entries, got %s %s'
+                             % (len(preds), tracks.dtype, tracks.shape))
+        for key, rows in filenames_map.items():
+            for idx in rows:
+                if tracks[idx] < 0:
+                    raise ValueError('write_posetrack_results: row %d of image %r has track id %d' % (idx, key, tracks[idx]))
     output_dir = osp.join(output_dir, 'val_set_json_results' if phase == 'validate' else 'test_set_json_results')
     os.makedirs(output_dir, exist_ok=True)
     video_map, vid2frame_map, vid2name_map = {}, {}, {}
-    all_preds, all_boxes = [], []
+    all_preds, all_boxes, all_rows = [], [], []
     cc = 0
     for key in filenames_map:
         parts = key.split('/')
@@ -532,30 +693,32 @@ def write_posetrack_results(preds, boxes, filenames_map, annot_dir, output_dir, 
             box_list.append(b)
         all_preds.append(pose_list)
         all_boxes.append(box_list)
+        all_rows.append(list(filenames_map[key]))
         cc += 1
 
     out_filenames, L = video2filenames(annot_dir)
     out_data = {}
     for vid in video_map:
         cur_length = L['images/' + vid]
-        kps_map, box_map, used = {}, {}, []
+        kps_map, box_map, row_map, used = {}, {}, {}, []
         for c, idx in enumerate(video_map[vid]):
             frame_num = vid2frame_map[vid][c]
             used.append(frame_num)
             kps_map[frame_num] = (vid2name_map[vid][c], all_preds[idx])
             box_map[frame_num] = all_boxes[idx]
+            row_map[frame_num] = all_rows[idx]
         sid, fid = (1, cur_length + 1) if not is_posetrack18 else (0, cur_length)
         for frame_num in range(sid, fid):
             if frame_num not in used:            # frames without a detection still get an (empty) entry
                 arr = vid2name_map[vid][0].split('/')
                 img_sfx = arr[0] + '/' + arr[1] + '/' + str(frame_num).zfill(6 if is_posetrack18 else 8) + '.jpg'
-                kps, tracks, bboxs = [], [], []
+                kps, ids, bboxs = [], [], []
             else:
                 img_sfx, kps = kps_map[frame_num]
                 bboxs = box_map[frame_num]
-                tracks = list(range(len(kps)))
+                ids = list(range(len(kps))) if tracks is None else [int(tracks[i]) for i in row_map[frame_num]]
             out_data.setdefault(vid, []).append({'image': {'name': img_sfx}, 'imgnum': [frame_num],
-                                                 'annorect': convert_data_to_annorect_struct(kps, tracks, bboxs)})
+                                                 'annorect': convert_data_to_annorect_struct(kps, ids, bboxs)})
     written = {}
     for vname, vdata in out_data.items():
         path = osp.join(output_dir, out_filenames[osp.join('images', vname)])

@@ -550,6 +550,38 @@ int fami_pose_nms_f32(const float* kpts, const float* area, const float* box_sco
                       int soft, int max_dets, double vis_thre, int use_vis, float* score, int* rank, int* kept,
                       fami_stream_t stream);
 
+/* Pose tracking by OKS: a person identity for every listed detection (csrc/track.hip).  The reference declares
+ * EVAL_TRACKING / TRACKING_THRESHOLD (posetimation/config/defaults.py:34-36) and writes track_id = position in the frame;
+ * it has no association rule, so THE RULE IS THIS PROJECT'S.  All pointers are DEVICE memory, 4-byte aligned.  kpts
+ * [N,J,3], area [N], sigmas [J] as for fami_pose_nms_f32; index [n]: rows of kpts grouped by frame, the frames grouped by
+ * video; fseg [M+1]: the detections of frame m are index[fseg[m] .. fseg[m+1]) (at most 256; an empty frame is legal);
+ * fnum [M]: its frame number; vseg [V+1]: the frames of video v are vseg[v] .. vseg[v+1) (an empty video is legal), their
+ * frame numbers strictly ascending.  Per video, starting with no track and next_id = 0; a live track holds an id and the
+ * (x, y) of its J joints, the box area and the frame number of the last detection matched to it:
+ *   1. before frame f every live track with f - last_frame > max_gap is retired (max_gap = 1: consecutive frame numbers
+ *      only; the gap is one of frame NUMBERS, not of positions in the table).
+ *   2. the detections of f are walked in the order of index.  Detection d takes the live track q with the largest
+ *        OKS(q, d) = mean over the masked joints of exp(-(dx^2 + dy^2) / (2 sigma_j)^2 / ((area_q + area_d) / 2 + 2^-52) / 2)
+ *      (fp64 on the fp32 inputs, one rounding per operation, the sum in ascending j, 0 on an empty mask; the mask is
+ *      conf_j(d) > vis_thre with use_vis != 0 and all joints with use_vis == 0) among the tracks not yet matched in this
+ *      frame -- tracks created in this frame do not compete; equal OKS: the lowest id -- if that OKS is > oks_thre: then
+ *      track[d] = the id of q, and q takes d's pose, area and frame number.  Otherwise d is new.
+ *   3. the new detections of f get the ids next_id, next_id + 1, ... in the order of index and become live tracks.
+ *   ntracks[v] = next_id at the end: ids start at 0 in every video and are never reused.
+ * The result does not depend on the slot a track occupies inside the kernel.  track [N] is written for listed rows only
+ * (the caller pre-fills what unlisted rows shall hold).  One launch, one workgroup per video, no atomics, no workspace,
+ * no host read-back: bitwise reproducible.
+ * Returns -1 before any launch for a null or misaligned pointer, J outside 1 .. 32, N outside 1 .. (2^31 - 1) / (3 J),
+ * n < 0, M or V outside 1 .. 2^31 - 2, a NaN threshold, max_gap < 1.  The tables are in device memory and are not checked
+ * here (fami_pose_amd.evaluate.pose_track does): a video whose segment is no sub-range of [0, M], or with a frame whose
+ * segment is no sub-range of [0, n] or longer than 256, frame numbers that do not ascend, a row outside [0, N), or more
+ * than 256 live tracks at once gets ntracks[v] = -1; it is left at the offending frame, so its rows hold either what they
+ * held or an id.  Nothing outside the two outputs is ever written and other videos are not affected.  A row listed twice
+ * has two writers (undefined which wins). */
+int fami_pose_track_f32(const float* kpts, const float* area, const float* sigmas, const int* index, const int* fseg,
+                        const int* fnum, const int* vseg, int N, int J, int n, int M, int V, double oks_thre,
+                        int max_gap, double vis_thre, int use_vis, int* track, int* ntracks, fami_stream_t stream);
+
 /* PoseTrack AP, the pose half of the evaluation tool the reference vendors (poseval/py/eval_helpers.py:322-367
  * removeIgnoredPoints, :453-668 assignGTmulti, :192-228 computeRPC / VOCap; evaluateAP.py:8-47 computeMetrics;
  * csrc/posetrack_ap.hip).  All pointers are DEVICE memory; fp64 arrays 8-byte, int arrays 4-byte aligned.  15 joints.
