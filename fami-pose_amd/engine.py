@@ -1,10 +1,14 @@
 """Host-side execution engine of the hot path: a tape of HIP kernel launches.
 
 Every op below enqueues kernels of libfami_hip.so (through the C ABI) on the
-current HIP stream and records the matching backward launch sequence; walking
-the tape in reverse is the backward pass.  There is no tracing compiler and no
-torch compute op on this path: torch provides device memory (tensors), the
-stream and (optionally) hipGraph capture of the whole launch sequence.
+stream of the current lane and records the matching backward launch sequence;
+walking the tape in reverse is the backward pass.  There is no tracing compiler
+and no torch compute op on this path: torch provides device memory (tensors),
+the streams and events that order the lanes (Engine._after is the one place
+that records an event and makes streams wait for it) and, optionally, hipGraph
+capture of the whole launch sequence.  Every launch goes through Engine.call or
+flush_reduces; tests/test_engine_launches_gpu.py pins the launches, event
+records and stream waits of a step.
 
 Activations are NHWC (`T.data` of shape [N,H,W,C]) in the engine's activation dtype -- fp32 (parity
 configuration), bf16 (BASELINE config 3: bf16 storage + bf16 MFMA convolutions, fp32 accumulation) or fp16
@@ -21,9 +25,6 @@ import torch
 from . import options
 from ._lib import lib
 
-BN_EPS = 1e-5
-
-
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -38,6 +39,24 @@ _SFX = {torch.float32: '_f32', torch.bfloat16: '_bf16', torch.float16: '_f16'}
 
 def _sfx(t):
     return _SFX[t.dtype]
+
+
+def _geometry(x, weight, stride, pad, dil):
+    """-> ((N, H, W, Ci, Co, kh, kw, stride, pad, dil), Ho, Wo) of a convolution of NHWC tensor x with an OIHW weight"""
+    N, H, W, Ci = x.shape
+    Co, Ci2, kh, kw = weight.shape
+    assert Ci2 == Ci, (x.shape, weight.shape)
+    return ((N, H, W, Ci, Co, kh, kw, stride, pad, dil),
+            (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1)
+
+
+def _conv_geometry(x, conv):
+    """_geometry of nn.Conv2d `conv` applied to x"""
+    return _geometry(x, conv.weight, conv.stride[0], conv.padding[0], conv.dilation[0])
+
+
+def _momentum(bn):
+    return 0.1 if bn.momentum is None else bn.momentum
 
 
 class T:
@@ -270,6 +289,21 @@ class Engine:
     # ------------------------------------------------------------------ stream lanes
     _side_pool = {}
 
+    @staticmethod
+    def _after(src, *waiting):
+        """Every stream of `waiting` continues after what `src` holds so far: ONE event, recorded on src -> that event."""
+        ev = torch.cuda.Event()
+        ev.record(src)
+        for st in waiting:
+            st.wait_event(ev)
+        return ev
+
+    def _taken(self, wstreams=True):
+        """The handles a newly picked stream must differ from: this step's main stream, every cached side lane and (wstreams)
+        this step's weight-gradient streams."""
+        return ({self._main.cuda_stream} | {t.cuda_stream for t in Engine._side_pool.get(self.dev, [])}
+                | ({t.cuda_stream for t in self._wstreams} if wstreams else set()))
+
     def _lanes(self, n):
         """-> n - 1 side streams, every one distinct from this step's main stream and from each other.  torch hands out
         streams round-robin from a fixed pool of 32 per device, so after enough torch.cuda.Stream() calls in a process a
@@ -280,10 +314,10 @@ class Engine:
         main = self._main.cuda_stream
         side = [s for s in pool if s.cuda_stream != main]
         tries = 0
-        while len(side) < n - 1 and tries < 64:
+        while len(side) < n - 1 and tries < 64:      # (a re-pick loop of its own: the pool grows inside it)
             tries += 1
             s = torch.cuda.Stream(self.dev)
-            if s.cuda_stream != main and all(s.cuda_stream != t.cuda_stream for t in pool):
+            if s.cuda_stream not in self._taken(wstreams=False):
                 pool.append(s)
                 side.append(s)
         if len(side) < n - 1:
@@ -303,10 +337,9 @@ class Engine:
     def _lane_stream(self):
         return self._main if self.lane == 0 else self._side[self.lane - 1]
 
-    def _new_wstream(self, extra=()):
+    def _new_wstream(self, taken):
         # same aliasing hazard as _lanes(): torch hands streams out of a 32-entry round-robin pool, so a cached stream can BE this
-        # step's main / capture stream or one of its side lanes -- re-pick until distinct
-        taken = {self._main.cuda_stream} | {t.cuda_stream for t in Engine._side_pool.get(self.dev, [])} | set(extra)
+        # step's main / capture stream or one of its side lanes -- re-pick until distinct (a loop of its own: it fails differently)
         ws, tries = None, 0
         while (ws is None or ws.cuda_stream in taken) and tries < 64:
             ws = torch.cuda.Stream(self.dev)
@@ -324,10 +357,10 @@ class Engine:
         n = max(1, self.stem_wlanes if pair else self.head_wlanes)
         while len(self._wstreams) < n:
             k = len(self._wstreams)
-            taken = {self._main.cuda_stream} | {t.cuda_stream for t in Engine._side_pool.get(self.dev, [])} | {t.cuda_stream for t in self._wstreams}
+            taken = self._taken()
             ws = Engine._wgrad_pool.get((self.dev, k))
             if ws is None or ws.cuda_stream in taken:
-                ws = self._new_wstream(tuple(t.cuda_stream for t in self._wstreams))
+                ws = self._new_wstream(taken)
             Engine._wgrad_pool[(self.dev, k)] = ws
             self._wstreams.append(ws)
         # key: what the launches accumulate into (a parameter).  A module applied twice inside such a scope keeps its weight gradients
@@ -340,9 +373,7 @@ class Engine:
             target = self._wstreams[self._wflip]
             if key is not None:
                 self._wowner[key] = self._wflip
-        ev = torch.cuda.Event()
-        ev.record(self._lane_stream())
-        target.wait_event(ev)
+        self._after(self._lane_stream(), target)
         saved = self.stream
         self.stream = target.cuda_stream
         self._wdirty = True
@@ -353,22 +384,16 @@ class Engine:
         if self._wdirty:
             for ws in self._wstreams:
                 self.flush_reduces(ws.cuda_stream)
-                ev = torch.cuda.Event()
-                ev.record(ws)
-                self._main.wait_event(ev)
+                self._after(ws, self._main)
             self._wdirty = False
 
     def side_launch(self, fn):
         """fn(raw_stream) on the first side lane, ordered after everything enqueued on lane 0 so far -> event to hand to
         wait_main().  For work nothing on the forward path reads (the dgrad weight images): it runs beside lane 0."""
         side = self._lanes(2)[0]
-        ev = torch.cuda.Event()
-        ev.record(self._main)
-        side.wait_event(ev)
+        self._after(self._main, side)
         fn(side.cuda_stream)
-        done = torch.cuda.Event()
-        done.record(side)
-        return done
+        return self._after(side)
 
     late_weights_ready = None
 
@@ -390,20 +415,15 @@ class Engine:
     def _do_fork(self, n):
         side = self._lanes(n)
         self.flush_reduces()
-        ev = torch.cuda.Event()
-        ev.record(self._main)
-        for i in range(n - 1):
-            side[i].wait_event(ev)
+        self._after(self._main, *side[:n - 1])       # ONE event for the n - 1 lanes
         self._forked = n
         self._epoch += 1
 
     def _do_join(self, n):
         side = self._lanes(n)
         self.flush_reduces()               # every lane's pending reduces go out on their own streams before the join events
-        for i in range(n - 1):
-            ev = torch.cuda.Event()
-            ev.record(side[i])
-            self._main.wait_event(ev)
+        for st in side[:n - 1]:                      # one event per lane
+            self._after(st, self._main)
         self.set_lane(0)
         self._forked = 0
         # parameters used on several lanes of the region: fold the lane-private gradients into the owner's buffer
@@ -426,13 +446,8 @@ class Engine:
         fork does not (pattern 4)."""
         side = [self._side[j - 1] for j in range(1, n)]
         for st in side:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self._main.wait_event(ev)
-        ev = torch.cuda.Event()
-        ev.record(self._main)
-        for st in side:
-            st.wait_event(ev)
+            self._after(st, self._main)
+        self._after(self._main, *side)
 
     def lanes_sync(self, n):
         """Inside a forked region of n lanes: an all-to-all dependency instead of a join + fork through lane 0 (a module's fuse
@@ -507,33 +522,20 @@ class Engine:
         if not self.defer_reduce:
             self.acall('fami_conv2d_wgrad', _p(x_data), _p(dy), _p(g), _p(ws), ws.numel() * 4, *geo, acc)
             return
-        st = self.stream
-        dws = self._red_dw.setdefault(st, set())
-        if g.data_ptr() in dws:            # a second reduce into the same gradient must follow the first
-            self.flush_reduces(st)
-            dws = self._red_dw.setdefault(st, set())
-        desc = (ctypes.c_long * self._red_longs)()
+        desc = self._reduce_open(g)
         if xbn is not None:
             self.acall('fami_conv2d_wgrad_defer_xbn', _p(x_data), _p(dy), _p(g), _p(ws), ws.numel() * 4, *geo[:5], acc, desc,
                        *[_p(t) for t in xbn])
         else:
             self.acall('fami_conv2d_wgrad_defer', _p(x_data), _p(dy), _p(g), _p(ws), ws.numel() * 4, *geo, acc, desc)
-        self._red.setdefault(st, []).append(desc)
-        dws.add(g.data_ptr())
-        if len(self._red[st]) >= 16:
-            self.flush_reduces(st)
+        self._reduce_close(g, desc)
 
     def wgrad_pair(self, x_data, dy, wpd, gx, accx, g, accw, geo, stats, xbn=None):
         """Input gradient (stats: the arguments of the backward-statistics epilogue, or None) and weight gradient of a 3x3 stride-1
         convolution in one launch; the weight gradient's slab reduce is deferred as in wgrad().  xbn (f32 storage): x_data is the
         input of a not materialised BatchNorm + ReLU (mean, invstd, gamma, beta)."""
         ws = self.ws(self.Q.fami_conv2d_wgrad_workspace(*geo))
-        st = self.stream
-        dws = self._red_dw.setdefault(st, set())
-        if g.data_ptr() in dws:
-            self.flush_reduces(st)
-            dws = self._red_dw.setdefault(st, set())
-        desc = (ctypes.c_long * self._red_longs)()
+        desc = self._reduce_open(g)
         if not self.half:
             assert stats is None
             self.call('fami_conv2d_bwd_pair_f32', _p(x_data), _p(dy), _p(wpd), _p(gx), _p(g), _p(ws), ws.numel() * 4, *geo, accx, accw, desc,
@@ -544,8 +546,20 @@ class Engine:
                 stats = (None, None, None, None, None, None, 0, None)
             self.acall('fami_conv2d_bwd_pair', _p(x_data), _p(dy), _p(wpd), _p(gx), _p(g), _p(ws), ws.numel() * 4, *geo, accx, accw, desc, *stats)
         self.npair += 1
+        self._reduce_close(g, desc)
+
+    def _reduce_open(self, g):
+        """-> a fresh descriptor for a slab reduce into gradient g, deferred on the current stream.  A second reduce into the same
+        gradient must follow the first: the stream's pending ones go out now."""
+        if g.data_ptr() in self._red_dw.get(self.stream, ()):
+            self.flush_reduces(self.stream)
+        return (ctypes.c_long * self._red_longs)()
+
+    def _reduce_close(self, g, desc):
+        """The launch that fills `desc` has been enqueued: the reduce joins its stream's batch, which goes out at 16."""
+        st = self.stream
         self._red.setdefault(st, []).append(desc)
-        dws.add(g.data_ptr())
+        self._red_dw.setdefault(st, set()).add(g.data_ptr())
         if len(self._red[st]) >= 16:
             self.flush_reduces(st)
 
@@ -576,9 +590,7 @@ class Engine:
 
     def acall(self, name, *args):
         """Call the activation-dtype instance of an entry point."""
-        if self.abl_lanes and (self.abl_lanes >> min(self.lane, 7)) & 1:
-            return
-        self.L.call_routed(self.route, name + self.sfx, *args, self.stream)
+        self.call(name + self.sfx, *args)
 
     def new_grad(self, t):
         g = torch.empty(t.data.shape, dtype=torch.float32 if t.f32grad else self.dt, device=self.dev)
@@ -611,15 +623,13 @@ class Engine:
         # backwards handing fami_bn_bwd2 the same dirty slices was a silent wrong-gradient bug.  An Engine
         # on another stream than the previous owner's first waits for that stream's work so far (the previous owner's
         # kernels may still be reading their slots); inside a capture the Trainer has synchronised the device already.
-        import weakref
+        # (This ownership logic and zeros_bytes' half of it stay written out: each line is a fixed bug.)
         st = Engine._zero_arenas.setdefault(self.dev.index, {'buf': None, 'high': 0, 'retired': [], 'owner': None,
                                                              'stream': None})
         capturing = torch.cuda.is_current_stream_capturing()
         prev = st['stream']
         if prev is not None and prev.cuda_stream != self.stream and not capturing:
-            ev = torch.cuda.Event()
-            ev.record(prev)
-            self._main.wait_event(ev)
+            self._after(prev, self._main)
         st['owner'] = weakref.ref(self)
         st['stream'] = None if capturing else self._main
         self._zst, self._zoff, self._zfilled = st, 0, 0
@@ -770,7 +780,8 @@ class Engine:
 
     def seed_nchw_split(self, x, g_nchw):
         """seed_nchw in two halves: the NCHW -> NHWC transpose now (on the current lane), the accumulation into x's gradient
-        buffer by the returned closure (call it on lane 0 after the join: several lanes may seed the same tensor)."""
+        buffer by the returned closure (call it on lane 0 after the join: several lanes may seed the same tensor).  Not
+        _add_nchw: the halves run on two lanes at two times."""
         if g_nchw is None or not x.requires_grad:
             return lambda: None
         N, H, W, C = x.shape
@@ -789,33 +800,32 @@ class Engine:
         """Add an NCHW gradient to NHWC tensor x."""
         if g_nchw is None or not x.requires_grad:
             return
+        self._add_nchw(g_nchw.contiguous(), x, _sfx)
+
+    def _add_nchw(self, src, x, sfx):
+        """NCHW tensor `src` into the NHWC gradient buffer of x: transposed straight into it, or (accumulating) into a temporary
+        that fami_axpby adds.  sfx: buffer -> the suffix of the instances to call."""
         N, H, W, C = x.shape
         g, acc = self.gbuf(x)
+        dst = self.like(g) if acc else g
+        self.call('fami_nchw_to_nhwc' + sfx(g), _p(src), _p(dst), N, C, H, W)
         if acc:
-            tmp = self.like(g)
-            self.call('fami_nchw_to_nhwc' + _sfx(g), _p(g_nchw.contiguous()), _p(tmp), N, C, H, W)
-            self.call('fami_axpby' + _sfx(g), _p(tmp), _p(g), _p(g), g.numel(), 1.0, 1.0)
-        else:
-            self.call('fami_nchw_to_nhwc' + _sfx(g), _p(g_nchw.contiguous()), _p(g), N, C, H, W)
+            self.call('fami_axpby' + sfx(g), _p(dst), _p(g), _p(g), g.numel(), 1.0, 1.0)
 
     def flush_pending(self, pend):
         """Launch the apply pass a BatchNorm deferred to its consumer (Engine.bn(defer=True)), if nothing has run it yet."""
         if pend is None or pend['done']:
             return
-        b = pend['bn']
-        self.acall('fami_bn_apply_slots', _p(pend['z']), None, _p(pend['y']), _p(b.weight.data), _p(b.bias.data), _p(pend['mean']),
-                   _p(pend['invstd']), _p(pend['rm']), _p(pend['rv']), pend['P'], pend['C'], 1, pend['mom'], pend['eps'], _p(pend['slots']))
+        self.acall('fami_bn_apply_slots', _p(pend['z']), None, _p(pend['y']), *[_p(t) for t in pend['stat']], pend['P'], pend['C'], 1,
+                   pend['mom'], pend['eps'], _p(pend['slots']))
         pend['done'] = True
 
     # ------------------------------------------------------------------ conv / bn
     def conv(self, x, weight, bias=None, stride=1, pad=0, dil=1, relu=False, out_f32=False, stats=None):
         """nn.Conv2d.  out_f32: write fp32 even in bf16 mode (heatmap-producing layers).  stats = (slots, pivot_src):
         the statistics pass of the BatchNorm that follows runs in the epilogue (fami_conv2d_fwd_stats_*)."""
-        N, H, W, Ci = x.shape
-        Co, Ci2, kh, kw = weight.shape
-        assert Ci2 == Ci, (x.shape, weight.shape)
-        Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-        Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+        geo, Ho, Wo = _geometry(x, weight, stride, pad, dil)
+        N, H, W, Ci, Co, kh, kw = geo[:7]
         wp = self.packed(weight, 0)
         flops = 2 * N * Ho * Wo * Ci * Co * kh * kw
         self.conv_flops += flops
@@ -827,16 +837,14 @@ class Engine:
             if (self.half and xb is None and not relu and not out_f32 and (kh, kw, stride, pad, dil) == (3, 3, 1, 1, 1)
                     and self.Q.fami_conv2d_fwd_bnin_ok(N, H, W, Ci, Co)):
                 y = self.act(N, Ho, Wo, Co)
-                b = pend['bn']
                 self.acall('fami_conv2d_fwd_bnin', _p(pend['z']), _p(wp), _p(None if bias is None else bias.data), _p(y), _p(x.data),
                            N, H, W, Ci, Co, _p(None if stats is None else stats[0]), _p(None if stats is None else stats[1]),
-                           _p(pend['slots']), pend['P'], _p(b.weight.data), _p(b.bias.data), _p(pend['mean']), _p(pend['invstd']),
-                           _p(pend['rm']), _p(pend['rv']), pend['mom'], pend['eps'])
+                           _p(pend['slots']), pend['P'], *[_p(t) for t in pend['stat']], pend['mom'], pend['eps'])
                 pend['done'] = True
                 self.nbnin += 1
                 if stats is not None:
                     self.nfused['fwd'] += 1
-                return self._conv_out(x, y, weight, bias, stride, pad, dil, relu, flops, xb, N, H, W, Ci, Co, kh, kw, Ho, Wo)
+                return self._conv_out(x, y, weight, bias, relu, flops, xb, geo)
             self.flush_pending(pend)
         if xb is not None:
             # x.data is z of a BatchNorm+ReLU nobody materialised: this convolution is its one consumer
@@ -865,10 +873,14 @@ class Engine:
             y = self.empty(N, Ho, Wo, Co)
             self.call('fami_conv2d_fwd_f32', _p(x.data), _p(wp), _p(None if bias is None else bias.data), None,
                       _p(y), N, H, W, Ci, Co, kh, kw, stride, pad, dil, int(relu), 0)
-        return self._conv_out(x, y, weight, bias, stride, pad, dil, relu, flops, xb, N, H, W, Ci, Co, kh, kw, Ho, Wo)
+        return self._conv_out(x, y, weight, bias, relu, flops, xb, geo)
 
-    def _conv_out(self, x, y, weight, bias, stride, pad, dil, relu, flops, xb, N, H, W, Ci, Co, kh, kw, Ho, Wo):
-        """The output tensor of Engine.conv and its backward closure (the forward launch has been enqueued)."""
+    def _conv_out(self, x, y, weight, bias, relu, flops, xb, geo):
+        """The output tensor of Engine.conv and its backward closure (the forward launch has been enqueued).  geo: _geometry's."""
+        N, H, W, Ci, Co, kh, kw, stride, pad, dil = geo
+        Ho, Wo = y.shape[1:3]
+        # (x.data is the input of a not materialised BatchNorm + ReLU: what the weight-gradient kernels apply while staging it)
+        xbn_args = None if xb is None else (xb['mean'], xb['invstd'], xb['bn'].weight.data, xb['bn'].bias.data)
         need_w = self.rq(weight) or self.rq(bias)
         out = T(y, x.requires_grad or need_w)
         wl = self.wlane_scope and self.head_wlane
@@ -876,8 +888,6 @@ class Engine:
         fuse_here = self.bn2 and self.serial_scope and self.serial_fuse     # see serial_scope in __init__
         if out.requires_grad:
             assert not relu, "fused relu epilogue is forward-only"
-            geo = (N, H, W, Ci, Co, kh, kw, stride, pad, dil)
-
             def bwd():
                 if out.grad is None:
                     return
@@ -902,8 +912,7 @@ class Engine:
                 saved = self._enter_wlane(wpair, id(weight)) if on_wl else None
                 if self.rq(weight):
                     g, acc = self.pgrad(weight)
-                    self.wgrad(x.data, dy, g, geo, acc,
-                               None if xb is None else (xb['mean'], xb['invstd'], xb['bn'].weight.data, xb['bn'].bias.data))
+                    self.wgrad(x.data, dy, g, geo, acc, xbn_args)
                     self.conv_flops += flops
                 if self.rq(bias):
                     do_bias()
@@ -940,7 +949,6 @@ class Engine:
                                  _p(rec['gamma']), _p(rec['beta']), rec['rmode'], _p(slots))
                         rec['pre_bwd'] = slots
                         self.nfused['bwd'] += 1
-                    xbn_args = None if xb is None else (xb['mean'], xb['invstd'], xb['bn'].weight.data, xb['bn'].bias.data)
                     if pair and (self.half or stats is None):
                         gw, accw = self.pgrad(weight)
                         self.conv_flops += flops
@@ -979,20 +987,35 @@ class Engine:
             return self.Q.fami_conv_t6_eligible(N, Ho, Wo, Ci, Co) != 3
         return True
 
+    def _stats_ok(self, bn, P, C):
+        """May the forward statistics of `bn` over [P, C] come out of a convolution's epilogue at all?"""
+        return self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(P, C)
+
+    def _conv_takes_stats(self, bn, geo, Ho, Wo):
+        """... and does THIS convolution's kernel take them (conv_fuses_stats)?  The XBN and the FAMI_ABL_BN1 branch of
+        conv_bn_relu_into ask _stats_ok alone."""
+        N, _, _, Ci, Co, kh, _, st, pd, dl = geo
+        return self._stats_ok(bn, N * Ho * Wo, Co) and self.conv_fuses_stats(N, Ho, Wo, Ci, Co, kh, st, pd, dl)
+
+    @staticmethod
+    def _feeds_3x3(nxt, C):
+        """Is nn.Conv2d `nxt` a 3x3 stride-1 pad-1 convolution of C inputs?"""
+        return tuple(nxt.weight.shape[1:]) == (C, 3, 3) and nxt.stride[0] == 1 and nxt.padding[0] == 1 and nxt.dilation[0] == 1
+
+    def _conv_stats(self, x, conv, bn):
+        """nn.Conv2d `conv` with the statistics pass of `bn` in its epilogue (bn None: without) -> (z, slot rows | None).  The rows
+        are taken BEFORE the convolution is enqueued: the arena offsets (and, before the arena is sized, the clearing launches)
+        follow that order."""
+        slots = None if bn is None else self.zeros_bytes(self.Q.fami_bn_slots_bytes(conv.weight.shape[0]))
+        return self.conv(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0], conv.dilation[0],
+                         stats=None if bn is None else (slots, bn.running_mean)), slots
+
     def conv_bn(self, x, conv, bn, relu=False, residual=None):
         """nn.Conv2d -> nn.BatchNorm2d (-> + residual) (-> ReLU): basic_model.py:34-63, basic_layer.py:25-26.  With a
         train-mode BatchNorm over a large enough tensor the statistics pass is the convolution's epilogue."""
-        N, H, W, _ = x.shape
-        Co, _, kh, kw = conv.weight.shape
-        st, pd, dl = conv.stride[0], conv.padding[0], conv.dilation[0]
-        Ho = (H + 2 * pd - dl * (kh - 1) - 1) // st + 1
-        Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
-        if (self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
-                and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)):
-            slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
-            z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
-            return self.bn(z, bn, relu=relu, residual=residual, pre=slots)
-        return self.bn(self.conv(x, conv.weight, conv.bias, st, pd, dl), bn, relu=relu, residual=residual)
+        geo, Ho, Wo = _conv_geometry(x, conv)
+        z, slots = self._conv_stats(x, conv, bn if self._conv_takes_stats(bn, geo, Ho, Wo) else None)
+        return self.bn(z, bn, relu=relu, residual=residual, pre=slots)
 
     def conv_bn_relu_into(self, x, conv, bn, nxt):
         """conv -> BatchNorm -> ReLU whose ONLY consumer is the 3x3 stride-1 convolution `nxt` (conv1 -> bn1 -> relu ->
@@ -1000,52 +1023,38 @@ class Engine:
         written -- conv's epilogue takes the statistics, nxt's forward and weight-gradient kernels apply scale / shift /
         ReLU while they stage z (conv_epi.h XBN), and the BatchNorm backward recomputes the ReLU mask from z.  Anything
         else falls back to conv_bn(relu=True).  FAMI_XBN (see __init__)."""
-        N, H, W, _ = x.shape
-        Co, _, kh, kw = conv.weight.shape
-        st, pd, dl = conv.stride[0], conv.padding[0], conv.dilation[0]
-        Ho = (H + 2 * pd - dl * (kh - 1) - 1) // st + 1
-        Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
+        geo, Ho, Wo = _conv_geometry(x, conv)
+        N, Co = geo[0], geo[4]
         P = N * Ho * Wo
+        stats_ok, into = self._stats_ok(bn, P, Co), self._feeds_3x3(nxt, Co)
         okq = self.Q.fami_conv2d_xbn_ok if self.half else self.Q.fami_conv2d_xbn_ok_f32
-        ok = (self.use_xbn and self.bn2 and self.defer_reduce and self.bn_batch_stats(bn) and self.fuse_bn_fwd
-              and self.defer_bn is None and bn.running_mean is not None and self.bn_fusable(P, Co)
-              and tuple(nxt.weight.shape[1:]) == (Co, 3, 3) and nxt.stride[0] == 1 and nxt.padding[0] == 1
-              and nxt.dilation[0] == 1 and okq(N, Ho, Wo, Co, nxt.weight.shape[0]))
+        ok = (self.use_xbn and self.bn2 and self.defer_reduce and stats_ok and self.defer_bn is None
+              and bn.running_mean is not None and into and okq(N, Ho, Wo, Co, nxt.weight.shape[0]))
         if not ok:
-            if self.abl_bn1 and self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(P, Co):
-                return self._abl_bn1(x, conv, bn, st, pd, dl, Co)
+            if self.abl_bn1 and stats_ok:
+                return self._abl_bn1(x, conv, bn, *geo[7:], Co)
             # 16-bit storage (round 6): the normalised tensor IS written, but by `nxt`'s own launch (Engine.conv takes the pending
             # apply pass: fami_conv2d_fwd_bnin_*) -- where conv's epilogue takes the statistics and the weight-resident kernel takes nxt
-            if (self.bn_in and self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(P, Co)
-                    and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)
-                    and tuple(nxt.weight.shape[1:]) == (Co, 3, 3) and nxt.stride[0] == 1 and nxt.padding[0] == 1
-                    and nxt.dilation[0] == 1 and self.Q.fami_conv2d_fwd_bnin_ok(N, Ho, Wo, Co, nxt.weight.shape[0])):
-                slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
-                z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
+            if (self.bn_in and self._conv_takes_stats(bn, geo, Ho, Wo) and into
+                    and self.Q.fami_conv2d_fwd_bnin_ok(N, Ho, Wo, Co, nxt.weight.shape[0])):
+                z, slots = self._conv_stats(x, conv, bn)
                 return self.bn(z, bn, relu=True, pre=slots, defer=True)
             return self.conv_bn(x, conv, bn, relu=True)
-        slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
-        z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
+        z, slots = self._conv_stats(x, conv, bn)
         self._lane_guard(('running statistics', id(bn)))
         mean, invstd = self.empty(Co), self.empty(Co)
         self.bn_trained.append(bn)
         need_p = self.rq(bn.weight)
         out = T(z.data, z.requires_grad or need_p)
-        out.xbn = {'bn': bn, 'slots': slots, 'mean': mean, 'invstd': invstd, 'P': P,
-                   'mom': 0.1 if bn.momentum is None else bn.momentum, 'used': False}
+        out.xbn = {'bn': bn, 'slots': slots, 'mean': mean, 'invstd': invstd, 'P': P, 'mom': _momentum(bn), 'used': False}
         if out.requires_grad:
             def bwd():
                 if out.grad is None:
                     return
                 gx, accx = self.gbuf(z) if z.requires_grad else (self.act(N, Ho, Wo, Co), 0)
-                gg = gb = None
-                accp = 0
-                if need_p:
-                    gg, accp = self.pgrad(bn.weight)
-                    gb, _ = self.pgrad(bn.bias)
-                self.acall('fami_bn_bwd2', _p(out.grad), _p(z.data), None, _p(mean), _p(invstd), _p(bn.weight.data),
-                           _p(bn.bias.data), _p(gx), _p(gg), _p(gb), None, P, Co, 2, accx, accp, 0,
-                           _p(self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))))
+                gg, gb, accp = self._bn_pgrads(bn, need_p)
+                self._bn_backward('two', self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co)), bn, out.grad, z.data, None,
+                                  (mean, invstd), (gx, gg, gb, None), (accx, accp, 0), P, Co, 2)
             self.record_bwd(bwd, [bn.weight, bn.bias], (z,))
         return out
 
@@ -1055,6 +1064,7 @@ class Engine:
         """FAMI_ABL_BN1 (WRONG results, timing only): conv -> statistics in its epilogue -> BatchNorm whose apply pass (bit 1:
         a one-workgroup finalize runs instead and the output aliases z) and / or backward apply pass (bit 2: the gradient
         passes through) are skipped."""
+        # (an ablation branch: its own copy of _conv_stats, on purpose)
         slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
         z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
         self._abl_skip = self.abl_bn1
@@ -1080,31 +1090,27 @@ class Engine:
             deferred = self.defer_bn is not None and bn.running_mean is not None
             if not deferred:
                 self._lane_guard(('running statistics', id(bn)))
-            mom = 0.1 if bn.momentum is None else bn.momentum
-            bn2 = self.bn2
+            mom, eps = float(_momentum(bn)), float(bn.eps)
+            # what every apply pass takes: scale, shift, the statistics it leaves, the running statistics it updates (unless deferred)
+            rm, rv = (None, None) if deferred else (bn.running_mean, bn.running_var)
+            stat = (bn.weight.data, bn.bias.data, mean, invstd, rm, rv)
             if pre is not None and (self._abl_skip & 1):
                 y = x.data
-                self.call('fami_bn_finalize_slots_f32', _p(pre), P, C, _p(mean), _p(invstd), _p(None if deferred else bn.running_mean),
-                          _p(None if deferred else bn.running_var), float(mom), float(bn.eps))
+                self.call('fami_bn_finalize_slots_f32', _p(pre), P, C, _p(mean), _p(invstd), _p(rm), _p(rv), mom, eps)
             elif pre is not None and defer and residual is None and relu:
-                pending = {'z': x.data, 'y': y, 'slots': pre, 'P': P, 'C': C, 'bn': bn, 'mean': mean, 'invstd': invstd,
-                           'rm': None if deferred else bn.running_mean, 'rv': None if deferred else bn.running_var,
-                           'mom': float(mom), 'eps': float(bn.eps), 'done': False}
+                pending = {'z': x.data, 'y': y, 'slots': pre, 'P': P, 'C': C, 'stat': stat, 'mom': mom, 'eps': eps, 'done': False}
                 self._pending.append(pending)
-            elif pre is not None:
-                self.acall('fami_bn_apply_slots', _p(x.data), _p(None if residual is None else residual.data), _p(y),
-                           _p(bn.weight.data), _p(bn.bias.data), _p(mean), _p(invstd),
-                           _p(None if deferred else bn.running_mean), _p(None if deferred else bn.running_var), P, C,
-                           int(relu), float(mom), float(bn.eps), _p(pre))
             else:
-                ws = self.zeros_bytes(self.Q.fami_bn_slots_bytes(C)) if bn2 else self.ws(self.Q.fami_bn_workspace(C))
-                self.acall('fami_bn_train_fwd2' if bn2 else 'fami_bn_train_fwd', _p(x.data),
-                           _p(None if residual is None else residual.data), _p(y),
-                           _p(bn.weight.data), _p(bn.bias.data), _p(mean), _p(invstd),
-                           _p(None if deferred else bn.running_mean), _p(None if deferred else bn.running_var), P, C,
-                           int(relu), float(mom), float(bn.eps), _p(ws))
+                if pre is not None:
+                    name, ws = 'fami_bn_apply_slots', pre
+                elif self.bn2:
+                    name, ws = 'fami_bn_train_fwd2', self.zeros_bytes(self.Q.fami_bn_slots_bytes(C))
+                else:
+                    name, ws = 'fami_bn_train_fwd', self.ws(self.Q.fami_bn_workspace(C))
+                self.acall(name, _p(x.data), _p(None if residual is None else residual.data), _p(y), *[_p(t) for t in stat],
+                           P, C, int(relu), mom, eps, _p(ws))
             if deferred:
-                self.defer_bn.append((bn, mean, invstd, P, float(mom)))
+                self.defer_bn.append((bn, mean, invstd, P, mom))
             self.bn_trained.append(bn)
         else:
             assert pre is None
@@ -1136,51 +1142,63 @@ class Engine:
                         x.grad = out.grad
                     return
                 gx, accx = self.gbuf(x) if x.requires_grad else (self.act(*shp), 0)
-                gg = gb = None
-                accp = 0
-                if need_p:
-                    gg, accp = self.pgrad(bn.weight)
-                    gb, _ = self.pgrad(bn.bias)
+                gg, gb, accp = self._bn_pgrads(bn, need_p)
                 gr, accr = (None, 0)
                 if residual is not None and residual.requires_grad:
                     gr, accr = self.gbuf(residual)
-                if not training:
-                    # frozen statistics: no batch terms, one pass; the mask comes from the stored y
-                    self.acall('fami_bn_eval_bwd', _p(out.grad), _p(x.data), _p(y), _p(mean), _p(invstd),
-                               _p(bn.weight.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, int(relu), accx, accp, accr,
-                               _p(self.ws(self.Q.fami_bn_workspace(C)) if need_p else None))
-                elif rec is not None and rec['pre_bwd'] is not None:
-                    # out.grad holds dz (mask applied) and the slot rows the two sums: fami_conv2d_dgrad_bnstats_*
-                    self.acall('fami_bn_bwd_apply_slots', _p(out.grad), _p(x.data), _p(mean), _p(invstd),
-                               _p(bn.weight.data), _p(bn.bias.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, accx, accp,
-                               accr, _p(rec['pre_bwd']))
-                elif self.bn2:
-                    self.acall('fami_bn_bwd2', _p(out.grad), _p(x.data), _p(y), _p(mean), _p(invstd),
-                               _p(bn.weight.data), _p(bn.bias.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, rmode, accx,
-                               accp, accr, _p(self.zeros_bytes(self.Q.fami_bn_slots_bytes(C))))
-                else:
-                    ws = self.ws(self.Q.fami_bn_workspace(C))
-                    self.acall('fami_bn_bwd', _p(out.grad), _p(x.data), _p(y), _p(mean), _p(invstd),
-                               _p(bn.weight.data), _p(gx), _p(gg), _p(gb), _p(gr), P, C, int(relu), accx, accp, accr,
-                               _p(ws))
+                form, ws = self._bn_bwd_form(C, training, self.bn2, need_p, None if rec is None else rec['pre_bwd'])
+                self._bn_backward(form, ws, bn, out.grad, x.data, y, (mean, invstd), (gx, gg, gb, gr), (accx, accp, accr), P, C, rmode)
             self.record_bwd(bwd, [bn.weight, bn.bias], (x, residual))
         return out
+
+    # ------------------------------------------------------------------ BatchNorm backward (bn, fuse_term, conv_bn_relu_into)
+    def _bn_pgrads(self, bn, need_p):
+        """-> (gradient buffers of bn.weight and bn.bias, their accumulate flag); (None, None, 0) when they are not trained"""
+        if not need_p:
+            return None, None, 0
+        gg, accp = self.pgrad(bn.weight)
+        gb, _ = self.pgrad(bn.bias)
+        return gg, gb, accp
+
+    def _bn_bwd_form(self, C, training, two, need_p, pre_bwd=None):
+        """-> (which backward launch a BatchNorm over C channels takes, its workspace).  Apart from the launch because the
+        workspace is allocated where the caller's sequence has it: a slot buffer taken before the arena is sized is cleared by a
+        launch of its own.
+        'eval': frozen statistics -- no batch terms, one pass, a workspace only for the parameter gradients;
+        'slots': pre_bwd, slot rows that an input-gradient epilogue (fami_conv2d_dgrad_bnstats_*) has filled -- apply pass only;
+        'two': the two-launch form (statistics into fp64 slot rows, finalize folded into the apply pass); 'three': the
+        three-launch form (deterministic mode, and fuse terms too small for slot rows)."""
+        if not training:
+            return 'eval', (self.ws(self.Q.fami_bn_workspace(C)) if need_p else None)
+        if pre_bwd is not None:
+            return 'slots', pre_bwd
+        if two:
+            return 'two', self.zeros_bytes(self.Q.fami_bn_slots_bytes(C))
+        return 'three', self.ws(self.Q.fami_bn_workspace(C))
+
+    def _bn_backward(self, form, ws, bn, dy, x, y, stats, grads, accs, P, C, rmode):
+        """The backward launch of one BatchNorm (form, ws: _bn_bwd_form's).  stats = (mean, invstd); grads = (gx, ggamma, gbeta,
+        gresidual) with accs = their accumulate flags (the two parameter gradients share one); rmode: the ReLU mask comes from
+        nowhere (0), from the stored y (1) or is recomputed from x (2) -- the eval and three-launch forms take a flag, and read y."""
+        head = [_p(dy), _p(x)]
+        st = [_p(stats[0]), _p(stats[1]), _p(bn.weight.data)]
+        tail = [*[_p(g) for g in grads], P, C]
+        if form == 'eval':
+            self.acall('fami_bn_eval_bwd', *head, _p(y), *st, *tail, int(rmode != 0), *accs, _p(ws))
+        elif form == 'slots':       # dy holds dz (mask applied)
+            self.acall('fami_bn_bwd_apply_slots', *head, *st, _p(bn.bias.data), *tail, *accs, _p(ws))
+        elif form == 'two':
+            self.acall('fami_bn_bwd2', *head, _p(y), *st, _p(bn.bias.data), *tail, rmode, *accs, _p(ws))
+        else:                       # (no beta: the mask never comes from x)
+            self.acall('fami_bn_bwd', *head, _p(y), *st, *tail, int(rmode != 0), *accs, _p(ws))
 
     # ------------------------------------------------------------------ fuse (hrnet.py:159-168)
     def conv_fuse_term(self, x, conv, bn, shift):
         """conv -> fuse term (hrnet.py:99-143: every cross-resolution path ends in conv + BatchNorm): the term's statistics
         come out of the convolution's epilogue when the tensor is large enough."""
-        N, H, W, _ = x.shape
-        Co, _, kh, kw = conv.weight.shape
-        st, pd, dl = conv.stride[0], conv.padding[0], conv.dilation[0]
-        Ho = (H + 2 * pd - dl * (kh - 1) - 1) // st + 1
-        Wo = (W + 2 * pd - dl * (kw - 1) - 1) // st + 1
-        if (self.bn_batch_stats(bn) and self.fuse_bn_fwd and self.bn_fusable(N * Ho * Wo, Co)
-                and self.conv_fuses_stats(N, Ho, Wo, conv.weight.shape[1], Co, kh, st, pd, dl)):
-            slots = self.zeros_bytes(self.Q.fami_bn_slots_bytes(Co))
-            z = self.conv(x, conv.weight, conv.bias, st, pd, dl, stats=(slots, bn.running_mean))
-            return self.fuse_term(z, bn, shift, pre=slots)
-        return self.fuse_term(self.conv(x, conv.weight, conv.bias, st, pd, dl), bn, shift)
+        geo, Ho, Wo = _conv_geometry(x, conv)
+        z, slots = self._conv_stats(x, conv, bn if self._conv_takes_stats(bn, geo, Ho, Wo) else None)
+        return self.fuse_term(z, bn, shift, pre=slots)
 
     def fuse_term(self, x, bn, shift, pre=None):
         """One term of a HighResolutionModule fuse sum (hrnet.py:151-172): its BatchNorm statistics now, its backward as
@@ -1193,14 +1211,12 @@ class Engine:
             mean, invstd = self.empty(C), self.empty(C)
             if self.bn_batch_stats(bn):
                 self._lane_guard(('running statistics', id(bn)))
-                mom = 0.1 if bn.momentum is None else bn.momentum
+                tail = (_p(mean), _p(invstd), _p(bn.running_mean), _p(bn.running_var), float(_momentum(bn)), float(bn.eps))
                 if pre is not None:
-                    self.call('fami_bn_finalize_slots_f32', _p(pre), Pk, C, _p(mean), _p(invstd), _p(bn.running_mean),
-                              _p(bn.running_var), float(mom), float(bn.eps))
+                    self.call('fami_bn_finalize_slots_f32', _p(pre), Pk, C, *tail)
                 else:
                     ws = self.ws(self.Q.fami_bn_workspace(C))
-                    self.acall('fami_bn_stats', _p(x.data), Pk, C, _p(mean), _p(invstd), _p(bn.running_mean),
-                               _p(bn.running_var), float(mom), float(bn.eps), _p(ws))
+                    self.acall('fami_bn_stats', _p(x.data), Pk, C, *tail, _p(ws))
                 self.bn_trained.append(bn)
             else:
                 assert pre is None
@@ -1223,45 +1239,16 @@ class Engine:
                     return
                 Pk = x.data.numel() // C
                 gx, accx = self.gbuf(x) if x.requires_grad else (self.like(x.data), 0)
-                gg = gb = None
-                accp = 0
-                if need_p:
-                    gg, accp = self.pgrad(bn.weight)
-                    gb, _ = self.pgrad(bn.bias)
-                st = h['stats']
-                if not training:
-                    # frozen statistics: one pass (fami_bn_eval_bwd_*), after the pooled ReLU backward for an upsampled term
-                    ws = self.ws(self.Q.fami_bn_workspace(C)) if need_p else None
-                    if shift == 0:
-                        self.acall('fami_bn_eval_bwd', _p(dy), _p(x.data), _p(y), _p(st[0]), _p(st[1]),
-                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 1, accx, accp, 0, _p(ws))
-                    else:
-                        low = self.like(x.data)
-                        self.acall('fami_pool_relu_bwd', _p(dy), _p(y), _p(low), N, H >> shift, W >> shift, C, shift, 1)
-                        self.acall('fami_bn_eval_bwd', _p(low), _p(x.data), None, _p(st[0]), _p(st[1]),
-                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 0, accx, accp, 0, _p(ws))
-                    return
-                # two-launch form (statistics into fp64 slot rows, finalize folded into the apply pass) where the BatchNorm is
-                # large enough for it -- the three-launch form's one-workgroup finalize sat between the two passes of all 53
-                # fuse-term BatchNorms of a step (5 us each)
-                two = self.bn2 and self.bn_fusable(Pk, C)
-                ws = self.zeros_bytes(self.Q.fami_bn_slots_bytes(C)) if two else self.ws(self.Q.fami_bn_workspace(C))
-                if shift == 0:
-                    if two:
-                        self.acall('fami_bn_bwd2', _p(dy), _p(x.data), _p(y), _p(st[0]), _p(st[1]), _p(bn.weight.data),
-                                   _p(bn.bias.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 1, accx, accp, 0, _p(ws))
-                    else:
-                        self.acall('fami_bn_bwd', _p(dy), _p(x.data), _p(y), _p(st[0]), _p(st[1]),
-                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 1, accx, accp, 0, _p(ws))
-                else:
+                gg, gb, accp = self._bn_pgrads(bn, need_p)
+                # train mode: the two-launch form where the BatchNorm is large enough for it -- the three-launch form's
+                # one-workgroup finalize sat between the two passes of all 53 fuse-term BatchNorms of a step (5 us each)
+                form, ws = self._bn_bwd_form(C, training, training and self.bn2 and self.bn_fusable(Pk, C), need_p)
+                mask = 1
+                if shift != 0:      # an upsampled term: the pooled ReLU backward, then the same launch with no y and no mask
                     low = self.like(x.data)
                     self.acall('fami_pool_relu_bwd', _p(dy), _p(y), _p(low), N, H >> shift, W >> shift, C, shift, 1)
-                    if two:
-                        self.acall('fami_bn_bwd2', _p(low), _p(x.data), None, _p(st[0]), _p(st[1]), _p(bn.weight.data),
-                                   _p(bn.bias.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 0, accx, accp, 0, _p(ws))
-                    else:
-                        self.acall('fami_bn_bwd', _p(low), _p(x.data), None, _p(st[0]), _p(st[1]),
-                                   _p(bn.weight.data), _p(gx), _p(gg), _p(gb), None, Pk, C, 0, accx, accp, 0, _p(ws))
+                    dy, y, mask = low, None, 0
+                self._bn_backward(form, ws, bn, dy, x.data, y, h['stats'], (gx, gg, gb, None), (accx, accp, 0), Pk, C, mask)
             self.record_bwd(bwd, [bn.weight, bn.bias] if bn is not None else [], (x,))
         return h
 
@@ -1364,13 +1351,7 @@ class Engine:
             def bwd():
                 if out.grad is None:
                     return
-                g, acc = self.gbuf(x)
-                if acc:
-                    tmp = self.like(g)
-                    self.acall('fami_nchw_to_nhwc', _p(out.grad), _p(tmp), N, C, H, W)
-                    self.acall('fami_axpby', _p(tmp), _p(g), _p(g), g.numel(), 1.0, 1.0)
-                else:
-                    self.acall('fami_nchw_to_nhwc', _p(out.grad), _p(g), N, C, H, W)
+                self._add_nchw(out.grad, x, lambda g: self.sfx)       # (the activation-dtype instances, as the forward)
             self.record_bwd(bwd, (), (x,))
         return out
 
@@ -1459,12 +1440,10 @@ class Engine:
             wp = self.empty(n)
             self.acall('fami_dcn_pack_weight', _p(weight.data), _p(wp), Co, C, kh, kw, G)   # 16-bit modes: + the 16-bit image
         y = self.act(B, H, W, Co)
-        if om:
-            assert off.shape[3] == 3 * G * K
-            self.acall('fami_dcn_fwd_om', _p(x.data), _p(off.data), _p(wp), _p(bias.data), _p(y), B, H, W, C, Co, G, kh, kw, 1, pad, dil)
-        else:
-            self.acall('fami_dcn_fwd', _p(x.data), _p(off.data), _p(msk.data), _p(wp), _p(bias.data), _p(y), B, H, W,
-                       C, Co, G, kh, kw, 1, pad, dil)
+        assert not om or off.shape[3] == 3 * G * K
+        # the merged-predictor instances (_om) take no mask tensor and return no mask gradient; nothing else differs
+        osfx, dims = '_om' if om else '', (B, H, W, C, Co, G, kh, kw, 1, pad, dil)
+        self.acall('fami_dcn_fwd' + osfx, _p(x.data), _p(off.data), *([] if om else [_p(msk.data)]), _p(wp), _p(bias.data), _p(y), *dims)
         rg = x.requires_grad or off.requires_grad or (not om and msk.requires_grad) or self.rq(weight)
         out = T(y, rg)
         wl = self.wlane_scope and self.head_wlane
@@ -1492,16 +1471,15 @@ class Engine:
                     if not om:
                         gmsk, accm = self.gbuf(msk)
                         assert acco == accm
+
+                def args(gxb):
+                    return (_p(x.data), _p(off.data), *([] if om else [_p(msk.data)]), _p(dy), _p(wpb), _p(col), _p(gxb), _p(goff),
+                            *([] if om else [_p(gmsk)]), *dims, acco)
                 if self.deterministic:
                     if x.requires_grad:
                         gx, accx = self.gbuf(x)
                     ws = self.ws(self.Q.fami_dcn_bwd_det_workspace(B, H, W, C))
-                    if om:
-                        self.acall('fami_dcn_bwd_det_om', _p(x.data), _p(off.data), _p(dy), _p(wpb), _p(col), _p(gx), _p(goff),
-                                   B, H, W, C, Co, G, kh, kw, 1, pad, dil, acco, accx, _p(ws))
-                    else:
-                        self.acall('fami_dcn_bwd_det', _p(x.data), _p(off.data), _p(msk.data), _p(dy), _p(wpb), _p(col),
-                                   _p(gx), _p(goff), _p(gmsk), B, H, W, C, Co, G, kh, kw, 1, pad, dil, acco, accx, _p(ws))
+                    self.acall('fami_dcn_bwd_det' + osfx, *args(gx), accx, _p(ws))
                 else:
                     if x.requires_grad:
                         gx, accx = self.gbuf(x)
@@ -1511,12 +1489,7 @@ class Engine:
                             gx32 = gx
                             if not accx:
                                 self.fill(gx)
-                    if om:
-                        self.acall('fami_dcn_bwd_om', _p(x.data), _p(off.data), _p(dy), _p(wpb), _p(col), _p(gx32), _p(goff),
-                                   B, H, W, C, Co, G, kh, kw, 1, pad, dil, acco)
-                    else:
-                        self.acall('fami_dcn_bwd', _p(x.data), _p(off.data), _p(msk.data), _p(dy), _p(wpb), _p(col),
-                                   _p(gx32), _p(goff), _p(gmsk), B, H, W, C, Co, G, kh, kw, 1, pad, dil, acco)
+                    self.acall('fami_dcn_bwd' + osfx, *args(gx32))
                     if gx is not None and gx32 is not gx:
                         self.acall('fami_cast_add', _p(gx32), _p(gx), gx.numel(), accx)
                 if self.rq(weight):
