@@ -56,9 +56,17 @@
   `torch.sort` between them; one upload, one download.  The ignore-region point filter, for which the reference needs
   shapely, is an even-odd crossing test in the first kernel.  The files `write_posetrack_results` wrote are its input.
 
-Out of scope: poseval's tracking metrics (`evaluateTracking`, MOTA: needs motmetrics; nothing scores the ids of
-`pose_track` yet), motion models and appearance re-identification, the PoseTrack18 `images` /
-`annotations` file layout (poseval's convert.py), per-sequence AP files and PCKh (evaluatePCKh.py).
+* `posetrack_mota` / `evaluate_posetrack_mota` / `evaluate_posetrack` -- the tracking half of the same tool
+  (`evaluate_simple.evaluate(gt_dir, pred_dir)[1]`; evaluateTracking.py:13-222, the `mot` lists of assignGTmulti,
+  py-motmetrics/motmetrics/mot.py:90-229 MOTAccumulator.update, the counts of metrics.py:196-218): per sequence and joint
+  one accumulator that remembers which predicted track every annotated track was matched to, per frame a carry-forward
+  step and a minimum-cost assignment, MISS / SWITCH / FP / MATCH counts, MOTA / MOTP / Prec / Rec.  On the device, one
+  wavefront per (sequence, joint) (csrc/posetrack_mot.hip), on the masks the AP's assign launch filtered; it scores the
+  ids `pose_track` writes.  `evaluate_posetrack` runs both halves on one pack, one upload and one assign launch.
+
+Out of scope: motmetrics' other metrics (MT / ML, fragmentations), per-sequence metric files, motion models and
+appearance re-identification, the PoseTrack18 `images` / `annotations` file layout (poseval's convert.py) and PCKh
+(evaluatePCKh.py).
 
 The reference imports its joint-name lists from modules that are missing from the released tree
 (`datasets.zoo.coco`, `datasets.zoo.posetrack.pose_topology`, keypoints_ord.py:10-11); COCO_JOINT / POSETRACK_JOINT
@@ -89,6 +97,8 @@ AP_MAX_PRED = 256               # ... one thread per predicted pose of a frame
 AP_MAX_GT = 64                  # ... the annotated poses of a frame are LDS-resident
 AP_MAX_SET = 458752             # ... one label bit per predicted pose of the set in 56 KiB of LDS
 AP_MIN_SCORE = -9999            # eval_helpers.MIN_SCORE: a predicted point without a score
+MOT_MAX_TRACKS = 256            # csrc/posetrack_mot.hip: annotated tracks of a sequence (the map m is LDS-resident)
+MOT_COUNTS = ('num_misses', 'num_switches', 'num_false_positives', 'num_detections', 'num_objects')
 POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_knee', 'left_ankle', 'right_wrist',
                    'right_elbow', 'right_shoulder', 'left_shoulder', 'left_elbow', 'left_wrist', 'neck', 'nose',
                    'head_top']
@@ -769,7 +779,7 @@ def _pack_points(points, where, with_score, unique_ids):
     return row, has
 
 
-def pack_posetrack_frames(gt_annolists, pr_annolists):
+def pack_posetrack_frames(gt_annolists, pr_annolists, seq_ids=None):
     """The frames of an evaluation set as the flat fp64 / int32 arrays `posetrack_ap` uploads.  gt_annolists and
     pr_annolists are the `annolist` frames of all sequences, one entry per frame, in the same order (what
     `load_posetrack_dirs` returns).  Frame selection is the reference's (eval_helpers.load_data_dir -> cleanupData ->
@@ -786,13 +796,31 @@ def pack_posetrack_frames(gt_annolists, pr_annolists):
     predicted or 64 annotated poses in a frame (the frame is named), an annotated pose without its head rectangle, an
     ignore region of fewer than three points, and a joint id listed twice in a frame WITH ignore regions (the reference
     filters first and then takes the first that is left; that order is not restated).  Neither input is modified (the
-    reference's assignGTmulti filters its prediction frames in place)."""
+    reference's assignGTmulti filters its prediction frames in place).
+    seq_ids (one entry per input frame, what `load_posetrack_dirs(with_seq=True)` returns; any hashable) adds what
+    `posetrack_mota` needs: gt_track [G] / pr_track [P] int32 (the `track_id` of every packed pose, renumbered from 0 in
+    order of appearance within its sequence, annotated and predicted ids apart), frame_seq [F] int32 (the sequence of
+    every kept frame, numbered in order of appearance) and seq_seg [S+1] int32 (sequence s owns the kept frames
+    seq_seg[s] .. seq_seg[s+1); a sequence may own none).  Then also ValueError for: a pose with points but no
+    `track_id`, a track id listed twice among one frame's annotated or among its predicted poses, a sequence whose
+    frames are not contiguous, more than 256 ground-truth tracks in a sequence.  Without seq_ids the dict has exactly the
+    keys above and no `track_id` is read."""
     if len(gt_annolists) != len(pr_annolists):
         raise ValueError('pack_posetrack_frames: %d ground-truth frames, %d prediction frames'
                          % (len(gt_annolists), len(pr_annolists)))
+    if seq_ids is not None and len(seq_ids) != len(gt_annolists):
+        raise ValueError('pack_posetrack_frames: %d frames, %d seq_ids' % (len(gt_annolists), len(seq_ids)))
     pr_rows, pr_has, gt_rows, gt_has, gt_head = [], [], [], [], []
     pr_seg, gt_seg, poly_seg, vert_seg, verts, kept = [0], [0], [0], [0], [], []
+    gt_track, pr_track, frame_seq, seen, maps = [], [], [], {}, ({}, {})
     for idx, (gf, pf) in enumerate(zip(gt_annolists, pr_annolists)):
+        if seq_ids is not None:
+            sid = seq_ids[idx]
+            if sid not in seen:
+                seen[sid] = len(seen)
+                maps = ({}, {})                                   # track ids are per sequence: renumbered from 0
+            elif sid != seq_ids[idx - 1]:
+                raise ValueError('pack_posetrack_frames: the frames of sequence %r are not contiguous (frame %d)' % (sid, idx))
         if len(gf['annorect']) == 0:
             continue
         where = 'frame %d' % idx
@@ -822,27 +850,51 @@ def pack_posetrack_frames(gt_annolists, pr_annolists):
             row, has = _pack_points(r['annopoints'][0]['point'], where + ' (prediction)', True, bool(regions))
             pr_rows.append(row)
             pr_has.append(has)
+        if seq_ids is not None:
+            for rects, ids, out, side in ((g_rects, maps[0], gt_track, 'annotated'), (p_rects, maps[1], pr_track, 'predicted')):
+                here = set()
+                for r in rects:
+                    tid = r.get('track_id')
+                    if tid is None or len(tid) == 0:
+                        raise ValueError('pack_posetrack_frames: a %s pose of %s has points but no track_id' % (side, where))
+                    tid = tid[0]
+                    if tid in here:
+                        raise ValueError('pack_posetrack_frames: track id %r is listed twice among the %s poses of %s'
+                                         % (tid, side, where))
+                    here.add(tid)
+                    out.append(ids.setdefault(tid, len(ids)))
+            if len(maps[0]) > MOT_MAX_TRACKS:
+                raise ValueError('pack_posetrack_frames: sequence %r has more than %d ground-truth tracks (at %s)'
+                                 % (seq_ids[idx], MOT_MAX_TRACKS, where))
+            frame_seq.append(seen[seq_ids[idx]])
         pr_seg.append(len(pr_rows))
         gt_seg.append(len(gt_rows))
         poly_seg.append(len(vert_seg) - 1)
         kept.append(idx)
     i32 = lambda a: np.asarray(a, dtype=np.int32)  # noqa: E731
-    return {'pr_xys': np.asarray(pr_rows, dtype=np.float64).reshape(-1, AP_JOINTS, 3), 'pr_has': i32(pr_has),
+    out = {'pr_xys': np.asarray(pr_rows, dtype=np.float64).reshape(-1, AP_JOINTS, 3), 'pr_has': i32(pr_has),
             'gt_xy': np.ascontiguousarray(np.asarray(gt_rows, dtype=np.float64).reshape(-1, AP_JOINTS, 3)[:, :, :2]),
             'gt_has': i32(gt_has),
             'gt_head': np.asarray(gt_head, dtype=np.float64).reshape(-1, 4), 'pr_seg': i32(pr_seg), 'gt_seg': i32(gt_seg),
             'poly_seg': i32(poly_seg), 'vert_seg': i32(vert_seg), 'verts': np.asarray(verts, dtype=np.float64).reshape(-1, 2),
             'frame_index': np.asarray(kept, dtype=np.int64)}
+    if seq_ids is not None:
+        frame_seq = i32(frame_seq)
+        out.update({'gt_track': i32(gt_track), 'pr_track': i32(pr_track), 'frame_seq': frame_seq,
+                    'seq_seg': i32(np.searchsorted(frame_seq, np.arange(len(seen) + 1)))})
+    return out
 
 
-def load_posetrack_dirs(gt_dir, pred_dir):
+def load_posetrack_dirs(gt_dir, pred_dir, with_seq=False):
     """-> (gt_annolists, pr_annolists) for `pack_posetrack_frames`: the `annolist` frames of every *.json file of gt_dir
     (sorted by name; the reference takes glob's order) and of the file of the same base name in pred_dir
     (eval_helpers.load_data_dir, :385-440).  IOError for a missing prediction file and ValueError for a prediction file
     with another number of frames, as the reference raises; ValueError for a file in the PoseTrack18 `images` /
-    `annotations` layout: its conversion (poseval's convert.py) is out of scope."""
-    gt_frames, pr_frames = [], []
-    for name in sorted(f for f in os.listdir(gt_dir) if f.endswith('.json')):
+    `annotations` layout: its conversion (poseval's convert.py) is out of scope.
+    with_seq=True: -> (gt_annolists, pr_annolists, seq_ids), seq_ids the index of the file every frame came from (the
+    reference's `seq_id`, load_data_dir :404): the third argument of `pack_posetrack_frames` for `posetrack_mota`."""
+    gt_frames, pr_frames, seq_ids = [], [], []
+    for seq, name in enumerate(sorted(f for f in os.listdir(gt_dir) if f.endswith('.json'))):
         pair = []
         for d in (gt_dir, pred_dir):
             path = osp.join(d, name)
@@ -857,9 +909,10 @@ def load_posetrack_dirs(gt_dir, pred_dir):
         if len(pair[0]) != len(pair[1]):
             raise ValueError('# prediction frames %d != # GT frames %d for %s'
                              % (len(pair[1]), len(pair[0]), osp.join(pred_dir, name)))
+        seq_ids += [seq] * len(pair[0])
         gt_frames += pair[0]
         pr_frames += pair[1]
-    return gt_frames, pr_frames
+    return (gt_frames, pr_frames, seq_ids) if with_seq else (gt_frames, pr_frames)
 
 
 def _get_cum(vals):
@@ -883,68 +936,127 @@ def posetrack_ap(frames, dist_thresh=0.5, device='cuda'):
     download.  An empty set returns the reference's values (all zeros) without device work.  ValueError for more than
     458752 predicted poses in the set (the curve kernel's cap)."""
     F = len(frames['pr_seg']) - 1
-    P, G = len(frames['pr_has']), len(frames['gt_has'])
-    names = POSETRACK_JOINT + ['total']
     if F <= 0:
-        z = np.zeros(AP_JOINTS + 1)
-        return {'ap': z.copy(), 'pre': z.copy(), 'rec': z.copy(), 'names': names, 'cum': _get_cum(z),
-                'label': np.zeros(0, np.int32), 'assigned': np.zeros(0, np.int32), 'ngt': np.zeros(AP_JOINTS, np.int32),
-                'pr_has': np.zeros(0, np.int32), 'gt_has': np.zeros(0, np.int32)}
+        return _ap_empty()
+    dist_thresh, dev = _posetrack_check('posetrack_ap', frames, dist_thresh, device, ap=True, mot=False)
+    return _ap_result(_posetrack_run('posetrack_ap', frames, dist_thresh, dev, ap=True, mot=False))
+
+
+def _ap_empty():
+    z = np.zeros(AP_JOINTS + 1)
+    return {'ap': z.copy(), 'pre': z.copy(), 'rec': z.copy(), 'names': POSETRACK_JOINT + ['total'], 'cum': _get_cum(z),
+            'label': np.zeros(0, np.int32), 'assigned': np.zeros(0, np.int32), 'ngt': np.zeros(AP_JOINTS, np.int32),
+            'pr_has': np.zeros(0, np.int32), 'gt_has': np.zeros(0, np.int32)}
+
+
+def _ap_result(raw):
+    res = raw['res']
+    return {'ap': res[0].copy(), 'pre': res[1].copy(), 'rec': res[2].copy(), 'names': POSETRACK_JOINT + ['total'],
+            'cum': _get_cum(res[0]), 'label': raw['label'], 'assigned': raw['assigned'], 'ngt': raw['ngt'],
+            'pr_has': raw['pr_has'], 'gt_has': raw['gt_has']}
+
+
+def _posetrack_check(who, frames, dist_thresh, device, ap, mot):
+    """What `posetrack_ap` / `posetrack_mota` refuse before any device work -> (dist_thresh, torch device)."""
+    F, P, G = len(frames['pr_seg']) - 1, len(frames['pr_has']), len(frames['gt_has'])
     dist_thresh = float(dist_thresh)
     if not np.isfinite(dist_thresh):
-        raise ValueError('posetrack_ap: dist_thresh must be finite')
-    if P > AP_MAX_SET:
-        raise ValueError('posetrack_ap: %d predicted poses, the limit is %d per set' % (P, AP_MAX_SET))
+        raise ValueError('%s: dist_thresh must be finite' % who)
+    if ap and P > AP_MAX_SET:
+        raise ValueError('%s: %d predicted poses, the limit is %d per set' % (who, P, AP_MAX_SET))
     counts = np.diff(frames['pr_seg']), np.diff(frames['gt_seg'])
     if counts[0].max() > AP_MAX_PRED or counts[1].max() > AP_MAX_GT:
         m = int(np.argmax((counts[0] > AP_MAX_PRED) | (counts[1] > AP_MAX_GT)))
-        raise ValueError('posetrack_ap: kept frame %d has %d predicted and %d annotated poses, the limits are %d and %d'
-                         % (m, counts[0][m], counts[1][m], AP_MAX_PRED, AP_MAX_GT))
+        raise ValueError('%s: kept frame %d has %d predicted and %d annotated poses, the limits are %d and %d'
+                         % (who, m, counts[0][m], counts[1][m], AP_MAX_PRED, AP_MAX_GT))
+    if mot:
+        seg, gt_track, pr_track = frames['seq_seg'], frames['gt_track'], frames['pr_track']
+        if len(seg) < 2 or seg[0] != 0 or seg[-1] != F or (np.diff(seg) < 0).any():
+            raise ValueError('%s: seq_seg must ascend from 0 to the %d kept frames' % (who, F))
+        if len(gt_track) != G or len(pr_track) != P:
+            raise ValueError('%s: gt_track / pr_track must have one entry per pose' % who)
+        if G and (gt_track.min() < 0 or gt_track.max() >= MOT_MAX_TRACKS):
+            raise ValueError('%s: annotated track ids must be in 0 .. %d (renumbered per sequence)' % (who, MOT_MAX_TRACKS - 1))
+        if P and pr_track.min() < 0:
+            raise ValueError('%s: predicted track ids must be >= 0' % who)
     dev = torch.device(device)
     if dev.type != 'cuda':
-        raise RuntimeError('posetrack_ap runs on the HIP path only (device is %s)' % dev)
+        raise RuntimeError('%s runs on the HIP path only (device is %s)' % (who, dev))
+    return dist_thresh, dev
+
+
+def _posetrack_run(who, frames, dist_thresh, dev, ap, mot):
+    """One upload, fami_posetrack_assign_f64, then the curve (ap) and / or the MOT launches (mot) on what it wrote, one
+    download -> the raw outputs."""
+    F, P, G = len(frames['pr_seg']) - 1, len(frames['pr_has']), len(frames['gt_has'])
     NP, NV = len(frames['vert_seg']) - 1, len(frames['verts'])
-    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), the int inputs, the int outputs, then (on an even
-    # word) ap / pre / rec -- one upload; everything from the first output on comes back in one download
+    S = len(frames['seq_seg']) - 1 if mot else 0
+    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), the int inputs, the int outputs, [the MOT step's
+    # int inputs and outputs,] then (on an even word) ap / pre / rec [and the MOT step's fp64 outputs] -- one upload;
+    # everything from the first output on comes back in one download
     f64 = [frames[k] for k in ('pr_xys', 'gt_xy', 'gt_head', 'verts')]
     i32 = [frames[k] for k in ('pr_has', 'gt_has', 'pr_seg', 'gt_seg', 'poly_seg', 'vert_seg')]
     sizes = [2 * a.size for a in f64] + [a.size for a in i32] + [P, G, P, P, F * AP_JOINTS, AP_JOINTS]
+    if mot:
+        sizes += [P, G, S + 1, S * AP_JOINTS * 5, S, AP_JOINTS * 5]
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     tail = int(off[-1] + (off[-1] & 1))
-    buf = np.zeros(tail + 2 * 3 * (AP_JOINTS + 1), dtype=np.int32)
+    n_res = 3 * (AP_JOINTS + 1)
+    buf = np.zeros(tail + 2 * (n_res + ((S + 1) * AP_JOINTS + 4 * (AP_JOINTS + 1) if mot else 0)), dtype=np.int32)
     for a, o in zip(f64, off):
         buf[o:o + 2 * a.size] = np.ascontiguousarray(a, dtype=np.float64).reshape(-1).view(np.int32)
     for a, o in zip(i32, off[4:]):
         buf[o:o + a.size] = a
+    if mot:
+        for k, o in zip(('pr_track', 'gt_track', 'seq_seg'), off[16:]):
+            buf[o:o + frames[k].size] = frames[k]
     d = torch.from_numpy(buf).to(dev)
-    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]] + [d.data_ptr() + 4 * tail]
+    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]]
+    p_res = d.data_ptr() + 4 * tail
+    p_sumd = p_res + 8 * n_res
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev).cuda_stream
         lib().call('fami_posetrack_assign_f64', p[0], p[4], p[1], p[5], p[2], p[6], p[7], p[8], p[9], p[3], P, G, F, NP, NV,
                    dist_thresh, p[10], p[11], p[12], p[13], p[14], s)
-        # plumbing between the two kernels: per joint, the predictions that still have it, by descending score
-        if P:
-            bits = torch.arange(AP_JOINTS, dtype=torch.int32, device=dev)[:, None]
-            has_out, label = d[int(off[10]):int(off[10]) + P], d[int(off[12]):int(off[12]) + P]
-            present = ((has_out[None, :] >> bits) & 1).bool()
-            score = d[:2 * P * AP_JOINTS * 3].view(torch.float64).view(P, AP_JOINTS, 3)[:, :, 2].t()
-            order = torch.sort(torch.where(present, score, score.new_tensor(float('-inf'))), dim=1, descending=True,
-                               stable=True).indices
-            lab = ((label[order] >> bits) & 1).to(torch.uint8).contiguous()
-            n_valid = present.sum(1, dtype=torch.int32).contiguous()
-        else:                                                        # annotated poses only: 15 empty lists
-            lab = torch.zeros(AP_JOINTS, dtype=torch.uint8, device=dev)
-            n_valid = torch.zeros(AP_JOINTS, dtype=torch.int32, device=dev)
-        lib().call('fami_posetrack_curve_f64', lab.data_ptr(), n_valid.data_ptr(), p[14], P, F, p[16], p[15], s)
+        if ap:
+            # plumbing between the two kernels: per joint, the predictions that still have it, by descending score
+            if P:
+                bits = torch.arange(AP_JOINTS, dtype=torch.int32, device=dev)[:, None]
+                has_out, label = d[int(off[10]):int(off[10]) + P], d[int(off[12]):int(off[12]) + P]
+                present = ((has_out[None, :] >> bits) & 1).bool()
+                score = d[:2 * P * AP_JOINTS * 3].view(torch.float64).view(P, AP_JOINTS, 3)[:, :, 2].t()
+                order = torch.sort(torch.where(present, score, score.new_tensor(float('-inf'))), dim=1, descending=True,
+                                   stable=True).indices
+                lab = ((label[order] >> bits) & 1).to(torch.uint8).contiguous()
+                n_valid = present.sum(1, dtype=torch.int32).contiguous()
+            else:                                                        # annotated poses only: 15 empty lists
+                lab = torch.zeros(AP_JOINTS, dtype=torch.uint8, device=dev)
+                n_valid = torch.zeros(AP_JOINTS, dtype=torch.int32, device=dev)
+            lib().call('fami_posetrack_curve_f64', lab.data_ptr(), n_valid.data_ptr(), p[14], P, F, p_res, p[15], s)
+        if mot:
+            # on the masks the assign launch wrote: the ignore filter runs once, and MOTA and AP see the same points
+            lib().call('fami_posetrack_mot_f64', p[0], p[10], p[1], p[11], p[2], p[6], p[7], p[8], p[16], p[17], p[18], P, G, F,
+                       S, dist_thresh, p[19], p_sumd, p[20], s)
+            lib().call('fami_posetrack_mot_final_f64', p[19], p_sumd, p[20], S, p[21], p_sumd + 8 * S * AP_JOINTS,
+                       p_sumd + 8 * (S + 1) * AP_JOINTS, s)
     out = d[int(off[10]):].cpu().numpy()
     o = [int(x - off[10]) for x in off[10:]]
-    pr_has_out, gt_has_out, label, assigned = (out[o[i]:o[i + 1]].copy() for i in range(4))
-    ngt_frame, ngt = out[o[4]:o[5]].reshape(F, AP_JOINTS), out[o[5]:o[6]].copy()
+    raw = dict(zip(('pr_has', 'gt_has', 'label', 'assigned'), (out[o[i]:o[i + 1]].copy() for i in range(4))))
+    ngt_frame, raw['ngt'] = out[o[4]:o[5]].reshape(F, AP_JOINTS), out[o[5]:o[6]].copy()
     if (ngt_frame < 0).any():
-        raise RuntimeError('posetrack_ap: the kernel refused kept frame %d' % int(np.argmax((ngt_frame < 0).any(1))))
-    res = out[tail - int(off[10]):].view(np.float64).reshape(3, AP_JOINTS + 1)
-    return {'ap': res[0].copy(), 'pre': res[1].copy(), 'rec': res[2].copy(), 'names': names, 'cum': _get_cum(res[0]),
-            'label': label, 'assigned': assigned, 'ngt': ngt, 'pr_has': pr_has_out, 'gt_has': gt_has_out}
+        raise RuntimeError('%s: the kernel refused kept frame %d' % (who, int(np.argmax((ngt_frame < 0).any(1)))))
+    dbl = out[tail - int(off[10]):].view(np.float64)
+    raw['res'] = dbl[:n_res].reshape(3, AP_JOINTS + 1)
+    if mot:
+        raw['counts'] = out[o[9]:o[10]].reshape(S, AP_JOINTS, 5).copy()
+        status = out[o[10]:o[11]]
+        if status.any():
+            raise RuntimeError('%s: the kernel refused sequence %d' % (who, int(np.argmax(status != 0))))
+        raw['totals'] = out[o[11]:o[12]].reshape(AP_JOINTS, 5).copy()
+        m = dbl[n_res:]
+        raw['sumd'], raw['sumd_tot'] = m[:S * AP_JOINTS].reshape(S, AP_JOINTS).copy(), m[S * AP_JOINTS:(S + 1) * AP_JOINTS].copy()
+        raw['table'] = m[(S + 1) * AP_JOINTS:].reshape(4, AP_JOINTS + 1).copy()
+    return raw
 
 
 def evaluate_posetrack_ap(gt_dir, pred_dir, device='cuda'):
@@ -952,3 +1064,78 @@ def evaluate_posetrack_ap(gt_dir, pred_dir, device='cuda'):
     `evaluate_simple.evaluate(gt_dir, pred_dir, eval_track=False)[0]` returns, in-process.  gt_dir holds the annolist
     ground-truth files, pred_dir the files of the same names -- the directory `write_posetrack_results` wrote to."""
     return posetrack_ap(pack_posetrack_frames(*load_posetrack_dirs(gt_dir, pred_dir)), device=device)['cum']
+
+
+# ---------------------------------------------------------------------------------------- PoseTrack MOTA (poseval)
+def _get_cum_mot(table):
+    """printTable(metrics, motHeader=True) of evaluate_simple.py:33-47: the seven group means of MOTA, then the totals of
+    MOTA, MOTP, Prec, Rec."""
+    return _get_cum(table[0]) + [float(table[r][AP_JOINTS]) for r in (1, 2, 3)]
+
+
+def _mot_result(table, totals, sumd_tot, per_seq):
+    res = {k: table[r].copy() for r, k in enumerate(('mota', 'motp', 'pre', 'rec'))}
+    res.update({k: totals[:, i].astype(np.int64) for i, k in enumerate(MOT_COUNTS)})
+    res.update({'sum_d': sumd_tot, 'per_seq': per_seq, 'names': POSETRACK_JOINT + ['total'], 'cum': _get_cum_mot(table)})
+    return res
+
+
+def _mot_empty(S):
+    nan, z = np.full(AP_JOINTS + 1, np.nan), np.zeros(AP_JOINTS + 1)
+    return _mot_result(np.stack([nan, z, nan, nan]), np.zeros((AP_JOINTS, 5), np.int32), np.zeros(AP_JOINTS),
+                       np.zeros((S, AP_JOINTS, 5), np.int32))
+
+
+def _mot_keys(who, frames):
+    if not all(k in frames for k in ('gt_track', 'pr_track', 'seq_seg')):
+        raise ValueError('%s: the frames carry no track ids; pack them with pack_posetrack_frames(gt, pr, seq_ids)' % who)
+
+
+def posetrack_mota(frames, dist_thresh=0.5, device='cuda'):
+    """PoseTrack MOTA of a set packed WITH seq_ids (`pack_posetrack_frames(gt, pr, seq_ids)`) on the device: poseval's
+    evaluateTracking -- the `mot` lists of assignGTmulti, motmetrics' MOTAccumulator.update per (sequence, joint), the
+    five counts, computeMetrics (csrc/posetrack_mot.hip; include/fami.h has the rule).  Per sequence and joint the
+    annotated poses (objects) are matched to the predicted ones (hypotheses) frame after frame at dist <= dist_thresh
+    head sizes: an object first keeps the hypothesis it had, the rest is a minimum-cost assignment; a pair that
+    contradicts the object's memory is a SWITCH, objects left are MISSes, hypotheses left FPs.  The last kept frame of
+    every sequence is not evaluated (the reference's `imgidxs[:-1]`); a sequence with ONE kept frame, for which the
+    reference raises IndexError, contributes nothing, like one with none.  A kept frame without a predicted or without
+    an annotated rect counts one MISS, one FP and one object for every joint (the reference's dummy lists).  Where
+    several assignments of a frame have equal cost (exact fp64 ties), which one is taken depends on the input alone and
+    is otherwise unspecified, as the reference's is.
+    -> dict: 'mota', 'motp', 'pre', 'rec' float64 [16] (per joint in PoseTrack order, x 100, entry 15 the mean over the
+    non-NaN joints; a joint without objects has NaN mota and rec, one without detections motp 0), 'num_misses',
+    'num_switches', 'num_false_positives', 'num_detections', 'num_objects' int64 [15], 'sum_d' float64 [15], 'per_seq'
+    int32 [S,15,5] (the five counts in that order, per sequence), 'names' [16], 'cum' (the 11 values of the reference's
+    MOT table: MOTA of Head, Shou, Elb, Wri, Hip, Knee, Ankl, then the totals of MOTA, MOTP, Prec, Rec).  One upload,
+    the assign launch of `posetrack_ap` (for the ignore filter), the two MOT launches, one download.  An empty set
+    returns the reference's values (NaN, motp 0) without device work.  ValueError for frames packed without seq_ids."""
+    _mot_keys('posetrack_mota', frames)
+    if len(frames['pr_seg']) - 1 <= 0:
+        return _mot_empty(max(len(frames['seq_seg']) - 1, 0))
+    dist_thresh, dev = _posetrack_check('posetrack_mota', frames, dist_thresh, device, ap=False, mot=True)
+    raw = _posetrack_run('posetrack_mota', frames, dist_thresh, dev, ap=False, mot=True)
+    return _mot_result(raw['table'], raw['totals'], raw['sumd_tot'], raw['counts'])
+
+
+def evaluate_posetrack_mota(gt_dir, pred_dir, device='cuda'):
+    """-> the 11 values of the reference's MOT table (`evaluate_simple.evaluate(gt_dir, pred_dir)[1]`), in-process; the
+    directories as for `evaluate_posetrack_ap`, the predictions written with `write_posetrack_results(tracks=...)`."""
+    gt, pr, seq = load_posetrack_dirs(gt_dir, pred_dir, with_seq=True)
+    return posetrack_mota(pack_posetrack_frames(gt, pr, seq), device=device)['cum']
+
+
+def evaluate_posetrack(gt_dir, pred_dir, eval_pose=True, eval_track=True, device='cuda'):
+    """The drop-in for the reference's `evaluate_simple.evaluate(gt_dir, pred_dir, eval_pose, eval_track)` -> (cum,
+    track_cum): the 8 AP values (NaN with eval_pose=False, as the reference prints them) and the 11 MOT values (None
+    with eval_track=False).  One load, one pack, one upload, ONE assign launch shared by both halves, one download."""
+    nan = [float('nan')] * 8
+    if not eval_pose and not eval_track:
+        return nan, None
+    loaded = load_posetrack_dirs(gt_dir, pred_dir, with_seq=eval_track)
+    frames = pack_posetrack_frames(*loaded)
+    if len(frames['pr_seg']) - 1 <= 0:
+        return (_ap_empty()['cum'] if eval_pose else nan), (_mot_empty(0)['cum'] if eval_track else None)
+    dist_thresh, dev = _posetrack_check('evaluate_posetrack', frames, 0.5, device, ap=eval_pose, mot=eval_track)
+    raw = _posetrack_run('evaluate_posetrack', frames, dist_thresh, dev, ap=eval_pose, mot=eval_track)
+    return (_get_cum(raw['res'][0]) if eval_pose else nan), (_get_cum_mot(raw['table']) if eval_track else None)

@@ -624,6 +624,57 @@ int fami_posetrack_assign_f64(const double* pr_xys, const int* pr_has, const dou
 int fami_posetrack_curve_f64(const unsigned char* lab, const int* n_valid, const int* ngt_frame, int P, int F,
                              double* out, int* ngt, fami_stream_t stream);
 
+/* PoseTrack MOTA, the tracking half of the same tool (poseval/py/evaluateTracking.py:13-222 computeMetrics; the `mot`
+ * part of eval_helpers.assignGTmulti, :594-612, 648-658; py-motmetrics/motmetrics/mot.py:90-229 MOTAccumulator.update;
+ * metrics.py:196-218 the counts; csrc/posetrack_mot.hip).  All pointers are DEVICE memory, aligned as above.
+ * fami_posetrack_mot_f64: the packed arrays of fami_posetrack_assign_f64, with pr_has / gt_has the masks that entry
+ *   point WROTE (pr_has_out / gt_has_out: the ignore filter runs once, MOTA and AP see the same points); pr_track [P] /
+ *   gt_track [G] the track id of every pose, >= 0, the annotated ones below 256 (ids are per sequence: the caller
+ *   renumbers them densely); seq_seg [S+1]: sequence s owns the kept frames seq_seg[s] .. seq_seg[s+1).  Work is per
+ *   sequence and per joint j: one accumulator each, its state a map m: annotated track -> the predicted track it was
+ *   last matched to (empty at the first frame).
+ *   Which frames count: all of the sequence but its LAST (evaluateTracking.py:71); a sequence of one frame (the
+ *   reference raises IndexError) or none contributes nothing.
+ *   What a frame contributes for joint j: objects = its annotated poses that still have joint j, in order, with their
+ *   track ids; hypotheses = its predicted poses that still have it.  d[o,h] = sqrt(dx^2 + dy^2) / head(o), head as
+ *   above, fp64, uncontracted: the AP's expression.  A pair is valid iff d <= dist_thresh.  The reference's quirk is
+ *   kept: a frame with no predicted rect or no annotated rect contributes for EVERY joint one object and one
+ *   hypothesis that cannot pair (one MISS, one FP, one object), whatever the other side holds, and leaves m alone.  A
+ *   rect is one that the packing kept; in a frame WITH ignore polygons, one whose mask is still non-zero.
+ *   One update:
+ *     1. carry forward: objects in order; if m[o] exists, is among the frame's hypotheses, is not taken in this frame
+ *        and the pair is valid: MATCH with D = d, both are taken (a hypothesis that two objects remember goes to the
+ *        first).
+ *     2. INV = 2 * max(valid d of the frame, step 1's pairs included) + 1; a frame without a valid d skips to 3.  Taken
+ *        rows and columns and invalid pairs cost INV, valid pairs d; the minimum-cost assignment of the rectangle
+ *        (min(rows, columns) pairs) is solved.  Every chosen pair of cost != INV is a SWITCH if m[o] exists and differs
+ *        from h, else a MATCH, D = d; then m[o] = h.  This is a minimum-COST choice, not a largest matching: the optimum
+ *        may hold fewer valid pairs.  Among several optima of equal cost the choice is a function of the input alone
+ *        and otherwise unspecified.
+ *     3. objects left are MISSes, hypotheses left are FPs.
+ *   counts [S,15,5] = num_misses, num_switches, num_false_positives, num_detections (MATCH + SWITCH), num_objects
+ *   (MATCH + SWITCH + MISS); sumd [S,15] = the sum of D; status [S] = 0.  One 64-lane wavefront per (sequence, joint),
+ *   shortest augmenting paths with every loop bounded by the caps, no atomics, no workspace: bitwise reproducible.
+ *   Returns -1 before any launch for a null or misaligned pointer (an array of extent 0 may be null), a negative
+ *   extent, F outside 1 .. (2^31 - 2) / 256, S outside 1 .. (2^31 - 2) / 75, a NaN threshold.  The tables live in device
+ *   memory and are not checked here (fami_pose_amd.evaluate.pack_posetrack_frames does): a sequence whose segment is no
+ *   sub-range of [0, F], or with a frame (the last excepted) over a cap (256 hypotheses, 64 objects), with a segment
+ *   that is no sub-range of its array, a negative track id or an annotated one >= 256, gets status[s] = 1,
+ *   counts[s,:,:] = -1, sumd[s,:] = 0 and is not processed further; other sequences are not affected.  A track id
+ *   listed twice in a frame is not detected: that sequence's counts are then unspecified (nothing else is).
+ * fami_posetrack_mot_final_f64: totals [15,5] and sumd_tot [15] = the sequences with status 0 added in index order;
+ *   table [4,16] fp64, rows mota, motp, pre, rec (evaluateTracking.py:158-192):
+ *     mota = 100 (1 - (misses + switches + fps) / objects), NaN without objects;
+ *     motp = 100 (1 - sumD / detections), 0 without detections;
+ *     pre = 100 detections / (fps + detections), NaN when that sum is 0;  rec = 100 detections / objects;
+ *   column 15 = the mean over the non-NaN joints, in joint order (NaN when there is none). */
+int fami_posetrack_mot_f64(const double* pr_xys, const int* pr_has, const double* gt_xy, const int* gt_has,
+                           const double* gt_head, const int* pr_seg, const int* gt_seg, const int* poly_seg,
+                           const int* pr_track, const int* gt_track, const int* seq_seg, int P, int G, int F, int S,
+                           double dist_thresh, int* counts, double* sumd, int* status, fami_stream_t stream);
+int fami_posetrack_mot_final_f64(const int* counts, const double* sumd, const int* status, int S, int* totals,
+                                 double* sumd_tot, double* table, fami_stream_t stream);
+
 /* ---- input pipeline on the device -------------------------------------------------------------
  * cv2.warpAffine(frame, trans, (Wd, Hd), flags=INTER_LINEAR) on the F 8-bit HWC frames of one clip (one transform
  * for key + supporting frames, datasets/zoo/posetrack/PoseTrack_Alignment.py:421-427; flip = source mirrored in x
