@@ -126,10 +126,12 @@ int fami_linear_fwd_f32(const float* x, const float* w, const float* b, float* y
   FAMI_CHECK_LAUNCH("fami_linear_fwd_f32");
   return FAMI_OK;
 }
-// dx (=|+=) dy w ; dw (=|+=) dy^T x ; db (=|+=) sum_m dy.  Any of dx / (dw,db) may be null.
+// dx (=|+=) dy w ; dw (=|+=) dy^T x ; db (=|+=) sum_m dy.  Any of dx / (dw,db) may be null; db rides on the dw launch, so
+// db without dw is refused.
 int fami_linear_bwd_f32(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int M,
                         int K, int N, int acc_dx, int acc_param, hipStream_t s) {
   FAMI_REQUIRE(dy && x && w && M > 0 && K > 0 && N > 0, "fami_linear_bwd_f32", "bad argument");
+  FAMI_REQUIRE(dw || !db, "fami_linear_bwd_f32", "bad argument (db needs dw: both come from one launch)");
   if (dx) {
     hipLaunchKernelGGL(linear_bwd_x_kernel, dim3(fami_cdiv((long)M * K, 64)), dim3(64), 0, s, dy, w, dx, M, K, N, acc_dx);
     FAMI_CHECK_LAUNCH("fami_linear_bwd_f32/dx");

@@ -428,7 +428,7 @@ template <typename T>
 static int fuse_sum_impl(int nterms, const T* const* x, const float* const* mean, const float* const* invstd,
                          const float* const* gamma, const float* const* beta, const int* shift, T* y, int N, int H,
                          int W, int C, int relu, hipStream_t s, const char* nm) {
-  FAMI_REQUIRE(nterms >= 1 && nterms <= 4 && x && shift && y && (C % 4) == 0, nm, "bad argument");
+  FAMI_REQUIRE(nterms >= 1 && nterms <= 4 && x && shift && y && N > 0 && H > 0 && W > 0 && C > 0 && (C % 4) == 0, nm, "bad argument");
   FuseArgs<T> a;
   a.nterms = nterms;
   for (int k = 0; k < 4; ++k) {
@@ -457,7 +457,7 @@ static int relu_bwd_impl(const T* dy, const T* y, T* dx, long n, int accumulate,
 template <typename T>
 static int pool_relu_bwd_impl(const T* dy, const T* y, T* out, int N, int Hl, int Wl, int C, int shift, int relu,
                               hipStream_t s, const char* nm) {
-  FAMI_REQUIRE(dy && out && (!relu || y) && (C % 4) == 0 && shift >= 0 && shift <= 4, nm, "bad argument");
+  FAMI_REQUIRE(dy && out && (!relu || y) && N > 0 && Hl > 0 && Wl > 0 && C > 0 && (C % 4) == 0 && shift >= 0 && shift <= 4, nm, "bad argument");
   hipLaunchKernelGGL(pool_relu_bwd_kernel<T>, dim3(fami_ew_grid((long)N * Hl * Wl * (C / 4))), dim3(256), 0, s, dy, y, out, N, Hl, Wl, C, shift, relu);
   FAMI_CHECK_LAUNCH(nm);
   return FAMI_OK;
@@ -598,19 +598,21 @@ int fami_adam_scaled_f32(float* p, const float* g, float* m, float* v, long n, c
 // array of n ints.  One launch per 32 pairs (the arguments travel in the kernarg segment).
 int fami_add_batch_f32(const long* ptrs, const int* counts, int n, hipStream_t s) {
   FAMI_REQUIRE(ptrs && counts && n > 0, "fami_add_batch_f32", "bad argument");
-  // The pairs of one launch run concurrently (one blockIdx.y each) with a plain read-modify-write, so a launch must not
-  // hold the same `out` twice: a repeated output closes the launch and opens the next one (same stream => the adds into one
-  // buffer happen in call order, and the result does not depend on how the pairs fall into launches).
+  // The pairs of one launch run concurrently (one blockIdx.y each) with a plain read-modify-write, so a launch must neither
+  // hold the same `out` twice nor read, as a source, an `out` it also writes: a repeated output, or a source that is an
+  // earlier output of the open launch, closes the launch and opens the next one (same stream => the adds happen in call
+  // order, and the result does not depend on how the pairs fall into launches).
   int i0 = 0;
   while (i0 < n) {
     AxpbyBatch b;
     int m = 0, maxn = 1;
     for (; m < FAMI_AXPBY_BATCH && i0 + m < n; ++m) {
+      const float* a = reinterpret_cast<const float*>(ptrs[2 * (i0 + m)]);
       float* o = reinterpret_cast<float*>(ptrs[2 * (i0 + m) + 1]);
       bool repeated = false;
-      for (int k = 0; k < m; ++k) repeated |= (b.out[k] == o);
+      for (int k = 0; k < m; ++k) repeated |= (b.out[k] == o) | (b.out[k] == a);
       if (repeated) break;
-      b.a[m] = reinterpret_cast<const float*>(ptrs[2 * (i0 + m)]);
+      b.a[m] = a;
       b.out[m] = o;
       b.n[m] = counts[i0 + m];
       if (b.n[m] > maxn) maxn = b.n[m];

@@ -263,7 +263,15 @@ __global__ __launch_bounds__(256) void softmax_kl_bwd_kernel(const float* __rest
   }
 }
 
-// flat argmax per row, first max on ties
+// numpy's order of (value, index) candidates (np.argmax / np.amax, which the reference decodes with): a NaN is above every
+// number, the larger value otherwise, and among equals -- two NaNs are equals here -- the lower index.  ohkm_select_kernel ranks
+// NaN the same way.
+__device__ __forceinline__ bool argmax_before(float ov, int oi, float bv, int bi) {
+  const bool on = ov != ov, bn = bv != bv;
+  if (on != bn) return on;
+  return (on || ov == bv) ? oi < bi : ov > bv;
+}
+// flat argmax per row, first max on ties; a row that holds a NaN gives its first NaN and maxval NaN
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ hm, long long* __restrict__ idx,
                                                           float* __restrict__ maxval, int L) {
   __shared__ float sv[4];
@@ -273,7 +281,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   int bi = 0x7fffffff;
   for (int l = threadIdx.x; l < L; l += 256) {
     const float v = hm[r * L + l];
-    if (v > bv) {
+    if (v > bv || (v != v && bv == bv)) {      // (l ascends: the first maximum, the first NaN)
       bv = v;
       bi = l;
     }
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(bv, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) {
+    if (argmax_before(ov, oi, bv, bi)) {
       bv = ov;
       bi = oi;
     }
@@ -295,7 +303,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < 4; ++k)
-      if (sv[k] > bv || (sv[k] == bv && si[k] < bi)) {
+      if (argmax_before(sv[k], si[k], bv, bi)) {
         bv = sv[k];
         bi = si[k];
       }
@@ -466,7 +474,7 @@ int fami_softmax_kl_bwd_f32(const float* A, const float* Bt, const float* stats,
   return FAMI_OK;
 }
 
-// idx[r] = first flat argmax of row r, maxval[r] (optional); hm [R,L]
+// idx[r] = first flat argmax of row r, maxval[r] (optional); hm [R,L].  NaN as in numpy: the first NaN of the row, maxval NaN.
 int fami_argmax2d_f32(const float* hm, long long* idx, float* maxval, int R, int L, hipStream_t s) {
   FAMI_REQUIRE(hm && idx && R > 0 && L > 0, "fami_argmax2d_f32", "bad argument");
   hipLaunchKernelGGL(argmax_rows_kernel, dim3(R), dim3(256), 0, s, hm, idx, maxval, L);

@@ -284,6 +284,7 @@ int fami_scale_pairs_f32(const float* in, float* out, long n, float sx, float sy
 int fami_incr_i64(long long* v, long n, fami_stream_t stream);
 /* v[i] += inc[i] : BatchNorm num_batches_tracked counters, all layers in one launch */
 int fami_add_i64(long long* v, const long long* inc, long n, fami_stream_t stream);
+/* fuse_sum and pool_relu_bwd (all three storage types) refuse non-positive N, H, W with -1 */
 int fami_fuse_sum_f32(int nterms, const float* const* x, const float* const* mean, const float* const* invstd,
                       const float* const* gamma, const float* const* beta, const int* shift, float* y, int N, int H,
                       int W, int C, int relu, fami_stream_t stream);
@@ -292,7 +293,8 @@ int fami_pool_relu_bwd_f32(const float* dy, const float* y, float* out, int N, i
                            int relu, fami_stream_t stream);
 /* out_k += a_k for n pairs of fp32 tensors in one launch per 32 pairs (the engine's lane join: lane-private gradients of a
  * module that ran on several stream lanes).  ptrs: host array of 2 n longs (a_0, out_0, a_1, out_1, ...), counts: n ints.
- * The same `out` may appear several times: a repeated output starts a new launch, so its adds happen in call order. */
+ * The same `out` may appear several times, and a pair's source may be an earlier pair's `out`: either starts a new launch, so
+ * the adds happen in call order. */
 int fami_add_batch_f32(const long* ptrs, const int* counts, int n, fami_stream_t stream);
 int fami_adam_prep_f32(float* state4, float beta1, float beta2, fami_stream_t stream);
 int fami_adam_f32(float* p, const float* g, float* m, float* v, long n, const float* state4, float beta1,
@@ -448,6 +450,7 @@ int fami_dcn_bwd_det_om_f32(const float* x, const float* om, const float* dy, co
 /* ---- dense layers of the translation regressor: nn.Linear x3 (Alignment_V15.py:69-71) ------- */
 int fami_linear_fwd_f32(const float* x, const float* w, const float* b, float* y, int M, int K, int N,
                         fami_stream_t stream);
+/* dx, dw, db may be null, except db without dw (-1: the bias gradient comes from the launch of dw) */
 int fami_linear_bwd_f32(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int M,
                         int K, int N, int acc_dx, int acc_param, fami_stream_t stream);
 
@@ -477,6 +480,8 @@ int fami_softmax_kl_fwd_f32(const float* A, const float* Bt, float* value, float
 int fami_softmax_kl_bwd_f32(const float* A, const float* Bt, const float* stats, float* dBt, int R, int L,
                             float temperature, float gscale, const float* gdev, int accumulate,
                             fami_stream_t stream);
+/* idx[r]: the first maximum of row r; NaN as in numpy (np.argmax / np.amax): the first NaN of the row, maxval NaN.
+ * fami_final_preds_f32 and fami_pck_accuracy_f32 then zero such a joint through their `maxval > 0` tests. */
 int fami_argmax2d_f32(const float* hm, long long* idx, float* maxval, int R, int L, fami_stream_t stream);
 /* get_final_preds (datasets/process/heatmaps_process.py:47-73 + transform_preds, affine_transform.py:13-43, rot 0):
  * argmax, quarter-pixel shift, inverse affine to image coordinates.  hm [B,J,H,W]; center, scale [B,2];
