@@ -312,6 +312,15 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   }
 }
 
+// transform_preds' inverse affine for rot = 0: heatmap (x, y) -> image coordinates.  The ONE copy: the integral decode returns
+// a masked joint bit for bit as the standard decode does.
+__device__ __forceinline__ void preds_affine(float x, float y, const float* __restrict__ c, float scale0,
+                                             float* __restrict__ out, int H, int W) {
+  const float s = scale0 * 200.f / (float)W;
+  out[0] = c[0] + (x - 0.5f * (float)W) * s;
+  out[1] = c[1] + (y - 0.5f * (float)H) * s;
+}
+
 // get_final_preds (datasets/process/heatmaps_process.py:47-73): per (b, j) the argmax coordinate (zeroed when the
 // maximum is <= 0), the quarter-pixel shift toward the higher neighbour, and transform_preds' inverse affine for
 // rot = 0 (affine_transform.py:13-43: uniform scale s = 200*scale[0]/W about (W/2, H/2) -> image centre).
@@ -333,9 +342,7 @@ __global__ void final_preds_kernel(const float* __restrict__ hm, const long long
     x += (dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f));
     y += (dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f));
   }
-  const float s = scale[b * 2] * 200.f / (float)W;
-  preds[r * 2 + 0] = center[b * 2 + 0] + (x - 0.5f * (float)W) * s;
-  preds[r * 2 + 1] = center[b * 2 + 1] + (y - 0.5f * (float)H) * s;
+  preds_affine(x, y, center + b * 2, scale[b * 2], preds + r * 2, H, W);
 }
 
 // PCK on heatmap argmax (engine/core/utils/evaluate.py:13-75 `calc_dists` / `dist_acc` / `accuracy`): one workgroup.
@@ -383,6 +390,209 @@ __global__ __launch_bounds__(256) void pck_kernel(const long long* __restrict__ 
     out[J + 1] = (float)avg;
     out[J + 2] = (float)cnt;
   }
+}
+
+// ---- integral (soft-argmax) coordinates: forward, L1 loss, gradient, decode (definition: include/fami.h) ----
+// One workgroup per map, the row in registers as in softmax_kl_rows_kernel (REG values per thread, L <= 256 * REG; REG = 0
+// streams).  a_l = beta * h_l is rounded on its own (mul_rn), so the forward, the gradient and the decode see the same
+// logits; fp32 sums: per thread in l order, then lanes, then waves.
+// DECODE = false: coords[r] = {cx, cy}, stats[r] = {m, Z}.
+// DECODE = true: the argmax of argmax_rows_kernel in the same walk (m = beta * max h: rounding is monotone, beta > 0),
+// out = preds [R,2] image coordinates, out2 = maxvals [R]; a joint final_preds_kernel masks gets its (0, 0).
+template <int REG, bool DECODE>
+__global__ __launch_bounds__(256) void softargmax_rows_kernel(const float* __restrict__ hm, float* __restrict__ out,
+                                                              float* __restrict__ out2,
+                                                              const float* __restrict__ center,
+                                                              const float* __restrict__ scale, int J, int H, int W,
+                                                              float beta) {
+  __shared__ float sm[4];
+  __shared__ int si[4];
+  const long r = blockIdx.x;
+  const int L = H * W;
+  const float* h = hm + r * L;
+  constexpr int NR = REG > 0 ? REG : 1;
+  float hv[NR];
+  if constexpr (REG > 0) {
+#pragma unroll
+    for (int j = 0; j < REG; ++j) {        // every load of the row in flight at once
+      const int l = threadIdx.x + j * 256;
+      hv[j] = l < L ? h[l] : -INFINITY;
+    }
+  }
+  float m, maxval = 0.f;
+  if constexpr (DECODE) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    auto take = [&](float v, int l) {      // (l ascends: the first maximum, the first NaN)
+      if (v > bv || (v != v && bv == bv)) {
+        bv = v;
+        bi = l;
+      }
+    };
+    if constexpr (REG > 0) {
+#pragma unroll
+      for (int j = 0; j < REG; ++j)
+        if (threadIdx.x + j * 256 < L) take(hv[j], threadIdx.x + j * 256);
+    } else {
+      for (int l = threadIdx.x; l < L; l += 256) take(h[l], l);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (argmax_before(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+      sm[wave] = bv;
+      si[wave] = bi;
+    }
+    __syncthreads();
+    bv = sm[0];
+    bi = si[0];
+    for (int k = 1; k < 4; ++k)
+      if (argmax_before(sm[k], si[k], bv, bi)) {
+        bv = sm[k];
+        bi = si[k];
+      }
+    maxval = bv;
+    m = mul_rn(beta, bv);
+  } else {
+    m = -INFINITY;
+    if constexpr (REG > 0) {
+#pragma unroll
+      for (int j = 0; j < REG; ++j) m = fmaxf(m, mul_rn(beta, hv[j]));
+    } else {
+      for (int l = threadIdx.x; l < L; l += 256) m = fmaxf(m, mul_rn(beta, h[l]));
+    }
+    m = block_max(m, sm);
+  }
+  float z = 0.f, sx = 0.f, sy = 0.f;
+  auto add = [&](float hl, int l) {
+    const float e = expf(mul_rn(beta, hl) - m);
+    const int y = l / W, x = l - y * W;
+    z += e;
+    sx += e * (float)x;
+    sy += e * (float)y;
+  };
+  if constexpr (REG > 0) {
+#pragma unroll
+    for (int j = 0; j < REG; ++j)
+      if (threadIdx.x + j * 256 < L) add(hv[j], threadIdx.x + j * 256);
+  } else {
+    for (int l = threadIdx.x; l < L; l += 256) add(h[l], l);
+  }
+  z = block_sum(z, sm);
+  sx = block_sum(sx, sm);
+  sy = block_sum(sy, sm);
+  if (threadIdx.x == 0) {
+    float cx = sx / z, cy = sy / z;
+    if constexpr (DECODE) {
+      if (!(maxval > 0.f)) cx = cy = 0.f;
+      const int b = (int)(r / J);
+      preds_affine(cx, cy, center + b * 2, scale[b * 2], out + r * 2, H, W);
+      out2[r] = maxval;
+    } else {
+      out[r * 2 + 0] = cx;
+      out[r * 2 + 1] = cy;
+      out2[r * 2 + 0] = m;
+      out2[r * 2 + 1] = z;
+    }
+  }
+}
+// joints [n,2] in input-image pixels -> heatmap pixels, the centre gauss_target_kernel<true> computes, rounded to fp32
+__global__ void heatmap_xy_kernel(const float* __restrict__ joints, float* __restrict__ xy, int n, double stride_x,
+                                  double stride_y) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  xy[i * 2 + 0] = (float)((double)joints[i * 2 + 0] / stride_x);
+  xy[i * 2 + 1] = (float)((double)joints[i * 2 + 1] / stride_y);
+}
+// rowval[r] = w_r (|cx - tx| / W + |cy - ty| / H)
+__global__ void integral_l1_rows_kernel(const float* __restrict__ coords, const float* __restrict__ txy,
+                                        const float* __restrict__ w, float* __restrict__ rowval, int R, float fw,
+                                        float fh) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float wr = w ? w[r] : 1.f;
+  rowval[r] = wr * (fabsf(coords[r * 2 + 0] - txy[r * 2 + 0]) / fw + fabsf(coords[r * 2 + 1] - txy[r * 2 + 1]) / fh);
+}
+__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+// dhm[r,l] (=|+=) beta p_l (gx (x_l - cx) + gy (y_l - cy)), p_l = expf(beta h_l - m) / Z from stats.
+// gcoords (soft-argmax alone): (gx, gy) = gcoords[r].  Otherwise the L1 term: (gx, gy) = g w_r (sgn(cx - tx) / W, sgn(cy - ty) / H).
+template <int REG>
+__global__ __launch_bounds__(256) void softargmax_bwd_kernel(const float* __restrict__ hm,
+                                                             const float* __restrict__ coords,
+                                                             const float* __restrict__ stats,
+                                                             const float* __restrict__ gcoords,
+                                                             const float* __restrict__ txy, const float* __restrict__ w,
+                                                             float* __restrict__ dhm, int H, int W, float beta,
+                                                             float scale, const float* gdev, int accumulate) {
+  const long r = blockIdx.x;
+  const int L = H * W;
+  const float cx = coords[r * 2 + 0], cy = coords[r * 2 + 1], m = stats[r * 2 + 0], z = stats[r * 2 + 1];
+  float gx, gy;
+  if (gcoords) {
+    gx = gcoords[r * 2 + 0] * beta;
+    gy = gcoords[r * 2 + 1] * beta;
+  } else {
+    const float g = (gdev ? gdev[0] * scale : scale) * (w ? w[r] : 1.f) * beta;
+    gx = g * (sgnf(cx - txy[r * 2 + 0]) / (float)W);
+    gy = g * (sgnf(cy - txy[r * 2 + 1]) / (float)H);
+  }
+  auto grad = [&](float hl, int l) {
+    const float p = expf(mul_rn(beta, hl) - m) / z;
+    const int y = l / W, x = l - y * W;
+    return p * (gx * ((float)x - cx) + gy * ((float)y - cy));
+  };
+  const float* h = hm + r * L;
+  float* d = dhm + r * L;
+  if constexpr (REG > 0) {
+    float hv[REG], dv[REG];
+#pragma unroll
+    for (int j = 0; j < REG; ++j) {
+      const int l = threadIdx.x + j * 256;
+      hv[j] = l < L ? h[l] : 0.f;
+      dv[j] = (accumulate && l < L) ? d[l] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < REG; ++j) {
+      const int l = threadIdx.x + j * 256;
+      if (l < L) {
+        const float v = grad(hv[j], l);
+        d[l] = accumulate ? dv[j] + v : v;
+      }
+    }
+  } else {
+    for (int l = threadIdx.x; l < L; l += 256) {
+      const float v = grad(h[l], l);
+      d[l] = accumulate ? d[l] + v : v;
+    }
+  }
+}
+// the instance by row length, as fami_softmax_kl_*: registers for L <= 4096 and L <= 8192, streaming beyond
+template <bool DECODE>
+static void launch_softargmax_rows(int R, hipStream_t s, const float* hm, float* out, float* out2, const float* center,
+                                   const float* scale, int J, int H, int W, float beta) {
+  const long L = (long)H * W;
+  if (L <= 256 * 16) hipLaunchKernelGGL((softargmax_rows_kernel<16, DECODE>), dim3(R), dim3(256), 0, s, hm, out, out2, center, scale, J, H, W, beta);
+  else if (L <= 256 * 32) hipLaunchKernelGGL((softargmax_rows_kernel<32, DECODE>), dim3(R), dim3(256), 0, s, hm, out, out2, center, scale, J, H, W, beta);
+  else hipLaunchKernelGGL((softargmax_rows_kernel<0, DECODE>), dim3(R), dim3(256), 0, s, hm, out, out2, center, scale, J, H, W, beta);
+}
+static void launch_softargmax_bwd(int R, hipStream_t s, const float* hm, const float* coords, const float* stats,
+                                  const float* gcoords, const float* txy, const float* w, float* dhm, int H, int W,
+                                  float beta, float scale, const float* gdev, int accumulate) {
+  const long L = (long)H * W;
+  if (L <= 256 * 16) hipLaunchKernelGGL(softargmax_bwd_kernel<16>, dim3(R), dim3(256), 0, s, hm, coords, stats, gcoords, txy, w, dhm, H, W, beta, scale, gdev, accumulate);
+  else if (L <= 256 * 32) hipLaunchKernelGGL(softargmax_bwd_kernel<32>, dim3(R), dim3(256), 0, s, hm, coords, stats, gcoords, txy, w, dhm, H, W, beta, scale, gdev, accumulate);
+  else hipLaunchKernelGGL(softargmax_bwd_kernel<0>, dim3(R), dim3(256), 0, s, hm, coords, stats, gcoords, txy, w, dhm, H, W, beta, scale, gdev, accumulate);
+}
+// beta finite and > 0 (NaN fails both comparisons), positive sizes, a row index that fits an int
+static bool softargmax_args_ok(long R, int H, int W, float beta) {
+  return R > 0 && R <= 0x7fffffffL && H > 0 && W > 0 && (long)H * W <= 0x7fffffffL && beta > 0.f && beta <= 3.4028234e38f;
 }
 
 #define OHKM_MAX_J 15360      // 60 KiB of the 64 KiB a workgroup may ask for without an opt-in
@@ -492,6 +702,63 @@ int fami_final_preds_f32(const float* hm, const float* center, const float* scal
   hipLaunchKernelGGL(final_preds_kernel, dim3(fami_cdiv(B * J, 64)), dim3(64), 0, s, hm, idx_ws, maxvals, center, scale,
                      preds, B, J, H, W);
   FAMI_CHECK_LAUNCH("fami_final_preds_f32");
+  return FAMI_OK;
+}
+
+// ---- integral (soft-argmax) coordinates ----
+// hm [R,H,W] -> coords [R,2] = (cx, cy) in heatmap pixels, stats [R,2] = {m, Z}
+int fami_softargmax_fwd_f32(const float* hm, float* coords, float* stats, int R, int H, int W, float beta, hipStream_t s) {
+  FAMI_REQUIRE(hm && coords && stats && softargmax_args_ok(R, H, W, beta), "fami_softargmax_fwd_f32",
+               "bad argument (beta finite and > 0, sizes positive)");
+  launch_softargmax_rows<false>(R, s, hm, coords, stats, nullptr, nullptr, 1, H, W, beta);
+  FAMI_CHECK_LAUNCH("fami_softargmax_fwd_f32");
+  return FAMI_OK;
+}
+// dhm (=|+=) d/dhm of sum_r (gcoords[r,0] cx_r + gcoords[r,1] cy_r)
+int fami_softargmax_bwd_f32(const float* hm, const float* coords, const float* stats, const float* gcoords, float* dhm,
+                            int R, int H, int W, float beta, int accumulate, hipStream_t s) {
+  FAMI_REQUIRE(hm && coords && stats && gcoords && dhm && softargmax_args_ok(R, H, W, beta), "fami_softargmax_bwd_f32",
+               "bad argument (beta finite and > 0, sizes positive)");
+  launch_softargmax_bwd(R, s, hm, coords, stats, gcoords, nullptr, nullptr, dhm, H, W, beta, 1.f, nullptr, accumulate);
+  FAMI_CHECK_LAUNCH("fami_softargmax_bwd_f32");
+  return FAMI_OK;
+}
+// joints [n,2] (input-image pixels) -> xy [n,2] heatmap pixels: the centre of fami_gauss_target_ex_f32(subpixel = 1)
+int fami_heatmap_xy_f32(const float* joints, float* xy, int n, int Hh, int Wh, int img_h, int img_w, hipStream_t s) {
+  FAMI_REQUIRE(joints && xy && n > 0 && Hh > 0 && Wh > 0 && img_h > 0 && img_w > 0, "fami_heatmap_xy_f32", "bad argument");
+  hipLaunchKernelGGL(heatmap_xy_kernel, dim3(fami_cdiv(n, 256)), dim3(256), 0, s, joints, xy, n,
+                     (double)img_w / (double)Wh, (double)img_h / (double)Hh);
+  FAMI_CHECK_LAUNCH("fami_heatmap_xy_f32");
+  return FAMI_OK;
+}
+// loss[0] = scale * sum_r w_r (|cx_r - tx_r| / W + |cy_r - ty_r| / H); w [R] or null; ws >= R floats
+int fami_integral_l1_fwd_f32(const float* coords, const float* target_xy, const float* w, float* loss, int R, int H,
+                             int W, double scale, float* ws, hipStream_t s) {
+  FAMI_REQUIRE(coords && target_xy && loss && ws && R > 0 && H > 0 && W > 0, "fami_integral_l1_fwd_f32", "bad argument");
+  hipLaunchKernelGGL(integral_l1_rows_kernel, dim3(fami_cdiv(R, 256)), dim3(256), 0, s, coords, target_xy, w, ws, R,
+                     (float)W, (float)H);
+  FAMI_CHECK_LAUNCH("fami_integral_l1_fwd_f32/rows");
+  hipLaunchKernelGGL(scalar_sum_kernel, dim3(1), dim3(256), 0, s, ws, R, scale, loss);
+  FAMI_CHECK_LAUNCH("fami_integral_l1_fwd_f32/sum");
+  return FAMI_OK;
+}
+// dhm (=|+=) (gdev ? gdev[0] : 1) * scale * d/dhm of the sum above
+int fami_integral_l1_bwd_f32(const float* hm, const float* coords, const float* stats, const float* target_xy,
+                             const float* w, float* dhm, int R, int H, int W, float beta, float scale, const float* gdev,
+                             int accumulate, hipStream_t s) {
+  FAMI_REQUIRE(hm && coords && stats && target_xy && dhm && softargmax_args_ok(R, H, W, beta), "fami_integral_l1_bwd_f32",
+               "bad argument (beta finite and > 0, sizes positive)");
+  launch_softargmax_bwd(R, s, hm, coords, stats, nullptr, target_xy, w, dhm, H, W, beta, scale, gdev, accumulate);
+  FAMI_CHECK_LAUNCH("fami_integral_l1_bwd_f32");
+  return FAMI_OK;
+}
+// hm [B,J,H,W], center/scale [B,2] -> preds [B,J,2] image coordinates of the soft-argmax, maxvals [B,J]: one launch
+int fami_softargmax_preds_f32(const float* hm, const float* center, const float* scale, float beta, float* preds,
+                              float* maxvals, int B, int J, int H, int W, hipStream_t s) {
+  FAMI_REQUIRE(hm && center && scale && preds && maxvals && B > 0 && J > 0 && softargmax_args_ok((long)B * J, H, W, beta),
+               "fami_softargmax_preds_f32", "bad argument (beta finite and > 0, sizes positive)");
+  launch_softargmax_rows<true>(B * J, s, hm, preds, maxvals, center, scale, J, H, W, beta);
+  FAMI_CHECK_LAUNCH("fami_softargmax_preds_f32");
   return FAMI_OK;
 }
 

@@ -82,7 +82,8 @@ import torch
 
 from ._lib import lib
 from .data import FLIP_PAIRS
-from .loss import _need_cuda, _p, _stream, check_blur_kernel, dark_get_final_preds, get_final_preds
+from .loss import (_need_cuda, _p, _stream, check_blur_kernel, check_integral_options, dark_get_final_preds,
+                   get_final_preds, integral_get_final_preds)
 from .zoo.registry import TEST_PHASE, VAL_PHASE
 
 COCO_JOINT = ['nose', 'left_eye', 'right_eye', 'left_ear', 'right_ear', 'left_shoulder', 'right_shoulder',
@@ -187,25 +188,30 @@ def _flip_forward(model, kf_x, sup_x):
     return model(mirror_cat(kf_x), mirror_cat(sup_x))
 
 
-def _decoder(decode, blur_kernel):
-    """-> f(heatmaps, center, scale) for decode = 'standard' (get_final_preds: quarter-pixel shift) or 'dark'
-    (dark_get_final_preds with a blur_kernel x blur_kernel Gaussian); ValueError for anything else, before any device work."""
+def _decoder(decode, blur_kernel, integral_beta=20.0):
+    """-> f(heatmaps, center, scale) for decode = 'standard' (get_final_preds: quarter-pixel shift), 'dark'
+    (dark_get_final_preds with a blur_kernel x blur_kernel Gaussian) or 'integral' (integral_get_final_preds: the soft-argmax
+    at integral_beta); ValueError for anything else, before any device work.  Each decode ignores the other's keyword."""
     if decode == 'standard':
         return get_final_preds
     if decode == 'dark':
         k = check_blur_kernel(blur_kernel)
         return lambda hm, center, scale: dark_get_final_preds(hm, center, scale, k)
-    raise ValueError("decode must be 'standard' or 'dark', got %r" % (decode,))
+    if decode == 'integral':
+        _, beta = check_integral_options(1.0, integral_beta)
+        return lambda hm, center, scale: integral_get_final_preds(hm, center, scale, beta)
+    raise ValueError("decode must be 'standard', 'dark' or 'integral', got %r" % (decode,))
 
 
 @torch.no_grad()
 def predict(model, kf_x, sup_x, center, scale, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS, decode='standard',
-            blur_kernel=11):
+            blur_kernel=11, integral_beta=20.0):
     """-> (preds [B,J,2] image coordinates, maxvals [B,J,1], final_hm [B,J,H/4,W/4]) as device tensors.
     `model` is a val/test-phase Alignment_V15 (2-tuple forward) or a train-phase one (3-tuple; MI terms ignored).
     flip=True: flip testing -- one forward on the doubled batch, final_hm is the merged map and the decode runs on it.
-    decode='dark': the distribution-aware decode (blur_kernel: odd, 9..17) instead of the quarter-pixel shift."""
-    final_preds = _decoder(decode, blur_kernel)
+    decode='dark': the distribution-aware decode (blur_kernel: odd, 9..17) instead of the quarter-pixel shift.
+    decode='integral': the soft-argmax of the map at integral_beta (loss.integral_get_final_preds)."""
+    final_preds = _decoder(decode, blur_kernel, integral_beta)
     if flip:
         final_hm = flip_merge(_flip_forward(model, kf_x, sup_x)[0], flip_pairs, shift_heatmap)
         preds, maxvals = final_preds(final_hm, center, scale)
@@ -281,14 +287,14 @@ class EvalAccumulator:
 
 @torch.no_grad()
 def evaluate_loop(model, batches, num_samples, num_joints=17, flip=False, shift_heatmap=False, flip_pairs=FLIP_PAIRS,
-                  decode='standard', blur_kernel=11):
+                  decode='standard', blur_kernel=11, integral_beta=20.0):
     """The reference's validation loop (core fn :256-309) on the HIP path.  `batches` yields
     (kf_x, sup_x, target_heatmaps | None, meta) with meta = {'image': [names], 'center': [B,2], 'scale': [B,2],
     'score': [B]}; tensors may live on the host (they are moved to the model's device).  -> EvalAccumulator.
     flip=True: flip testing -- both heads (final_hm, kf_bb_hm) are merged from one doubled-batch forward; decode and
     PCK run on the merged maps.  decode='dark': both heads are decoded with dark_get_final_preds (blur_kernel: odd, 9..17);
-    PCK stays on the argmax."""
-    final_preds = _decoder(decode, blur_kernel)
+    decode='integral': both with integral_get_final_preds at integral_beta.  PCK stays on the argmax."""
+    final_preds = _decoder(decode, blur_kernel, integral_beta)
     dev = next(model.parameters()).device
     acc = EvalAccumulator(num_samples, num_joints)
     model.eval()

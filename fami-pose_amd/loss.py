@@ -252,6 +252,132 @@ def dark_get_final_preds(batch_heatmaps, center, scale, blur_kernel=11):
     return preds, mx.unsqueeze(-1)
 
 
+def check_integral_options(weight, beta):
+    """-> (float(weight), float(beta)), or ValueError -- host arithmetic only.  weight: a finite number > 0 (the factor of
+    the integral L1 term); beta: a finite number > 0 (the soft-argmax sharpness, 1 / temperature)."""
+    for name, v in (('weight', weight), ('beta', beta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('integral L1 %s is a finite number, not %r' % (name, v))
+    if not weight > 0:
+        raise ValueError('integral L1 weight must be > 0 (None switches the term off), got %r' % (weight,))
+    if not 0 < beta <= float(np.finfo(np.float32).max):
+        raise ValueError('integral beta must be > 0 and finite in fp32, got %r' % (beta,))
+    return float(weight), float(beta)
+
+
+def _softargmax_fwd(hm, beta):
+    """hm [B,J,H,W] fp32 contiguous -> (coords [B*J,2], stats [B*J,2])"""
+    B, J, H, W = hm.shape
+    coords = torch.empty(B * J, 2, device=hm.device)
+    stats = torch.empty(B * J, 2, device=hm.device)
+    lib().call('fami_softargmax_fwd_f32', _p(hm), _p(coords), _p(stats), B * J, H, W, beta, _stream(hm))
+    return coords, stats
+
+
+class _SoftArgmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hm, beta):
+        coords, stats = _softargmax_fwd(hm, beta)
+        ctx.save_for_backward(hm, coords, stats)
+        ctx.beta = beta
+        return coords.reshape(hm.shape[0], hm.shape[1], 2).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        hm, coords, stats = ctx.saved_tensors
+        B, J, H, W = hm.shape
+        d = torch.empty_like(hm)
+        lib().call('fami_softargmax_bwd_f32', _p(hm), _p(coords), _p(stats), _p(g.float().contiguous()), _p(d), B * J, H, W,
+                   ctx.beta, 0, _stream(hm))
+        return d, None
+
+
+def soft_argmax(hm, beta=20.0):
+    """Heatmaps [B,J,H,W] (device) -> the expectation of the pixel position under softmax(beta * hm) per map, [B,J,2] =
+    (x, y) in heatmap pixels (fami_softargmax_fwd_f32; differentiable: fami_softargmax_bwd_f32).  beta = 20 is the
+    reference's heatmap temperature T = 0.05 (Alignment_V15.py:250-277)."""
+    _, beta = check_integral_options(1.0, beta)
+    _need_cuda(hm)
+    if hm.dim() != 4:
+        raise ValueError('soft_argmax takes heatmaps [B,J,H,W], got %s' % (tuple(hm.shape),))
+    return _SoftArgmax.apply(hm.float().contiguous(), beta)
+
+
+def heatmap_xy(joints, image_size, heatmap_size):
+    """joints [B,J,2|3] (input-image pixels, device) -> [B,J,2] heatmap pixels, joint / feature stride: the position
+    generate_heatmaps(encoding='subpixel') centres its Gaussian at (the same expression, rounded to fp32), and the
+    target_xy of IntegralL1Loss.  image_size / heatmap_size are (w, h)."""
+    _need_cuda(joints)
+    B, J = joints.shape[:2]
+    xy = joints[..., :2].float().contiguous()
+    out = torch.empty(B, J, 2, device=joints.device)
+    lib().call('fami_heatmap_xy_f32', _p(xy), _p(out), B * J, int(heatmap_size[1]), int(heatmap_size[0]), int(image_size[1]),
+               int(image_size[0]), _stream(joints))
+    return out
+
+
+class _IntegralL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hm, txy, w, beta, scale):
+        B, J, H, W = hm.shape
+        coords, stats = _softargmax_fwd(hm, beta)
+        out = torch.empty(1, device=hm.device)
+        ws = torch.empty(B * J, device=hm.device)
+        lib().call('fami_integral_l1_fwd_f32', _p(coords), _p(txy), _p(w), _p(out), B * J, H, W, float(scale), _p(ws),
+                   _stream(hm))
+        ctx.save_for_backward(hm, coords, stats, txy, w)
+        ctx.beta, ctx.scale = beta, scale
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        hm, coords, stats, txy, w = ctx.saved_tensors
+        B, J, H, W = hm.shape
+        d = torch.empty_like(hm)
+        lib().call('fami_integral_l1_bwd_f32', _p(hm), _p(coords), _p(stats), _p(txy), _p(w), _p(d), B * J, H, W, ctx.beta,
+                   float(ctx.scale), _p(g.reshape(1).float().contiguous()), 0, _stream(hm))
+        return d, None, None, None, None
+
+
+class IntegralL1Loss(nn.Module):
+    """Integral pose regression (Sun et al., ECCV 2018), the coordinate term the reference's train loop constructs
+    (alignment_mi_function_term6_1.py:61-69; its file was never released, so the definition is this project's, include/fami.h):
+    (1 / (B J)) sum_bj w_bj (|cx - tx| / W + |cy - ty| / H) with (cx, cy) = soft_argmax(output, beta) and target_xy [B,J,2]
+    the joint in HEATMAP pixels (joint / feature stride).  The gradient reaches `output` only."""
+
+    def __init__(self, beta=20.0, use_target_weight=True):
+        super().__init__()
+        _, self.beta = check_integral_options(1.0, beta)
+        self.use_target_weight = use_target_weight
+
+    def forward(self, output, target_xy, target_weight):
+        _need_cuda(output)
+        B, J = output.shape[:2]
+        w = target_weight.reshape(B * J).float().contiguous() if self.use_target_weight else None
+        txy = target_xy.detach().reshape(B * J, 2).float().contiguous()
+        return _IntegralL1.apply(output.float().contiguous(), txy, w, self.beta, 1.0 / (B * J))
+
+
+def integral_get_final_preds(batch_heatmaps, center, scale, beta=20.0):
+    """The integral decode: the soft-argmax of every map (soft_argmax; no blur, no Newton step) through the inverse affine of
+    get_final_preds -- one launch (fami_softargmax_preds_f32).  maxvals, and every joint the standard decode masks
+    (maximum <= 0 or NaN), are bit for bit get_final_preds'.  Same conventions: heatmaps [B,J,H,W] (device), center /
+    scale [B,2] -> (preds [B,J,2] image coordinates, maxvals [B,J,1]) as device tensors.
+    The expectation runs over the WHOLE map: a peak near a border, whose tail the map cuts off, is pulled inward (up to
+    0.29 px for a sigma-3 target at beta = 20), and mass elsewhere in the map pulls toward it."""
+    _, beta = check_integral_options(1.0, beta)
+    _need_cuda(batch_heatmaps)
+    B, J, H, W = batch_heatmaps.shape
+    dev = batch_heatmaps.device
+    c = torch.as_tensor(center, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
+    sc = torch.as_tensor(scale, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
+    preds = torch.empty(B, J, 2, device=dev)
+    mx = torch.empty(B, J, device=dev)
+    lib().call('fami_softargmax_preds_f32', _p(batch_heatmaps.float().contiguous()), _p(c), _p(sc), beta, _p(preds), _p(mx),
+               B, J, H, W, _stream(batch_heatmaps))
+    return preds, mx.unsqueeze(-1)
+
+
 def accuracy(output, target, thr=0.5):
     """PCK on heatmap argmax (evaluate.py:39-75).  -> (acc[J+1], avg_acc, cnt, pred[B,J,2] ndarray)."""
     pred, _ = get_max_preds(output)

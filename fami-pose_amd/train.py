@@ -701,6 +701,16 @@ class Trainer:
     loss_parts[0] = mse_weight * (1/B) sum_b (1/k) sum_{top-k} mean_p (w (pred - gt))^2, and the seeds are
     fami_wmse_bwd_f32 on the selected weights with mse_weight / (B L k).  k = J is the default loss.  PCK and the MI
     terms are untouched.  ohkm_selection() is the last step's selection.
+
+    integral_l1_weight = W_I (needs targets_from_joints; None = none): the integral L1 coordinate term, loss.IntegralL1Loss
+    (definition: include/fami.h) -- W_I / (B J) sum_bj w_bj (|cx - tx| / W + |cy - ty| / H) with (cx, cy) the soft-argmax of the
+    final map at integral_beta and (tx, ty) = joint / stride.  Fixed at construction and baked into the captured plans.
+    Behind the heatmap loss: fami_softargmax_fwd_f32, fami_heatmap_xy_f32, fami_integral_l1_fwd_f32; its seed
+    fami_integral_l1_bwd_f32 directly behind fami_wmse_bwd_f32, accumulating into the same buffer under the same loss scale.
+    It reads the target weights, also where OHKM selects.  loss_parts keeps its 7 entries: the term lives in its own device
+    scalar (integral_loss_value(); loss_value() and window_loss_value() include it; under accumulation its window sum is a
+    tensor of its own and accum_state_dict() gains 'integral_loss_sum').  integral_coords(): the last step's coordinates.
+    LOSS.INTEGRAL_L1.USE / .WEIGHT in from_cfg.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
@@ -708,7 +718,7 @@ class Trainer:
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
                  weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None,
                  ema_decay=None, ema_warmup=False, frozen_bn=None, target_encoding='quantised', joint_weights=None,
-                 ohkm_topk=None):
+                 ohkm_topk=None, integral_l1_weight=None, integral_beta=20.0):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
@@ -717,8 +727,16 @@ class Trainer:
         (class docstring; None = 1).  ema_decay / ema_warmup: the moving average of the weights (class docstring; None =
         none).  frozen_bn: None, 'all', 'backbone' or module-name prefixes -- freeze_batchnorm(model, frozen_bn) before
         anything is captured (class docstring; None leaves the model's flags as they are).  target_encoding / joint_weights
-        / ohkm_topk: the options of the supervision (class docstring; no config key but joint_weights')."""
-        from .loss import check_ohkm_topk, check_target_options
+        / ohkm_topk: the options of the supervision (class docstring; no config key but joint_weights').
+        integral_l1_weight / integral_beta: the integral L1 coordinate term (class docstring; LOSS.INTEGRAL_L1.USE / .WEIGHT;
+        None = none)."""
+        from .loss import check_integral_options, check_ohkm_topk, check_target_options
+        self.integral_l1_weight = self.integral_beta = None
+        if integral_l1_weight is not None:
+            self.integral_l1_weight, self.integral_beta = check_integral_options(integral_l1_weight, integral_beta)
+            if not targets_from_joints:
+                raise ValueError('integral_l1_weight supervises the joint position itself: it needs targets_from_joints=True '
+                                 '(precomputed targets carry no real-valued position; loss.IntegralL1Loss takes one)')
         num_joints = getattr(model, 'num_joints', None)
         self.subpixel, self.joint_weights = check_target_options(target_encoding, joint_weights, num_joints)
         if (self.subpixel or self.joint_weights is not None) and not targets_from_joints:
@@ -855,6 +873,15 @@ class Trainer:
                          torch.tensor(self.joint_weights, dtype=torch.float32, device=self.dev))
         self._sel_w = {}          # OHKM: (B, J) -> selected weights [B*J], written by that batch shape's launches
         self._sel_key = None      # ... and the shape of the last step
+        # integral L1 term: its device scalar of the last step, (B, J) -> (coords, stats, target_xy) [B*J,2] each, the shape of
+        # the last step, and under accumulation {open window, last closed window} sums of the scalar
+        self.integral_loss = self._window_integral = None
+        self._int_bufs = {}
+        self._int_key = None
+        if self.integral_l1_weight is not None:
+            self.integral_loss = torch.zeros(1, device=self.dev)
+            if self.accum_steps > 1:
+                self._window_integral = torch.zeros(2, 1, device=self.dev)
         if hasattr(model, '_ensure_nbt'):
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
@@ -879,6 +906,9 @@ class Trainer:
                 raise ValueError('LOSS.USE_DIFFERENT_JOINTS_WEIGHT: the only vector at hand is PoseTrack\'s for %d joints, the '
                                  'model has %d -- pass joint_weights=' % (len(JOINTS_WEIGHT), cfg['MODEL']['NUM_JOINTS']))
             kw['joint_weights'] = JOINTS_WEIGHT
+        integral = cfg.get('LOSS', {}).get('INTEGRAL_L1', {})      # mppe_config.py:217-219, core fn :61-69
+        if integral.get('USE', False):
+            kw['integral_l1_weight'] = integral.get('WEIGHT', 1.0)
         kw.update(trainer_kw)
         return cls(model, **kw)
 
@@ -1040,6 +1070,18 @@ class Trainer:
             eng.call('fami_ohkm_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]),
                      _p(self._sel_w[self._sel_key]), B, J, L, self.ohkm_topk, float(scale), _p(ws))
             w = self._sel_w[self._sel_key]
+        if self.integral_l1_weight is not None:
+            # the coordinate term: soft-argmax of the final map against joint / stride, on the TARGET weights (not OHKM's)
+            self._int_key = (B, J)
+            if self._int_key not in self._int_bufs:
+                self._int_bufs[self._int_key] = tuple(torch.zeros(B * J, 2, device=self.dev) for _ in range(3))
+            coords, stats, txy = self._int_bufs[self._int_key]
+            tw = weight.reshape(B * J)
+            iscale = self.integral_l1_weight / (B * J)
+            eng.call('fami_softargmax_fwd_f32', _p(final_nchw), _p(coords), _p(stats), B * J, Hh, Wh, self.integral_beta)
+            eng.call('fami_heatmap_xy_f32', _p(joints), _p(txy), B * J, Hh, Wh, kf_x.shape[2], kf_x.shape[3])
+            eng.call('fami_integral_l1_fwd_f32', _p(coords), _p(txy), _p(tw), _p(self.integral_loss), B * J, Hh, Wh,
+                     float(iscale), _p(eng.ws(B * J * 4)))
         if self.pck:
             # accuracy(pred_heatmaps, target) and accuracy(kf_bb_heatmaps, target), core fn :159-163, without the four
             # device-to-host heatmap copies
@@ -1054,6 +1096,9 @@ class Trainer:
         ls, ls_dev = (1.0, self.scaler_state[0:1]) if self.dynamic_scale else (self.loss_scale, None)
         dpred = torch.empty_like(final_nchw)
         eng.call('fami_wmse_bwd_f32', _p(final_nchw), _p(target), _p(w), _p(dpred), B * J, L, float(scale * ls), _p(ls_dev), 0)
+        if self.integral_l1_weight is not None:
+            eng.call('fami_integral_l1_bwd_f32', _p(final_nchw), _p(coords), _p(stats), _p(txy), _p(tw), _p(dpred), B * J,
+                     Hh, Wh, self.integral_beta, float(iscale * ls), _p(ls_dev), 1)
         eng.seed_nchw(aux['final'], dpred)
         if self.use_mi and aux['mis']:
             a, b = self.alpha, self.beta
@@ -1110,6 +1155,13 @@ class Trainer:
         if self._sel_key is None:
             return None
         return (self._sel_w[self._sel_key] != 0).reshape(self._sel_key)
+
+    def integral_coords(self):
+        """integral_l1_weight: the soft-argmax coordinates the last step's loss saw, a device tensor [B,J,2] in heatmap pixels
+        (None without the option or before the first step)."""
+        if self._int_key is None or self._int_key not in self._int_bufs:
+            return None
+        return self._int_bufs[self._int_key][0].reshape(*self._int_key, 2)
 
     def skipped_steps(self):
         """Optimizer steps skipped so far because the loss-scaled gradients held inf / NaN (fp16 mode; synchronises).
@@ -1389,6 +1441,10 @@ class Trainer:
         w = self._window_loss
         self._lc('fami_axpby_f32', _p(self.loss_parts), _p(w[0]) if self.window_position else None, _p(w[1 if closing else 0]),
                  7, 1.0, 1.0, _stream(self.dev))
+        if self._window_integral is not None:       # ... and the integral term into a sum of its own
+            wi = self._window_integral
+            self._lc('fami_axpby_f32', _p(self.integral_loss), _p(wi[0]) if self.window_position else None,
+                     _p(wi[1 if closing else 0]), 1, 1.0, 1.0, _stream(self.dev))
         self.window_position = 0 if closing else self.window_position + 1
 
     def reset_window(self):
@@ -1400,15 +1456,22 @@ class Trainer:
         only).  None without accumulation."""
         if self._window_loss is None:
             return None
-        return self._total_loss((self._window_loss[1] / self.accum_steps).tolist())
+        total = self._total_loss((self._window_loss[1] / self.accum_steps).tolist())
+        if self._window_integral is not None:
+            total += self._window_integral[1].item() / self.accum_steps
+        return total
 
     def accum_state_dict(self):
         """The 'grad_accum' checkpoint entry: {'steps': N, 'position': k} and, inside a window (k > 0), the accumulation
-        arena and the open window's loss sum on the host (synchronises)."""
+        arena and the open window's loss sum on the host (synchronises); with integral_l1_weight also 'integral_loss_sum',
+        the open window's sum of that term."""
         sd = {'steps': self.accum_steps, 'position': self.window_position}
         if self.window_position > 0:
             sd['arena'] = self.accum.detach().cpu().clone()
             sd['loss_sum'] = self._window_loss[0].detach().cpu().clone()
+            wi = getattr(self, '_window_integral', None)      # (getattr: checkpoint code borrows this method for host objects)
+            if wi is not None:
+                sd['integral_loss_sum'] = wi[0].detach().cpu().clone()
         return sd
 
     def load_accum_state_dict(self, sd):
@@ -1422,6 +1485,11 @@ class Trainer:
         if k > 0:
             self.accum.copy_(sd['arena'])
             self._window_loss[0].copy_(sd['loss_sum'])
+            wi = getattr(self, '_window_integral', None)
+            if wi is not None:
+                if 'integral_loss_sum' not in sd:
+                    raise ValueError('the checkpoint was written inside a window without the integral L1 term')
+                wi[0].copy_(sd['integral_loss_sum'])
         self.window_position = k
 
     def _accum_eager_step(self, kf_x, sup_x, target, weight):
@@ -1623,6 +1691,8 @@ class Trainer:
                              (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape)))
         if self.ohkm_topk is not None:
             self._sel_key = (target.shape[0], target.shape[1])       # (a replay does not pass through _forward_backward)
+        if self.integral_l1_weight is not None:
+            self._int_key = (target.shape[0], target.shape[1])
         if not self.use_graph:
             return self._eager_step(kf_x, sup_x, target, weight)
         key = (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape))
@@ -1663,7 +1733,12 @@ class Trainer:
 
     def loss_value(self):
         """Total loss of the last step (host float; forces a sync -- logging only)."""
-        return self._total_loss(self.loss_parts.tolist())
+        return self._total_loss(self.loss_parts.tolist()) + self.integral_loss_value()
+
+    def integral_loss_value(self):
+        """The integral L1 term of the last step, weight included (host float; forces a sync -- logging only); 0.0 without
+        integral_l1_weight."""
+        return 0.0 if self.integral_loss is None else self.integral_loss.item()
 
     def _total_loss(self, p):
         """[mse * W, mi_1..mi_6] -> the loss the reference optimises (core fn :119-148)"""

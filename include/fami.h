@@ -506,6 +506,42 @@ int fami_dark_preds_f32(const float* hm, const float* center, const float* scale
 long fami_dark_preds_lds_bytes(int H, int W, int k);
 long fami_dark_preds_lds_limit(void);
 
+/* ---- integral (soft-argmax) coordinates: loss term and decode (csrc/loss.hip) -------------------
+ * Integral pose regression (Sun et al., ECCV 2018): an L1 loss on the soft-argmax of the heatmap -- the term the
+ * reference's train loop constructs (alignment_mi_function_term6_1.py:61-69, LOSS.INTEGRAL_L1.USE / .WEIGHT) from a file
+ * that was never released.  This project's definition; beta = 1 / T with the reference's heatmap temperature T = 0.05.
+ * Row: one heatmap hm[b, j] of H x W fp32 values h_i at pixel (x_i, y_i), x in 0..W-1, y in 0..H-1.
+ * Forward: a_i = beta * h_i (ONE fp32 rounding, never contracted), m = max a_i, e_i = expf(a_i - m), Z = sum e_i,
+ *   cx = sum e_i x_i / Z, cy = sum e_i y_i / Z in heatmap pixels; coords[r] = {cx, cy}, stats[r] = {m, Z}.
+ * Target position (tx, ty): the joint in heatmap pixels, joint / feature stride -- fami_heatmap_xy_f32 evaluates the
+ *   expression fami_gauss_target_ex_f32(subpixel = 1) centres its Gaussian at, (double)joint / ((double)img / size), and
+ *   rounds it to fp32.
+ * Loss: L = scale * sum_r w_r (|cx_r - tx_r| / W + |cy_r - ty_r| / H); w [R] (the target weights; NULL: 1); the row values
+ *   are summed in fp64 in a fixed order as in fami_wmse_fwd_f32 (ws: R floats).  The caller's scale is weight / (B J).
+ * Backward: dhm[r,i] (=|+=) g w_r beta p_i (sgn(cx - tx) (x_i - cx) / W + sgn(cy - ty) (y_i - cy) / H) with
+ *   p_i = expf(beta h_i - m) / Z recomputed from stats, sgn(0) = 0, g = scale * (gdev ? gdev[0] : 1): the
+ *   fami_wmse_bwd_f32 convention.  fami_softargmax_bwd_f32 is the soft-argmax alone:
+ *   dhm[r,i] (=|+=) beta p_i (gcoords[r,0] (x_i - cx) + gcoords[r,1] (y_i - cy)).
+ * Decode: argmax and maxvals exactly those of fami_final_preds_f32; coordinates (cx, cy) through the same inverse affine
+ *   (transform_preds, rot 0).  A joint the standard decode masks (`maxval > 0` false, NaN included) returns bit for bit
+ *   what fami_final_preds_f32 returns.  One launch, no workspace, no host read-back.
+ * No atomics, one 256-thread workgroup per row, the row in registers for H W <= 4096 and <= 8192 and streamed beyond, any
+ * W and alignment; run-to-run bitwise reproducible.  Heatmaps are fp32 at this boundary in every compute mode.
+ * beta not finite or <= 0, or a non-positive size: -1, nothing written. */
+int fami_softargmax_fwd_f32(const float* hm, float* coords, float* stats, int R, int H, int W, float beta,
+                            fami_stream_t stream);
+int fami_softargmax_bwd_f32(const float* hm, const float* coords, const float* stats, const float* gcoords, float* dhm,
+                            int R, int H, int W, float beta, int accumulate, fami_stream_t stream);
+int fami_heatmap_xy_f32(const float* joints_xy, float* xy, int n, int Hh, int Wh, int img_h, int img_w,
+                        fami_stream_t stream);
+int fami_integral_l1_fwd_f32(const float* coords, const float* target_xy, const float* w, float* loss, int R, int H,
+                             int W, double scale, float* ws, fami_stream_t stream);
+int fami_integral_l1_bwd_f32(const float* hm, const float* coords, const float* stats, const float* target_xy,
+                             const float* w, float* dhm, int R, int H, int W, float beta, float scale, const float* gdev,
+                             int accumulate, fami_stream_t stream);
+int fami_softargmax_preds_f32(const float* hm, const float* center, const float* scale, float beta, float* preds,
+                              float* maxvals, int B, int J, int H, int W, fami_stream_t stream);
+
 /* PCK accuracy on heatmap argmax, engine/core/utils/evaluate.py:39-75 (`accuracy`, called twice per training step at
  * engine/core/functions/alignment_mi_function_term6_1.py:159-163 after D2H copies of four heatmap stacks): here
  * three launches and no host sync.  pred_hm / target_hm [B,J,H,W]; out[J+3] = {acc[0] = mean of the defined
