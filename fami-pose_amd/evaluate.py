@@ -64,6 +64,16 @@
   wavefront per (sequence, joint) (csrc/posetrack_mot.hip), on the masks the AP's assign launch filtered; it scores the
   ids `pose_track` writes.  `evaluate_posetrack` runs both halves on one pack, one upload and one assign launch.
 
+* `pack_coco_keypoints` / `coco_keypoint_ap` / `load_coco_keypoints` / `evaluate_coco_keypoints` /
+  `coco_keypoint_results` / `EvalAccumulator.coco_results` -- the fourth step of the HRNet protocol, the number it reports:
+  pycocotools' `COCOeval(gt, dt, 'keypoints')` (AP, AP50, AP75, AP-medium, AP-large and the five ARs) for one category.
+  pycocotools is no part of the reference tree (oracle/ref_harness.py stubs it), so include/fami.h restates the definition
+  in full.  In-process, in fp64 on the device: one workgroup per image ranks and cuts the detections, fills the OKS matrix
+  and runs the 30 greedy walks (10 thresholds x 3 area ranges); one workgroup per (range, threshold) reads the curve at the
+  101 recall thresholds (csrc/coco_ap.hip); a stable `torch.sort` between them, one upload, one download.  It scores what
+  `pose_nms` keeps by the similarity `pose_nms` uses.  Box / segm IoU types, several categories, COCOeval's `scores` and
+  `evalImgs` and COCO dataset indexing are out of scope.
+
 Out of scope: motmetrics' other metrics (MT / ML, fragmentations), per-sequence metric files, motion models and
 appearance re-identification, the PoseTrack18 `images` / `annotations` file layout (poseval's convert.py) and PCKh
 (evaluatePCKh.py).
@@ -283,6 +293,14 @@ class EvalAccumulator:
         `write_posetrack_results`.  The accumulator itself is not modified."""
         fmap = self.filenames_map if filenames_map is None else filenames_map
         return pose_track(self.all_preds[:self.idx], self.all_boxes[:self.idx], fmap, **kw)
+
+    def coco_results(self, image_ids, keep=None, boxes=None, category_id=1):
+        """Everything accumulated so far as COCO result dicts (module-level `coco_keypoint_results`): image_ids [idx] the
+        COCO image id of every row, keep the keep map of `pose_nms` (or a flat list of rows), boxes the rescored copy it
+        returned (default: all_boxes, the detector's box scores) -- so pose_nms -> coco_results -> pack_coco_keypoints ->
+        coco_keypoint_ap runs without a file.  The accumulator itself is not modified."""
+        boxes = self.all_boxes[:self.idx] if boxes is None else boxes
+        return coco_keypoint_results(self.all_preds[:self.idx], boxes, image_ids, keep=keep, category_id=category_id)
 
 
 @torch.no_grad()
@@ -1145,3 +1163,292 @@ def evaluate_posetrack(gt_dir, pred_dir, eval_pose=True, eval_track=True, device
     dist_thresh, dev = _posetrack_check('evaluate_posetrack', frames, 0.5, device, ap=eval_pose, mot=eval_track)
     raw = _posetrack_run('evaluate_posetrack', frames, dist_thresh, dev, ap=eval_pose, mot=eval_track)
     return (_get_cum(raw['res'][0]) if eval_pose else nan), (_get_cum_mot(raw['table']) if eval_track else None)
+
+
+# ---------------------------------------------------------------------------------------- COCO keypoint AP / AR (pycocotools)
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)     # Params.setKpParams
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+COCO_AREA_RNGS = np.array([[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)  # all, medium, large
+COCO_MAX_DETS = 20
+COCO_MAX_PER_IMAGE = 256        # csrc/coco_ap.hip: one thread per detection of an image (before the cut)
+COCO_MAX_GT = 128               # ... the annotations of an image are LDS-resident
+COCO_MAX_KEPT = 64              # ... the largest max_dets
+COCO_MAX_SET = 229376           # ... two bits per kept detection of the set in 56 KiB of LDS
+COCO_STAT_NAMES = ['AP', 'AP50', 'AP75', 'AP_M', 'AP_L', 'AR', 'AR50', 'AR75', 'AR_M', 'AR_L']
+
+
+def _coco_rows(anns, what, J):
+    """The keypoint lists of `anns` as one [n,J,3] float64 array (J: None = taken from the first list) -> (array, J)."""
+    rows = []
+    for i, a in enumerate(anns):
+        k = a.get('keypoints')
+        if k is None or not hasattr(k, '__len__'):
+            raise ValueError('pack_coco_keypoints: %s %d has no keypoint list' % (what, i))
+        if J is None:
+            J = len(k) // 3
+            if len(k) != 3 * J or not 1 <= J <= NMS_MAX_JOINTS:
+                raise ValueError('pack_coco_keypoints: %s %d has %d keypoint values; 3 x J with J in 1 .. %d is supported'
+                                 % (what, i, len(k), NMS_MAX_JOINTS))
+        if len(k) != 3 * J:
+            raise ValueError('pack_coco_keypoints: %s %d has %d keypoint values, not 3 x %d' % (what, i, len(k), J))
+        rows.append(k)
+    try:
+        arr = np.asarray(rows, dtype=np.float64).reshape(-1, J or 1, 3)
+    except (TypeError, ValueError):
+        raise ValueError('pack_coco_keypoints: the keypoints of a %s are not numbers' % what)
+    if not np.isfinite(arr).all():
+        raise ValueError('pack_coco_keypoints: %s %d has a non-finite keypoint value'
+                         % (what, int(np.argmax(~np.isfinite(arr).all(axis=(1, 2))))))
+    return arr, J
+
+
+def _coco_column(anns, key, what, width=None):
+    """Field `key` of every dict as a float64 array ([n] or [n,width]); ValueError when missing, malformed or non-finite."""
+    vals = []
+    for i, a in enumerate(anns):
+        if key not in a:
+            raise ValueError('pack_coco_keypoints: %s %d has no %r' % (what, i, key))
+        vals.append(a[key])
+    try:
+        arr = np.asarray(vals, dtype=np.float64).reshape((-1,) if width is None else (-1, width))
+    except (TypeError, ValueError):
+        raise ValueError('pack_coco_keypoints: %r of a %s is not %s' % (key, what, 'a number' if width is None else '%d numbers' % width))
+    if len(arr) != len(anns) or not np.isfinite(arr).all():
+        raise ValueError('pack_coco_keypoints: %r of a %s is not finite' % (key, what))
+    return arr
+
+
+def pack_coco_keypoints(gt_anns, dt_anns, img_ids=None):
+    """A COCO keypoint evaluation set as the flat fp64 / int32 arrays `coco_keypoint_ap` uploads.  gt_anns: COCO annotation
+    dicts (`image_id`, `keypoints` [3 J: x, y, v], `area`, `bbox` [x, y, w, h]; optional `iscrowd`, `num_keypoints`,
+    `category_id`); dt_anns: result dicts (`image_id`, `keypoints` [3 J: x, y, confidence], `score`; optional
+    `category_id`).  What pycocotools' loadRes / _prepare do to them is done here: ignore = iscrowd or num_keypoints == 0
+    (a missing `iscrowd` counts as 0, a missing `num_keypoints` is the number of v > 0; an `ignore` field of the input is
+    not read, as _prepare overwrites it); a detection's area is that of the bounding box of its J (x, y) pairs, in float64.
+    Images are taken in ascending `image_id`; img_ids (default: every id that occurs) names the images to evaluate --
+    annotations and detections of other images are left out, an id without either is legal.
+    -> dict: gt_kpts [G,J,3], gt_area [G], gt_bbox [G,4], gt_flags [G] int32 (bit 0 ignore, bit 1 iscrowd), dt_kpts [D,J,3],
+    dt_score [D], dt_area [D], gt_seg / dt_seg [M+1] int32 (image m owns the rows seg[m] .. seg[m+1), list order kept),
+    image_ids [M], gt_index [G] / dt_index [D] (the position of every packed row in the inputs), num_joints.
+    ValueError for: a keypoint list that is not 3 J long (J from the first list, 1 .. 32), non-finite keypoints, scores,
+    areas or boxes, a missing `area` / `bbox` on an annotation, a missing `score` or `image_id`, more than one distinct
+    `category_id`, more than 128 annotations or 256 detections in an image.  Neither input is modified."""
+    gt_anns, dt_anns = list(gt_anns), list(dt_anns)
+    for what, anns in (('annotation', gt_anns), ('detection', dt_anns)):
+        for i, a in enumerate(anns):
+            if 'image_id' not in a:
+                raise ValueError('pack_coco_keypoints: %s %d has no image_id' % (what, i))
+    cats = {a['category_id'] for a in gt_anns + dt_anns if 'category_id' in a}
+    if len(cats) > 1:
+        raise ValueError('pack_coco_keypoints: one category is supported, the set names %d (%s)'
+                         % (len(cats), ', '.join(sorted(map(repr, cats))[:4])))
+    ids = sorted({a['image_id'] for a in gt_anns + dt_anns}) if img_ids is None else sorted(set(img_ids))
+    number = {v: i for i, v in enumerate(ids)}
+    M = len(ids)
+
+    def group(anns):
+        """-> (positions of the listed images' dicts, grouped by image in list order; seg [M+1])"""
+        img = np.asarray([number.get(a['image_id'], -1) for a in anns], dtype=np.int64)
+        pos = np.flatnonzero(img >= 0)
+        pos = pos[np.argsort(img[pos], kind='stable')]
+        return pos, np.searchsorted(img[pos], np.arange(M + 1)).astype(np.int32)
+
+    gpos, gt_seg = group(gt_anns)
+    dpos, dt_seg = group(dt_anns)
+    gts, dts = [gt_anns[i] for i in gpos], [dt_anns[i] for i in dpos]
+    for seg, cap, what in ((gt_seg, COCO_MAX_GT, 'annotations'), (dt_seg, COCO_MAX_PER_IMAGE, 'detections')):
+        n = np.diff(seg)
+        if M and n.max() > cap:
+            raise ValueError('pack_coco_keypoints: image %r has %d %s, the limit is %d per image'
+                             % (ids[int(n.argmax())], n.max(), what, cap))
+    gt_kpts, J = _coco_rows(gts, 'annotation', None)
+    dt_kpts, J = _coco_rows(dts, 'detection', J)
+    J = J or len(COCO_SIGMAS)
+    gt_kpts, dt_kpts = gt_kpts.reshape(-1, J, 3), dt_kpts.reshape(-1, J, 3)
+    gt_area, gt_bbox = _coco_column(gts, 'area', 'annotation'), _coco_column(gts, 'bbox', 'annotation', 4)
+    dt_score = _coco_column(dts, 'score', 'detection')
+    crowd = np.asarray([bool(g.get('iscrowd', 0)) for g in gts], dtype=bool)
+    labelled = (gt_kpts[:, :, 2] > 0).sum(1)
+    nk = np.asarray([g['num_keypoints'] if 'num_keypoints' in g else int(labelled[i]) for i, g in enumerate(gts)], dtype=np.float64)
+    ignore = crowd | (nk.reshape(-1) == 0)
+    x, y = dt_kpts[:, :, 0], dt_kpts[:, :, 1]
+    dt_area = (x.max(1) - x.min(1)) * (y.max(1) - y.min(1)) if len(dts) else np.zeros(0)
+    return {'gt_kpts': gt_kpts, 'gt_area': gt_area, 'gt_bbox': gt_bbox,
+            'gt_flags': (ignore.astype(np.int32) | (crowd.astype(np.int32) << 1)).astype(np.int32),
+            'dt_kpts': dt_kpts, 'dt_score': dt_score, 'dt_area': np.ascontiguousarray(dt_area, dtype=np.float64),
+            'gt_seg': gt_seg, 'dt_seg': dt_seg, 'image_ids': ids, 'gt_index': gpos, 'dt_index': dpos, 'num_joints': J}
+
+
+def _coco_summarize(precision, recall, iou_thrs):
+    """COCOeval.summarize for keypoints (_summarizeKps): means over the entries > -1, -1 where there is none."""
+    def one(s, thr, a):
+        if a >= s.shape[-1]:
+            return -1.0
+        if thr is not None:
+            s = s[np.where(thr == iou_thrs)[0]]
+        s = s[..., a]
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+    return np.array([one(s, thr, a) for s in (precision, recall)
+                     for thr, a in ((None, 0), (.5, 0), (.75, 0), (None, 1), (None, 2))], dtype=np.float64)
+
+
+def _coco_thresholds(J, max_dets, sigmas, iou_thrs, rec_thrs, area_rngs):
+    who = 'coco_keypoint_ap'
+    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or not 1 <= max_dets <= COCO_MAX_KEPT:
+        raise ValueError('%s: max_dets must be an integer in 1 .. %d, got %r' % (who, COCO_MAX_KEPT, max_dets))
+    if sigmas is None:
+        if J != len(COCO_SIGMAS):
+            raise ValueError('%s: COCO_SIGMAS has %d joints, the set has %d: pass sigmas' % (who, len(COCO_SIGMAS), J))
+        sigmas = COCO_SIGMAS
+    sig = np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    if sig.shape != (J,) or not np.isfinite(sig).all() or not (sig > 0).all():
+        raise ValueError('%s: sigmas must be %d finite positive values' % (who, J))
+    iou = np.ascontiguousarray(COCO_IOU_THRS if iou_thrs is None else iou_thrs, dtype=np.float64).reshape(-1)
+    rec = np.ascontiguousarray(COCO_REC_THRS if rec_thrs is None else rec_thrs, dtype=np.float64).reshape(-1)
+    rng = np.ascontiguousarray(COCO_AREA_RNGS if area_rngs is None else area_rngs, dtype=np.float64)
+    if not 1 <= iou.size <= 32 or not 1 <= rec.size <= 256 or rng.ndim != 2 or rng.shape[1] != 2 or not 1 <= rng.shape[0] <= 8:
+        raise ValueError('%s: 1 .. 32 iou_thrs, 1 .. 256 rec_thrs and 1 .. 8 area_rngs [A,2] are supported' % who)
+    if not (np.isfinite(iou).all() and np.isfinite(rec).all() and np.isfinite(rng).all()):
+        raise ValueError('%s: thresholds must be finite' % who)
+    return int(max_dets), np.ascontiguousarray((sig * 2) ** 2), iou, rec, rng
+
+
+def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None, rec_thrs=None, area_rngs=None, device='cuda'):
+    """COCO keypoint AP / AR of a packed set (`pack_coco_keypoints`) on the device: pycocotools'
+    `COCOeval(gt, dt, 'keypoints')` evaluate + accumulate + summarize for one category (csrc/coco_ap.hip; include/fami.h
+    restates the definition in full).  Per image the detections are ranked by score (equal scores keep list order), the
+    first max_dets kept and matched greedily to the annotations by OKS, once per area range and OKS threshold, with
+    pycocotools' crowd / ignore rules; per (range, threshold) one precision / recall curve over the set, read at the recall
+    thresholds.  All arithmetic is fp64.  Defaults: COCO_SIGMAS (J = 17; any other J needs its own sigmas), COCO_IOU_THRS
+    (.5 : .05 : .95), COCO_REC_THRS (0 : .01 : 1), COCO_AREA_RNGS (all, medium, large), max_dets 20 -- the threshold arrays
+    are numpy's, handed down as they are.
+    -> dict: 'stats' float64 [10] (AP, AP50, AP75, AP_M, AP_L, AR, AR50, AR75, AR_M, AR_L: COCOeval.stats; -1 where
+    nothing counts, e.g. no annotation of that size, a threshold .5 / .75 that iou_thrs does not hold, or fewer than three
+    area ranges), 'names', 'precision' [T,R,A], 'recall' [T,A] (-1 where a range holds no annotation that counts),
+    'num_kept' (detections after the cut).  pycocotools' `scores` array is not produced, and "matched" is a flag, not the
+    annotation's id (pycocotools never counts a match to an annotation with id 0).
+    One upload, the match launch, one stable `torch.sort` plus gather, the curve launch, one download.  An empty set (no
+    image, or neither annotations nor detections) returns all -1 without device work.  ValueError before any device work
+    for max_dets outside 1 .. 64, sigmas that do not fit, non-finite or too many thresholds, an image over a cap, more
+    than 229376 kept detections in the set."""
+    J = int(packed['num_joints'])
+    K, var, iou, rec, rng = _coco_thresholds(J, max_dets, sigmas, iou_thrs, rec_thrs, area_rngs)
+    T, R, A = iou.size, rec.size, rng.shape[0]
+    gt_seg, dt_seg = np.asarray(packed['gt_seg'], dtype=np.int32), np.asarray(packed['dt_seg'], dtype=np.int32)
+    M, G, D = len(gt_seg) - 1, len(packed['gt_flags']), len(packed['dt_score'])
+    if M <= 0 or G + D == 0:
+        precision, recall = -np.ones((T, R, A)), -np.ones((T, A))
+        return {'stats': _coco_summarize(precision, recall, iou), 'names': list(COCO_STAT_NAMES), 'precision': precision,
+                'recall': recall, 'num_kept': 0}
+    n_gt, n_dt = np.diff(gt_seg), np.diff(dt_seg)
+    if len(dt_seg) != M + 1 or gt_seg[0] != 0 or dt_seg[0] != 0 or gt_seg[-1] != G or dt_seg[-1] != D or n_gt.min() < 0 or n_dt.min() < 0:
+        raise ValueError('coco_keypoint_ap: gt_seg / dt_seg must ascend from 0 to the %d annotations / %d detections' % (G, D))
+    if n_gt.max() > COCO_MAX_GT or n_dt.max() > COCO_MAX_PER_IMAGE:
+        m = int(np.argmax((n_gt > COCO_MAX_GT) | (n_dt > COCO_MAX_PER_IMAGE)))
+        raise ValueError('coco_keypoint_ap: image %d has %d annotations and %d detections, the limits are %d and %d'
+                         % (m, n_gt[m], n_dt[m], COCO_MAX_GT, COCO_MAX_PER_IMAGE))
+    kept = np.minimum(n_dt, K)
+    N = int(kept.sum())
+    if N > COCO_MAX_SET:
+        raise ValueError('coco_keypoint_ap: %d detections after the cut, the limit is %d per set' % (N, COCO_MAX_SET))
+    if M * K * A * T > 0x7fffffff or max(G, D) * J * 3 > 0x7fffffff:
+        raise ValueError('coco_keypoint_ap: the set is too large for 32-bit indices')
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('coco_keypoint_ap runs on the HIP path only (device is %s)' % dev)
+    # the kept slots of every image, as the match launch lays them out: m * K + k for k < min(detections of m, K)
+    first = np.concatenate([[0], np.cumsum(kept)[:-1]])
+    slots = (np.repeat(np.arange(M, dtype=np.int64) * K - first, kept) + np.arange(N, dtype=np.int64)).astype(np.int32)
+    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), then the int inputs -- one upload
+    f64 = [np.ascontiguousarray(packed[k], dtype=np.float64).reshape(-1)
+           for k in ('gt_kpts', 'gt_area', 'gt_bbox', 'dt_kpts', 'dt_score', 'dt_area')]
+    i32 = [np.ascontiguousarray(packed['gt_flags'], dtype=np.int32).reshape(-1), gt_seg, dt_seg, slots]
+    if [a.size for a in f64] != [G * J * 3, G, G * 4, D * J * 3, D, D]:
+        raise ValueError('coco_keypoint_ap: the packed arrays do not fit %d annotations and %d detections of %d joints' % (G, D, J))
+    if not all(np.isfinite(a).all() for a in f64):
+        raise ValueError('coco_keypoint_ap: the packed arrays must be finite')
+    sizes = [2 * a.size for a in f64] + [a.size for a in i32]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    buf = np.zeros(int(off[-1]) + 2, dtype=np.int32)
+    for a, o in zip(f64, off):
+        buf[o:o + 2 * a.size] = a.view(np.int32)
+    for a, o in zip(i32, off[6:]):
+        buf[o:o + a.size] = a
+    d = torch.from_numpy(buf).to(dev)
+    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]]
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        out_score = torch.empty(M * K, dtype=torch.float64, device=dev)
+        out_row = torch.empty(M * K, dtype=torch.int32, device=dev)
+        out_flags = torch.empty(M * K, A * T, dtype=torch.uint8, device=dev)
+        npig = torch.empty(M * A, dtype=torch.int32, device=dev)
+        res = torch.empty(T * R * A + T * A + 1, dtype=torch.float64, device=dev)
+        lib().call('fami_coco_kpt_match_f64', p[0], p[1], p[2], p[6], p[3], p[4], p[5], p[7], p[8], var.ctypes.data,
+                   iou.ctypes.data, rng.ctypes.data, G, D, M, J, T, A, K, out_score.data_ptr(), out_row.data_ptr(),
+                   out_flags.data_ptr(), npig.data_ptr(), s)
+        # plumbing between the two kernels: the kept detections of the whole set by descending score, images in order
+        slot = d[int(off[9]):int(off[9]) + N].long()
+        order = torch.sort(out_score[slot], descending=True, stable=True).indices
+        flags = out_flags[slot[order]].t().contiguous()
+        lib().call('fami_coco_kpt_curve_f64', flags.data_ptr() if N else None, npig.data_ptr(), rec.ctypes.data, N, M, T, A, R,
+                   res.data_ptr(), res.data_ptr() + 8 * T * R * A, s)
+        res[-1:] = npig.min().to(torch.float64)                   # the refusal marker rides in the one download
+    out = res.cpu().numpy()
+    if out[-1] < 0:
+        raise RuntimeError('coco_keypoint_ap: the kernel refused an image')
+    precision, recall = out[:T * R * A].reshape(T, R, A).copy(), out[T * R * A:T * R * A + T * A].reshape(T, A).copy()
+    return {'stats': _coco_summarize(precision, recall, iou), 'names': list(COCO_STAT_NAMES), 'precision': precision,
+            'recall': recall, 'num_kept': N}
+
+
+def load_coco_keypoints(gt_json, dt_json):
+    """-> (gt_anns, dt_anns, img_ids), the arguments of `pack_coco_keypoints`: the `annotations` of an instances-style
+    ground-truth file (person_keypoints_*.json) with the ids of its `images` (None when the file lists none: then every
+    id that occurs is evaluated), and the list a results file holds.  As COCO.loadRes, ValueError for a results file that
+    is not a list or that names an image the ground truth does not list."""
+    with open(gt_json) as f:
+        gt = json.load(f)
+    with open(dt_json) as f:
+        dt = json.load(f)
+    if not isinstance(gt, dict) or 'annotations' not in gt:
+        raise ValueError('load_coco_keypoints: %s has no `annotations`' % gt_json)
+    if not isinstance(dt, list):
+        raise ValueError('load_coco_keypoints: %s is not a list of results' % dt_json)
+    img_ids = [im['id'] for im in gt['images']] if 'images' in gt else None
+    if img_ids is not None:
+        extra = {r.get('image_id') for r in dt} - set(img_ids)
+        if extra:
+            raise ValueError('load_coco_keypoints: results name %d images the ground truth does not list (e.g. %r)'
+                             % (len(extra), sorted(extra, key=repr)[0]))
+    return gt['annotations'], dt, img_ids
+
+
+def evaluate_coco_keypoints(gt_json, dt_json, device='cuda', **kw):
+    """-> the 10 values of `COCOeval(cocoGt, cocoGt.loadRes(dt_json), 'keypoints')` after evaluate / accumulate /
+    summarize (`.stats`: AP, AP50, AP75, AP_M, AP_L, AR, AR50, AR75, AR_M, AR_L), in-process; keywords as for
+    `coco_keypoint_ap`."""
+    return coco_keypoint_ap(pack_coco_keypoints(*load_coco_keypoints(gt_json, dt_json)), device=device, **kw)['stats']
+
+
+def coco_keypoint_results(preds, boxes, image_ids, keep=None, category_id=1):
+    """The result dicts HRNet's COCO evaluation writes, for `pack_coco_keypoints` or `json.dump`: preds [N,J,3] (x, y,
+    confidence in image pixels) and boxes [N,6] (column 5 the score: rescored by `pose_nms` where that ran) as
+    `EvalAccumulator` holds them, image_ids [N] the COCO image id of every row.  keep: the rows to write, in that order --
+    the keep map of `pose_nms` (its lists are flattened in its order) or a flat list of row indices; default every row.
+    -> [{'image_id', 'category_id', 'keypoints': [x, y, confidence] x J, 'score'}]."""
+    preds, boxes = np.asarray(preds, dtype=np.float64), np.asarray(boxes, dtype=np.float64)
+    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
+        raise ValueError('coco_keypoint_results expects preds [N,J,3] and boxes [N,6], got %s and %s' % (preds.shape, boxes.shape))
+    image_ids = list(image_ids)
+    if len(image_ids) != len(preds):
+        raise ValueError('coco_keypoint_results: %d rows, %d image_ids' % (len(preds), len(image_ids)))
+    if keep is None:
+        rows = range(len(preds))
+    else:
+        rows = [int(i) for v in keep.values() for i in v] if hasattr(keep, 'values') else [int(i) for i in keep]
+        if rows and not (0 <= min(rows) and max(rows) < len(preds)):
+            raise ValueError('coco_keypoint_results: keep names a row outside [0, %d)' % len(preds))
+    ids = [i.item() if isinstance(i, np.generic) else i for i in image_ids]
+    return [{'image_id': ids[i], 'category_id': category_id, 'keypoints': preds[i].reshape(-1).tolist(),
+             'score': float(boxes[i, 5])} for i in rows]

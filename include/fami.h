@@ -716,6 +716,68 @@ int fami_posetrack_mot_f64(const double* pr_xys, const int* pr_has, const double
 int fami_posetrack_mot_final_f64(const int* counts, const double* sumd, const int* status, int S, int* totals,
                                  double* sumd_tot, double* table, fami_stream_t stream);
 
+/* COCO keypoint AP / AR: COCOeval(gt, dt, 'keypoints') of pycocotools' cocoeval.py (computeOks, evaluateImg, accumulate),
+ * the number the HRNet evaluation protocol reports, for ONE category (csrc/coco_ap.hip).  pycocotools is no part of the
+ * reference tree, so the definition is restated here in full and THIS TEXT IS THE CONTRACT.  Pointers are DEVICE memory
+ * unless marked HOST; fp64 arrays 8-byte, int arrays 4-byte aligned.  All arithmetic is fp64 on fp64 inputs.
+ * fami_coco_kpt_match_f64: M images; image m owns the annotations gt_seg[m] .. gt_seg[m+1) (at most 128) and the
+ *   detections dt_seg[m] .. dt_seg[m+1) (at most 256); either may be empty.  gt_kpts [G,J,3] (x, y, v), gt_area [G],
+ *   gt_bbox [G,4] (bx, by, bw, bh), gt_flags [G] (bit 0: ignore = iscrowd or num_keypoints == 0, bit 1: iscrowd);
+ *   dt_kpts [D,J,3] (x, y, confidence: not read), dt_score [D] (finite), dt_area [D] (the area of the bounding box of the
+ *   J (x, y) pairs, loadRes's rule; the caller computes it).  HOST: vars [J] = (2 sigma_j)^2, iou_thrs [T] (T in
+ *   1 .. 32), area_rng [A,2] = (lo, hi) per range (A in 1 .. 8) -- built with numpy by the caller and never recomputed
+ *   (np.linspace(.5, .95, 10)[8] is 0.8999999999999999); they travel to the kernel as launch arguments.  Per image:
+ *     1. the detections are ordered by descending score, equal scores by list position (a stable sort), and the first
+ *        max_dets (1 .. 64) are kept.
+ *     2. for every annotation g and kept detection d, with k1 = #(vg > 0):
+ *          k1 > 0:  dx = xd - xg, dy = yd - yg;
+ *          k1 == 0: with x0 = bx - bw, x1 = bx + 2 bw, y0 = by - bh, y1 = by + 2 bh:
+ *                   dx = max(0, x0 - xd) + max(0, xd - x1), dy = max(0, y0 - yd) + max(0, yd - y1);
+ *          e_j = (dx^2 + dy^2) / vars_j / (area_g + 2^-52) / 2;
+ *          OKS(d, g) = the mean of exp(-e_j) over the joints with vg > 0, over ALL joints when k1 == 0;
+ *        one rounding per operation, the sum in ascending j.  (Not the OKS of fami_pose_nms_f32 / fami_pose_track_f32,
+ *        which averages two areas and reads fp32.)
+ *     3. per area range a: gIg(g) = ignore or area_g < lo or area_g > hi -- strict comparisons, an area of exactly lo or hi
+ *        is inside, so one of exactly 32^2 or 96^2 lies in two of COCO's ranges; the annotations are ordered with the
+ *        non-ignored ones first, list order otherwise (a stable argsort of gIg).
+ *     4. per (a, t) and for each kept detection in score order: best = min(iou_thrs[t], 1 - 1e-10), m = none; walk the
+ *        annotations in the order of 3: skip one already matched at this (a, t) unless it is a crowd annotation; STOP if
+ *        m is set, m is not ignored and this one is; skip it if OKS < best; else best = OKS, m = this (an exact tie goes
+ *        to the later annotation).  If m is set: the detection is matched, dIg = gIg(m), m is matched.
+ *     5. an unmatched detection whose own area is < lo or > hi gets dIg = 1.
+ *   out_score [M,max_dets] and out_row [M,max_dets]: the score and the row (in dt_kpts) of kept slot k of image m, 0 and
+ *   -1 for a slot behind the image's last detection; out_flags [M,max_dets,A*T] bytes, index a * T + t: bit 0 matched,
+ *   bit 1 dIg (0 for an empty slot); npig [M,A] = the annotations of the image with gIg = 0.  An image with neither
+ *   annotations nor detections writes empty slots and npig 0; one with detections only, its detections unmatched.
+ *   Deliberate differences: pycocotools decides "matched" by dtm != 0 with dtm the matched annotation's id, so an
+ *   annotation with id 0 never counts there; here it is a flag.  The `scores` array of accumulate is not produced.
+ *   One launch, one workgroup per image, no atomics, no workspace: bitwise reproducible.  Returns -1 before any launch for
+ *   a null or misaligned pointer (an array of extent 0 may be null), G or D < 0 or G * J * 3 or D * J * 3 >= 2^31, M < 1 or
+ *   M * max_dets * A * T >= 2^31, J outside 1 .. 32, T outside 1 .. 32, A outside 1 .. 8, max_dets outside 1 .. 64, a NaN
+ *   in vars, iou_thrs or area_rng.  The segment tables live in device memory and are not checked here
+ *   (fami_pose_amd.evaluate.pack_coco_keypoints does): an image over a cap, or with a segment that is no sub-range of
+ *   its array, gets npig[m,:] = -1 and nothing else written; other images are not affected.
+ * fami_coco_kpt_curve_f64: flags [A*T,N] bytes, row a * T + t the bytes of ALL kept detections of the set in descending
+ *   score order (a stable sort over the images in order: the caller's); npig_img [M,A] as written above; HOST: rec_thrs
+ *   [R] (R in 1 .. 256).  Per (a, t), with npig = sum_m npig_img[m,a]:
+ *     npig == 0: precision[t,:,a] = recall[t,a] = -1.  Otherwise tp_k / fp_k = the number of detections among the first
+ *     k + 1 with matched & !dIg / !matched & !dIg;  rc_k = tp_k / npig;  pr_k = tp_k / (fp_k + tp_k + 2^-52);
+ *     recall[t,a] = rc_last (0 when N = 0);  pr_k <- max(pr_k, pr_(k+1), ...);  for each r: k = the first index with
+ *     rc_k >= rec_thrs[r] (searchsorted, side left) and precision[t,r,a] = pr_k, 0 when there is none.
+ *   precision [T,R,A], recall [T,A].  Every value is int -> double, one add, one add of 2^-52 and one divide, or a maximum
+ *   of such values: the result equals the numpy expressions bit for bit.  N is at most 229376: two bits per detection
+ *   in 56 KiB of LDS.  Returns -1 before any launch for a null or misaligned pointer (flags may be null with N = 0), N
+ *   outside 0 .. 229376, M outside 1 .. (2^31 - 2) / 8, T, A or R outside their ranges, a NaN in rec_thrs.
+ * The ten summary numbers (AP, AP50, AP75, AP-medium, AP-large and the five ARs) are means over the entries > -1 of
+ * slices of these two arrays and are taken on the host (fami_pose_amd.evaluate.coco_keypoint_ap), as pycocotools does. */
+int fami_coco_kpt_match_f64(const double* gt_kpts, const double* gt_area, const double* gt_bbox, const int* gt_flags,
+                            const double* dt_kpts, const double* dt_score, const double* dt_area, const int* gt_seg,
+                            const int* dt_seg, const double* vars, const double* iou_thrs, const double* area_rng, int G,
+                            int D, int M, int J, int T, int A, int max_dets, double* out_score, int* out_row,
+                            unsigned char* out_flags, int* npig, fami_stream_t stream);
+int fami_coco_kpt_curve_f64(const unsigned char* flags, const int* npig_img, const double* rec_thrs, int N, int M, int T,
+                            int A, int R, double* precision, double* recall, fami_stream_t stream);
+
 /* ---- input pipeline on the device -------------------------------------------------------------
  * cv2.warpAffine(frame, trans, (Wd, Hd), flags=INTER_LINEAR) on the F 8-bit HWC frames of one clip (one transform
  * for key + supporting frames, datasets/zoo/posetrack/PoseTrack_Alignment.py:421-427; flip = source mirrored in x
