@@ -22,6 +22,7 @@ from .evaluate import (COCO_SIGMAS, pose_nms, pose_nms_options, pose_track, pack
                        evaluate_posetrack_ap, posetrack_mota, evaluate_posetrack_mota, evaluate_posetrack,
                        pack_coco_keypoints, coco_keypoint_ap, load_coco_keypoints, evaluate_coco_keypoints,
                        coco_keypoint_results)
+from .data import draw_degradation, check_degradation, DEGRADE_DEFAULTS
 
 __all__ = ['CfgNode', 'default_cfg', 'MODEL_REGISTRY', 'CORE_FUNCTION_REGISTRY', 'DATASET_REGISTRY', 'TRAIN_PHASE',
            'VAL_PHASE', 'TEST_PHASE', 'build_model', 'get_model_hyperparameter', 'Alignment_V15', 'HRNet',
@@ -29,4 +30,5 @@ __all__ = ['CfgNode', 'default_cfg', 'MODEL_REGISTRY', 'CORE_FUNCTION_REGISTRY',
            'pack_posetrack_frames',
            'load_posetrack_dirs', 'posetrack_ap', 'evaluate_posetrack_ap', 'posetrack_mota',
            'evaluate_posetrack_mota', 'evaluate_posetrack', 'pack_coco_keypoints', 'coco_keypoint_ap',
-           'load_coco_keypoints', 'evaluate_coco_keypoints', 'coco_keypoint_results']
+           'load_coco_keypoints', 'evaluate_coco_keypoints', 'coco_keypoint_results', 'draw_degradation',
+           'check_degradation', 'DEGRADE_DEFAULTS']

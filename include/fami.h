@@ -815,6 +815,59 @@ long fami_warp_batch_table_bytes(int B, int F);
 int fami_warp_normalize_batch_u8(const void* table, float* key, float* sup, int B, int F, int Hd, int Wd, int swap_rb,
                                  float mean0, float mean1, float mean2, float std0, float std1, float std2,
                                  fami_stream_t stream);
+/* The batched crop with DEGRADATION of the 8-bit crop: line blur, colour, occluders.  The reference has nothing of the
+ * kind (its datasets/transforms/data_augment.py is a plotting helper); the rule below is this project's and this text is
+ * its contract.  Same table, grid and outputs as fami_warp_normalize_batch_u8, plus
+ * degrade: DEVICE memory the caller owns, fami_degrade_table_bytes(B, F) bytes (-1 for B <= 0 or F <= 0), 8-byte
+ *   aligned: B*F fami_degrade_frame_t records, record [b*F + f] for frame f of clip b (key frame at f = 0).
+ * `flags` says which stages run on the frame; a stage whose flag is off is SKIPPED, not run with neutral parameters.
+ * With flags == 0 in every record the output is fami_warp_normalize_batch_u8's, bit for bit.  Per output pixel (x, y),
+ * 0 <= x < Wd, 0 <= y < Hd, of frame f, in this order:
+ *  1. Line blur (FAMI_DEGRADE_BLUR; taps odd, 1..15; step_x, step_y integers in 1/1024 source pixel).  With
+ *     (PX, PY) = (X0 + adelta, Y0 + bdelta), the un-shifted fixed-point position of the plain crop (csrc/preproc.hip),
+ *     tap k = -(taps-1)/2 .. (taps-1)/2 samples at ((PX + k*step_x) >> 5, (PY + k*step_y) >> 5) exactly as the plain crop
+ *     samples at (PX >> 5, PY >> 5): integer bilinear weights summing to 2^15, taps outside the image read 0, columns
+ *     mirrored under the clip's `flip`; each tap gives one 8-bit value per channel, (acc + 2^14) >> 15.  The result is
+ *     u_c = (2 * sum_c + taps) / (2 * taps) in integer arithmetic (the mean, rounded half up).  taps = 1 with zero steps is
+ *     the plain sample.  Flag off: u_c is the plain sample.  The caller guarantees |k * step| < 2^24 for every tap.
+ *  2. Colour (FAMI_DEGRADE_COLOUR; alpha, delta, sat fp32).  Every fp32 operation is rounded on its own, no contraction.
+ *     Channels are the OUTPUT's (c = 0, 1, 2 are R, G, B after swap_rb):
+ *       t_c = u_c * alpha + delta;   g = ((0.299f * t_0) + (0.587f * t_1)) + (0.114f * t_2);
+ *       t_c = g + sat * (t_c - g);   t_c = min(max(t_c, 0), 255).
+ *     The value stays a float; it is not rounded back to a byte.  Flag off: t_c = (float)u_c.
+ *  3. Occluders (FAMI_DEGRADE_OCCLUDE; n_rect <= 4 rectangles in crop pixels, half-open: x0 <= x < x1, y0 <= y < y1;
+ *     they may reach outside the crop or be empty).  A covered pixel takes a fill value IN PLACE of t_c:
+ *       mode 0: the constant byte fill[c];
+ *       mode 1: noise, lowbias32(((c * Hd + y) * Wd + x) ^ seed) >> 24 with the record's seed, everything in wrapping
+ *               32-bit unsigned arithmetic; lowbias32(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b;
+ *               v ^= v >> 16.
+ *     Rectangles apply in order: the later one wins an overlap.  Nothing else about overlaps is defined.
+ *  4. Normalisation: ((t_c / 255) - mean[c]) / std[c], as in the plain crop.
+ * Checked here (-1, no launch): what fami_warp_normalize_batch_u8 checks, a null or misaligned degrade.  The records
+ * live in device memory and are NOT checked: the caller guarantees odd taps in 1..15, the step bound, n_rect in 0..4 and
+ * finite alpha, delta, sat (fami_pose_amd.data.ClipBatcher does; the kernel clamps taps and n_rect into range so that a
+ * bad record cannot divide by zero or read past the record).  No atomics, no workspace: results are bitwise reproducible. */
+#define FAMI_DEGRADE_BLUR 1
+#define FAMI_DEGRADE_COLOUR 2
+#define FAMI_DEGRADE_OCCLUDE 4
+typedef struct fami_degrade_rect_t {
+  int x0, y0, x1, y1;    /* crop pixels, half-open */
+  unsigned char fill[3]; /* mode 0: the byte of output channel c */
+  unsigned char mode;    /* 0 constant, 1 noise */
+} fami_degrade_rect_t;
+typedef struct fami_degrade_frame_t {
+  unsigned int flags; /* FAMI_DEGRADE_* */
+  int taps, step_x, step_y;
+  float alpha, delta, sat;
+  unsigned int seed;
+  int n_rect;
+  int reserved[3]; /* 0 (pads the record to 128 bytes) */
+  fami_degrade_rect_t rect[4];
+} fami_degrade_frame_t;
+long fami_degrade_table_bytes(int B, int F);
+int fami_warp_degrade_batch_u8(const void* table, const void* degrade, float* key, float* sup, int B, int F, int Hd,
+                               int Wd, int swap_rb, float mean0, float mean1, float mean2, float std0, float std1,
+                               float std2, fami_stream_t stream);
 
 
 /* ======================================================================================================
