@@ -46,7 +46,9 @@ def default_cfg(width=48, num_joints=17, freeze_backbone=False, name='Alignment_
                   # augmentation draws (data.draw_augmentation), Base_PoseTrack17.yaml:99-101
                   'FLIP': True, 'NUM_JOINTS_HALF_BODY': 8, 'PROB_HALF_BODY': 0.3},
         # INTEGRAL_L1 (Trainer.from_cfg -> integral_l1_weight): the reference's defaults, mppe_config.py:217-219
-        'LOSS': {'HEATMAP_MSE': {'USE': True, 'WEIGHT': 1.0}, 'INTEGRAL_L1': {'USE': False, 'WEIGHT': 1.0}},
+        # STRUCTURE_COSINE (Trainer.from_cfg -> structure_cos_weight): the reference's defaults, mppe_config.py:225-227
+        'LOSS': {'HEATMAP_MSE': {'USE': True, 'WEIGHT': 1.0}, 'INTEGRAL_L1': {'USE': False, 'WEIGHT': 1.0},
+                 'STRUCTURE_COSINE': {'USE': False, 'WEIGHT': 1.0}},
         # flip testing (evaluate.flip_test_options); the reference's defaults, posetimation/config/mppe_config.py:322-346
         # rescoring and OKS-NMS (evaluate.pose_nms_options); the reference's defaults, mppe_config.py:326-330, 343-347
         'VAL': {'FLIP_VAL': False, 'SHIFT_HEATMAP': False, 'IN_VIS_THRE': 0.0, 'OKS_THRE': 0.5, 'SOFT_NMS': False},

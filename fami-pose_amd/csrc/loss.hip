@@ -595,6 +595,102 @@ static bool softargmax_args_ok(long R, int H, int W, float beta) {
   return R > 0 && R <= 0x7fffffffL && H > 0 && W > 0 && (long)H * W <= 0x7fffffffL && beta > 0.f && beta <= 3.4028234e38f;
 }
 
+// ---- structure (limb-direction cosine) term: rows and coordinate gradient (definition: include/fami.h) ----
+#define STRUCT_MAX 64      // limbs and joints of a sample: the backward holds both in the LDS of one wavefront
+// One limb a -> b of one sample (c, t, w point at the sample's joint 0; w may be null) in fp64 on the fp32 operands, every
+// operation rounded on its own.  -> valid; cosv, and with GRAD (dx, dy) = dcos/du; all 0 where not valid.
+// An index outside 0..J-1 or a == b (the host refuses such a table before upload) reads nothing and is not valid.
+template <bool GRAD>
+__device__ __forceinline__ bool limb_cos(const float* __restrict__ c, const float* __restrict__ t,
+                                         const float* __restrict__ w, int a, int b, int J, double min_len2, double eps,
+                                         double& cosv, double& dx, double& dy) {
+#pragma clang fp contract(off)
+  cosv = dx = dy = 0.0;
+  if ((unsigned)a >= (unsigned)J || (unsigned)b >= (unsigned)J || a == b) return false;
+  if (w && !(w[a] > 0.f && w[b] > 0.f)) return false;
+  const double tx = (double)t[b * 2 + 0] - (double)t[a * 2 + 0], ty = (double)t[b * 2 + 1] - (double)t[a * 2 + 1];
+  const double tt = tx * tx + ty * ty;
+  if (!(tt > min_len2)) return false;
+  const double ux = (double)c[b * 2 + 0] - (double)c[a * 2 + 0], uy = (double)c[b * 2 + 1] - (double)c[a * 2 + 1];
+  const double uu = ux * ux + uy * uy, ut = ux * tx + uy * ty;
+  const double nu = sqrt(uu), nt = sqrt(tt);
+  const bool clamp = nu <= eps;           // (a NaN length is not clamped: it reaches loss and gradient)
+  const double mu = clamp ? eps : nu, mt = nt <= eps ? eps : nt;
+  cosv = ut / (mu * mt);
+  if constexpr (GRAD) {
+    const double nn = mu * mt;
+    dx = tx / nn;
+    dy = ty / nn;
+    if (!clamp) {
+      const double n2 = nu * nu;
+      dx = dx - (cosv * ux) / n2;
+      dy = dy - (cosv * uy) / n2;
+    }
+  }
+  return true;
+}
+// rowval[s,p] = valid ? 1 - cos : 0, rounded once
+__global__ void structure_cos_rows_kernel(const float* __restrict__ coords, const float* __restrict__ txy,
+                                          const float* __restrict__ w, const int* __restrict__ pairs,
+                                          float* __restrict__ rowval, int n, int J, int P, double min_len2, double eps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = i / P, p = i - s * P;
+  const long o = (long)s * J;
+  double cosv, dx, dy;
+  const bool valid = limb_cos<false>(coords + o * 2, txy + o * 2, w ? w + o : nullptr, pairs[p * 2], pairs[p * 2 + 1], J,
+                                     min_len2, eps, cosv, dx, dy);
+  rowval[i] = valid ? (float)(1.0 - cosv) : 0.f;
+}
+// One wavefront per sample.  Lanes over the limbs put dcos/du and the two joints (-1: not valid) into LDS; lanes over the
+// joints then walk the limb list in order: gcoords[s,j] = g sum_p -dcos/du_p (+1 at b_p, -1 at a_p) in fp64, rounded once;
+// a joint on no valid limb gets 0.  g = scale * (gdev ? gdev[0] : 1), the fp32 product of wmse_bwd_kernel.
+__global__ __launch_bounds__(STRUCT_MAX) void structure_cos_bwd_kernel(const float* __restrict__ coords,
+                                                                       const float* __restrict__ txy,
+                                                                       const float* __restrict__ w,
+                                                                       const int* __restrict__ pairs,
+                                                                       float* __restrict__ gcoords, int J, int P,
+                                                                       double min_len2, double eps, float scale,
+                                                                       const float* gdev) {
+  __shared__ double sdx[STRUCT_MAX], sdy[STRUCT_MAX];
+  __shared__ int sa[STRUCT_MAX], sb[STRUCT_MAX];
+  const long o = (long)blockIdx.x * J;
+  const int t = threadIdx.x;
+  if (t < P) {
+    const int a = pairs[t * 2], b = pairs[t * 2 + 1];
+    double cosv, dx, dy;
+    const bool valid = limb_cos<true>(coords + o * 2, txy + o * 2, w ? w + o : nullptr, a, b, J, min_len2, eps, cosv, dx, dy);
+    sdx[t] = dx;
+    sdy[t] = dy;
+    sa[t] = valid ? a : -1;
+    sb[t] = valid ? b : -1;
+  }
+  __syncthreads();
+  if (t < J) {
+    const double g = (double)(gdev ? gdev[0] * scale : scale);
+    double gx = 0.0, gy = 0.0;
+    bool any = false;
+    for (int p = 0; p < P; ++p) {
+      if (sb[p] == t) {
+        gx -= sdx[p];
+        gy -= sdy[p];
+        any = true;
+      } else if (sa[p] == t) {
+        gx += sdx[p];
+        gy += sdy[p];
+        any = true;
+      }
+    }
+    gcoords[(o + t) * 2 + 0] = any ? (float)(g * gx) : 0.f;
+    gcoords[(o + t) * 2 + 1] = any ? (float)(g * gy) : 0.f;
+  }
+}
+// sizes within the caps (a row index that fits an int), min_len finite and >= 0, eps finite and > 0 (NaN fails the comparisons)
+static bool structure_args_ok(int B, int J, int P, float min_len, float eps) {
+  return B > 0 && B <= 0x7fffffff / STRUCT_MAX && J >= 2 && J <= STRUCT_MAX && P >= 1 && P <= STRUCT_MAX && min_len >= 0.f &&
+         min_len <= 3.4028234e38f && eps > 0.f && eps <= 3.4028234e38f;
+}
+
 #define OHKM_MAX_J 15360      // 60 KiB of the 64 KiB a workgroup may ask for without an opt-in
 
 extern "C" {
@@ -750,6 +846,31 @@ int fami_integral_l1_bwd_f32(const float* hm, const float* coords, const float* 
                "bad argument (beta finite and > 0, sizes positive)");
   launch_softargmax_bwd(R, s, hm, coords, stats, nullptr, target_xy, w, dhm, H, W, beta, scale, gdev, accumulate);
   FAMI_CHECK_LAUNCH("fami_integral_l1_bwd_f32");
+  return FAMI_OK;
+}
+// ---- structure (limb-direction cosine) term ----
+// loss[0] = scale * sum_sp (valid ? 1 - cos(c[b_p] - c[a_p], t[b_p] - t[a_p]) : 0); w [B*J] or null; pairs [P,2] int32 on the
+// device; ws >= B*P floats, the row values
+int fami_structure_cos_fwd_f32(const float* coords, const float* target_xy, const float* w, const int* pairs, float* loss,
+                               int B, int J, int P, float min_len, float eps, double scale, float* ws, hipStream_t s) {
+  FAMI_REQUIRE(coords && target_xy && pairs && loss && ws && structure_args_ok(B, J, P, min_len, eps),
+               "fami_structure_cos_fwd_f32", "bad argument (1 <= P <= 64, 2 <= J <= 64, min_len finite and >= 0, eps finite and > 0)");
+  hipLaunchKernelGGL(structure_cos_rows_kernel, dim3(fami_cdiv((long)B * P, 256)), dim3(256), 0, s, coords, target_xy, w,
+                     pairs, ws, B * P, J, P, (double)min_len * (double)min_len, (double)eps);
+  FAMI_CHECK_LAUNCH("fami_structure_cos_fwd_f32/rows");
+  hipLaunchKernelGGL(scalar_sum_kernel, dim3(1), dim3(256), 0, s, ws, B * P, scale, loss);
+  FAMI_CHECK_LAUNCH("fami_structure_cos_fwd_f32/sum");
+  return FAMI_OK;
+}
+// gcoords [B*J,2] = (gdev ? gdev[0] : 1) * scale * d/dcoords of the sum above (every entry written)
+int fami_structure_cos_bwd_f32(const float* coords, const float* target_xy, const float* w, const int* pairs,
+                               float* gcoords, int B, int J, int P, float min_len, float eps, float scale,
+                               const float* gdev, hipStream_t s) {
+  FAMI_REQUIRE(coords && target_xy && pairs && gcoords && structure_args_ok(B, J, P, min_len, eps),
+               "fami_structure_cos_bwd_f32", "bad argument (1 <= P <= 64, 2 <= J <= 64, min_len finite and >= 0, eps finite and > 0)");
+  hipLaunchKernelGGL(structure_cos_bwd_kernel, dim3(B), dim3(STRUCT_MAX), 0, s, coords, target_xy, w, pairs, gcoords, J, P,
+                     (double)min_len * (double)min_len, (double)eps, scale, gdev);
+  FAMI_CHECK_LAUNCH("fami_structure_cos_bwd_f32");
   return FAMI_OK;
 }
 // hm [B,J,H,W], center/scale [B,2] -> preds [B,J,2] image coordinates of the soft-argmax, maxvals [B,J]: one launch

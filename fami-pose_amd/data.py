@@ -20,6 +20,11 @@ MEAN = (0.485, 0.456, 0.406)      # datasets/transforms/build.py:13-14 (RGB)
 STD = (0.229, 0.224, 0.225)
 FLIP_PAIRS = ((3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))   # PoseTrack_Alignment.py:40
 JOINTS_WEIGHT = (1., 1., 1., 1., 1., 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5)    # PoseTrack_Alignment.py:41-43
+# The limbs (a, b) of the 17-joint PoseTrack order for loss.StructureCosineSimilarity.  This project's table (the reference's
+# lives in a module it did not ship): head chain 2-0-1, neck to shoulders, the two arms, trunk, the two legs.  The ears (3, 4),
+# which PoseTrack does not annotate, are on no limb; as undirected limbs the set is closed under FLIP_PAIRS.
+LIMB_PAIRS = ((2, 0), (0, 1), (1, 5), (1, 6), (5, 6), (5, 7), (7, 9), (6, 8), (8, 10), (5, 11), (6, 12), (11, 12), (11, 13),
+              (13, 15), (12, 14), (14, 16))
 UPPER_BODY_IDS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10)                            # PoseTrack_Alignment.py:44
 PIXEL_STD = 200                                                                # datasets/zoo/base.py:27
 

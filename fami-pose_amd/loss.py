@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import lib
+from .data import LIMB_PAIRS
 
 
 def _p(t):
@@ -376,6 +377,137 @@ def integral_get_final_preds(batch_heatmaps, center, scale, beta=20.0):
     lib().call('fami_softargmax_preds_f32', _p(batch_heatmaps.float().contiguous()), _p(c), _p(sc), beta, _p(preds), _p(mx),
                B, J, H, W, _stream(batch_heatmaps))
     return preds, mx.unsqueeze(-1)
+
+
+STRUCTURE_MAX = 64      # limbs and joints per sample the structure kernels take (csrc/loss.hip STRUCT_MAX)
+
+
+def check_structure_options(weight, pairs, min_len, eps, num_joints=None):
+    """-> (float(weight), pairs as a tuple of (a, b) int tuples, float(min_len), float(eps)), or ValueError -- host arithmetic
+    only, before anything is uploaded.  weight: a finite number > 0 (the factor of the structure term); pairs: 1..64 limbs
+    (a, b) of integer joint indices with a != b, inside 0..num_joints-1 where num_joints (2..64) is known; min_len: finite, >= 0,
+    in heatmap pixels; eps: finite, > 0.  min_len and eps must be finite in fp32 (eps also non-zero there)."""
+    for name, v in (('weight', weight), ('min_len', min_len), ('eps', eps)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('structure cosine %s is a finite number, not %r' % (name, v))
+    f32max = float(np.finfo(np.float32).max)
+    if not weight > 0:
+        raise ValueError('structure cosine weight must be > 0 (None switches the term off), got %r' % (weight,))
+    if not 0 <= min_len <= f32max:
+        raise ValueError('structure cosine min_len must be >= 0 and finite in fp32, got %r' % (min_len,))
+    if not (0 < eps <= f32max and float(np.float32(eps)) > 0):
+        raise ValueError('structure cosine eps must be > 0 and finite in fp32, got %r' % (eps,))
+    if num_joints is not None and not 2 <= num_joints <= STRUCTURE_MAX:
+        raise ValueError('the structure cosine term takes 2..%d joints, got %r' % (STRUCTURE_MAX, num_joints))
+    try:
+        rows = [tuple(p) for p in pairs]
+    except TypeError:
+        raise ValueError('structure cosine pairs is a sequence of (a, b) joint indices, not %r' % (pairs,))
+    if not 1 <= len(rows) <= STRUCTURE_MAX:
+        raise ValueError('the structure cosine term takes 1..%d limbs, got %d' % (STRUCTURE_MAX, len(rows)))
+    out = []
+    for p in rows:
+        if len(p) != 2 or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in p):
+            raise ValueError('a limb is a pair (a, b) of integer joint indices, got %r' % (p,))
+        a, b = int(p[0]), int(p[1])
+        hi = (STRUCTURE_MAX if num_joints is None else num_joints) - 1
+        if not (0 <= a <= hi and 0 <= b <= hi):
+            raise ValueError('limb %r: joint indices lie in 0..%d' % (p, hi))
+        if a == b:
+            raise ValueError('limb %r joins a joint to itself' % (p,))
+        out.append((a, b))
+    return float(weight), tuple(out), float(min_len), float(eps)
+
+
+_PAIRS_CACHE = {}
+
+
+def _pairs_on(dev, pairs):
+    """a checked pair table as an int32 device tensor [P,2]; one upload per (device, table)."""
+    key = (str(dev), pairs)
+    t = _PAIRS_CACHE.get(key)
+    if t is None:
+        t = _PAIRS_CACHE[key] = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
+    return t
+
+
+def _structure_rows(coords, txy, w, pairs_t, B, J, min_len, eps, scale):
+    """-> (loss [1], row values [B*P]): fami_structure_cos_fwd_f32 on contiguous fp32 device tensors"""
+    P = pairs_t.shape[0]
+    out = torch.empty(1, device=coords.device)
+    rows = torch.empty(B * P, device=coords.device)
+    lib().call('fami_structure_cos_fwd_f32', _p(coords), _p(txy), _p(w), _p(pairs_t), _p(out), B, J, P, min_len, eps,
+               float(scale), _p(rows), _stream(coords))
+    return out, rows
+
+
+class _StructureCos(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hm, txy, w, pairs_t, beta, min_len, eps, scale):
+        B, J = hm.shape[:2]
+        coords, stats = _softargmax_fwd(hm, beta)
+        out, _ = _structure_rows(coords, txy, w, pairs_t, B, J, min_len, eps, scale)
+        ctx.save_for_backward(hm, coords, stats, txy, w, pairs_t)
+        ctx.opts = (beta, min_len, eps, scale)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        hm, coords, stats, txy, w, pairs_t = ctx.saved_tensors
+        beta, min_len, eps, scale = ctx.opts
+        B, J, H, W = hm.shape
+        gcoords = torch.empty(B * J, 2, device=hm.device)
+        d = torch.empty_like(hm)
+        lib().call('fami_structure_cos_bwd_f32', _p(coords), _p(txy), _p(w), _p(pairs_t), _p(gcoords), B, J, pairs_t.shape[0],
+                   min_len, eps, float(scale), _p(g.reshape(1).float().contiguous()), _stream(hm))
+        lib().call('fami_softargmax_bwd_f32', _p(hm), _p(coords), _p(stats), _p(gcoords), _p(d), B * J, H, W, beta, 0, _stream(hm))
+        return d, None, None, None, None, None, None, None
+
+
+class StructureCosineSimilarity(nn.Module):
+    """The structure term the reference's train loop constructs beside JointMSELoss and IntegralL1Loss
+    (alignment_mi_function_term6_1.py:60-70; its file was never released, so the definition is this project's, include/fami.h):
+    (1 / (B P)) sum_bp valid_bp (1 - cos(c[b_p] - c[a_p], t[b_p] - t[a_p])) with c = soft_argmax(output, beta), t = target_xy
+    [B,J,2] in HEATMAP pixels and pairs the P limbs (a, b).  A limb counts (valid) when both its joints have a target weight
+    > 0 and its target is longer than min_len pixels; the denominator stays B P.  min_len = 1.0 is a starting value, not
+    tuned on data.  The gradient reaches `output` only, through fami_structure_cos_bwd_f32 and fami_softargmax_bwd_f32."""
+
+    def __init__(self, pairs=LIMB_PAIRS, beta=20.0, min_len=1.0, eps=1e-8, use_target_weight=True):
+        super().__init__()
+        _, self.beta = check_integral_options(1.0, beta)
+        _, self.pairs, self.min_len, self.eps = check_structure_options(1.0, pairs, min_len, eps)
+        self.use_target_weight = use_target_weight
+
+    def forward(self, output, target_xy, target_weight):
+        _need_cuda(output)
+        B, J = output.shape[:2]
+        check_structure_options(1.0, self.pairs, self.min_len, self.eps, J)
+        w = target_weight.reshape(B * J).float().contiguous() if self.use_target_weight else None
+        txy = target_xy.detach().reshape(B * J, 2).float().contiguous()
+        return _StructureCos.apply(output.float().contiguous(), txy, w, _pairs_on(output.device, self.pairs), self.beta,
+                                   self.min_len, self.eps, 1.0 / (B * len(self.pairs)))
+
+
+def limb_cosines(coords, target_xy, w, pairs=LIMB_PAIRS, min_len=1.0, eps=1e-8):
+    """The cosine of every limb, for logging: coords / target_xy [B,J,2] (device, heatmap pixels), w [B,J] or [B,J,1] target
+    weights or None -> [B,P] fp32 on the device, NaN where the limb is not valid.  The values are 1 - the rows of
+    fami_structure_cos_fwd_f32; which limbs are valid is restated here with tensor operations."""
+    _need_cuda(coords)
+    B, J = coords.shape[:2]
+    _, pairs, min_len, eps = check_structure_options(1.0, pairs, min_len, eps, J)
+    c = coords.detach().reshape(B * J, 2).float().contiguous()
+    t = target_xy.detach().reshape(B * J, 2).float().contiguous()
+    wv = None if w is None else w.detach().reshape(B * J).float().contiguous()
+    pt = _pairs_on(coords.device, pairs)
+    _, rows = _structure_rows(c, t, wv, pt, B, J, min_len, eps, 1.0)
+    a, b = pt[:, 0].long(), pt[:, 1].long()
+    td = t.reshape(B, J, 2).double()
+    d = td[:, b] - td[:, a]
+    valid = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] > float(np.float32(min_len)) ** 2
+    if wv is not None:
+        wb = wv.reshape(B, J)
+        valid &= (wb[:, a] > 0) & (wb[:, b] > 0)
+    return torch.where(valid, 1.0 - rows.reshape(B, len(pairs)), torch.full_like(rows, float('nan')).reshape(B, len(pairs)))
 
 
 def accuracy(output, target, thr=0.5):

@@ -711,6 +711,19 @@ class Trainer:
     scalar (integral_loss_value(); loss_value() and window_loss_value() include it; under accumulation its window sum is a
     tensor of its own and accum_state_dict() gains 'integral_loss_sum').  integral_coords(): the last step's coordinates.
     LOSS.INTEGRAL_L1.USE / .WEIGHT in from_cfg.
+
+    structure_cos_weight = W_S (needs targets_from_joints; None = none): the structure term, loss.StructureCosineSimilarity
+    (definition: include/fami.h) -- W_S / (B P) sum_bp valid_bp (1 - cos) between the predicted limb (the soft-argmax of the
+    final map at integral_beta) and the target limb (joint / stride), over the P limbs of structure_pairs (None:
+    data.LIMB_PAIRS); a limb is valid when both its joints have a target weight > 0 and its target is longer than
+    structure_min_len heatmap pixels (1.0: a starting value, not tuned on data).  Fixed at construction and baked into the
+    captured plans.  Behind the heatmap loss: fami_softargmax_fwd_f32, fami_heatmap_xy_f32 (both ONCE, their buffers shared,
+    when integral_l1_weight is set as well), fami_structure_cos_fwd_f32; its seeds fami_structure_cos_bwd_f32 and
+    fami_softargmax_bwd_f32 (accumulate = 1) behind fami_wmse_bwd_f32 (and fami_integral_l1_bwd_f32), into the same buffer
+    under the same loss scale.  It reads the target weights, also where OHKM selects.  Its device scalar, window sum and
+    checkpoint key ('structure_loss_sum') are the integral term's arrangement: structure_loss_value(); loss_value() and
+    window_loss_value() include it.  structure_cosines(): the last step's cosines [B,P].  LOSS.STRUCTURE_COSINE.USE / .WEIGHT in
+    from_cfg.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
@@ -718,7 +731,8 @@ class Trainer:
                  loss_scale=None, pck=True, data_parallel=None, optimizer='adam', momentum=0.0, dampening=0.0,
                  weight_decay=0.0, nesterov=False, lr_groups=None, max_grad_norm=None, scaler=None, accum_steps=None,
                  ema_decay=None, ema_warmup=False, frozen_bn=None, target_encoding='quantised', joint_weights=None,
-                 ohkm_topk=None, integral_l1_weight=None, integral_beta=20.0):
+                 ohkm_topk=None, integral_l1_weight=None, integral_beta=20.0, structure_cos_weight=None, structure_pairs=None,
+                 structure_min_len=1.0):
         """optimizer 'adam' (torch.optim.Adam) or 'sgd' (torch.optim.SGD with momentum / dampening / nesterov);
         weight_decay applies to either.  lr_groups: [(name_prefixes, lr)] -- the parameters that leave the base group
         (rate `lr`) for a rate of their own (parameter_groups; TRAIN.LR_SECOND_GROUP).  Trainer.from_cfg reads all of it
@@ -729,15 +743,27 @@ class Trainer:
         anything is captured (class docstring; None leaves the model's flags as they are).  target_encoding / joint_weights
         / ohkm_topk: the options of the supervision (class docstring; no config key but joint_weights').
         integral_l1_weight / integral_beta: the integral L1 coordinate term (class docstring; LOSS.INTEGRAL_L1.USE / .WEIGHT;
-        None = none)."""
-        from .loss import check_integral_options, check_ohkm_topk, check_target_options
-        self.integral_l1_weight = self.integral_beta = None
+        None = none).  structure_cos_weight / structure_pairs / structure_min_len: the structure term (class docstring;
+        LOSS.STRUCTURE_COSINE.USE / .WEIGHT; None = none; its soft-argmax is the one at integral_beta)."""
+        from .loss import check_integral_options, check_ohkm_topk, check_structure_options, check_target_options
+        self.integral_l1_weight = self.integral_beta = self._softargmax_beta = None
         if integral_l1_weight is not None:
             self.integral_l1_weight, self.integral_beta = check_integral_options(integral_l1_weight, integral_beta)
             if not targets_from_joints:
                 raise ValueError('integral_l1_weight supervises the joint position itself: it needs targets_from_joints=True '
                                  '(precomputed targets carry no real-valued position; loss.IntegralL1Loss takes one)')
         num_joints = getattr(model, 'num_joints', None)
+        self.structure_cos_weight = self.structure_pairs = self.structure_min_len = self.structure_eps = None
+        if structure_cos_weight is not None:
+            from .data import LIMB_PAIRS
+            _, self._softargmax_beta = check_integral_options(1.0, integral_beta)
+            self.structure_cos_weight, self.structure_pairs, self.structure_min_len, self.structure_eps = check_structure_options(
+                structure_cos_weight, LIMB_PAIRS if structure_pairs is None else structure_pairs, structure_min_len, 1e-8, num_joints)
+            if not targets_from_joints:
+                raise ValueError('structure_cos_weight supervises the joint position itself: it needs targets_from_joints=True '
+                                 '(precomputed targets carry no real-valued position; loss.StructureCosineSimilarity takes one)')
+        elif self.integral_l1_weight is not None:
+            self._softargmax_beta = self.integral_beta
         self.subpixel, self.joint_weights = check_target_options(target_encoding, joint_weights, num_joints)
         if (self.subpixel or self.joint_weights is not None) and not targets_from_joints:
             raise ValueError("target_encoding='subpixel' and joint_weights act where the Trainer makes the targets: they need "
@@ -882,6 +908,14 @@ class Trainer:
             self.integral_loss = torch.zeros(1, device=self.dev)
             if self.accum_steps > 1:
                 self._window_integral = torch.zeros(2, 1, device=self.dev)
+        # structure term: the same arrangement; (B, J) -> (gcoords [B*J,2], target weights [B*J]) and the pair table on the device
+        self.structure_loss = self._window_structure = self._pairs_dev = None
+        self._struct_bufs = {}
+        if self.structure_cos_weight is not None:
+            self.structure_loss = torch.zeros(1, device=self.dev)
+            self._pairs_dev = torch.tensor(self.structure_pairs, dtype=torch.int32).reshape(-1, 2).to(self.dev)
+            if self.accum_steps > 1:
+                self._window_structure = torch.zeros(2, 1, device=self.dev)
         if hasattr(model, '_ensure_nbt'):
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
@@ -909,6 +943,9 @@ class Trainer:
         integral = cfg.get('LOSS', {}).get('INTEGRAL_L1', {})      # mppe_config.py:217-219, core fn :61-69
         if integral.get('USE', False):
             kw['integral_l1_weight'] = integral.get('WEIGHT', 1.0)
+        structure = cfg.get('LOSS', {}).get('STRUCTURE_COSINE', {})      # mppe_config.py:225-227, core fn :62-70
+        if structure.get('USE', False):
+            kw['structure_cos_weight'] = structure.get('WEIGHT', 1.0)
         kw.update(trainer_kw)
         return cls(model, **kw)
 
@@ -1039,7 +1076,12 @@ class Trainer:
             B, J = joints.shape[:2]
             Hh, Wh = kf_x.shape[2] // 4, kf_x.shape[3] // 4
             target = eng.empty(B, J, Hh, Wh)
-            weight = eng.empty(B, J)
+            if self.structure_cos_weight is None:
+                weight = eng.empty(B, J)
+            else:      # structure_cosines() reads the step's target weights afterwards: a buffer of the Trainer's own
+                if (B, J) not in self._struct_bufs:
+                    self._struct_bufs[(B, J)] = (torch.zeros(B * J, 2, device=self.dev), torch.zeros(B * J, device=self.dev))
+                weight = self._struct_bufs[(B, J)][1].view(B, J)
             if self.subpixel or self._joint_w is not None:
                 if self._joint_w is not None and self._joint_w.numel() != J:
                     raise ValueError('joint_weights holds %d values, the batch has %d joints' % (self._joint_w.numel(), J))
@@ -1070,18 +1112,26 @@ class Trainer:
             eng.call('fami_ohkm_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]),
                      _p(self._sel_w[self._sel_key]), B, J, L, self.ohkm_topk, float(scale), _p(ws))
             w = self._sel_w[self._sel_key]
-        if self.integral_l1_weight is not None:
-            # the coordinate term: soft-argmax of the final map against joint / stride, on the TARGET weights (not OHKM's)
+        if self.integral_l1_weight is not None or self.structure_cos_weight is not None:
+            # the coordinate terms: soft-argmax of the final map against joint / stride, on the TARGET weights (not OHKM's);
+            # coordinates and target positions once, whichever of the two terms read them
             self._int_key = (B, J)
             if self._int_key not in self._int_bufs:
                 self._int_bufs[self._int_key] = tuple(torch.zeros(B * J, 2, device=self.dev) for _ in range(3))
             coords, stats, txy = self._int_bufs[self._int_key]
             tw = weight.reshape(B * J)
-            iscale = self.integral_l1_weight / (B * J)
-            eng.call('fami_softargmax_fwd_f32', _p(final_nchw), _p(coords), _p(stats), B * J, Hh, Wh, self.integral_beta)
+            eng.call('fami_softargmax_fwd_f32', _p(final_nchw), _p(coords), _p(stats), B * J, Hh, Wh, self._softargmax_beta)
             eng.call('fami_heatmap_xy_f32', _p(joints), _p(txy), B * J, Hh, Wh, kf_x.shape[2], kf_x.shape[3])
+        if self.integral_l1_weight is not None:
+            iscale = self.integral_l1_weight / (B * J)
             eng.call('fami_integral_l1_fwd_f32', _p(coords), _p(txy), _p(tw), _p(self.integral_loss), B * J, Hh, Wh,
                      float(iscale), _p(eng.ws(B * J * 4)))
+        if self.structure_cos_weight is not None:
+            P = len(self.structure_pairs)
+            sscale = self.structure_cos_weight / (B * P)
+            gcoords = self._struct_bufs[(B, J)][0]
+            eng.call('fami_structure_cos_fwd_f32', _p(coords), _p(txy), _p(tw), _p(self._pairs_dev), _p(self.structure_loss), B, J,
+                     P, self.structure_min_len, self.structure_eps, float(sscale), _p(eng.ws(B * P * 4)))
         if self.pck:
             # accuracy(pred_heatmaps, target) and accuracy(kf_bb_heatmaps, target), core fn :159-163, without the four
             # device-to-host heatmap copies
@@ -1099,6 +1149,11 @@ class Trainer:
         if self.integral_l1_weight is not None:
             eng.call('fami_integral_l1_bwd_f32', _p(final_nchw), _p(coords), _p(stats), _p(txy), _p(tw), _p(dpred), B * J,
                      Hh, Wh, self.integral_beta, float(iscale * ls), _p(ls_dev), 1)
+        if self.structure_cos_weight is not None:
+            eng.call('fami_structure_cos_bwd_f32', _p(coords), _p(txy), _p(tw), _p(self._pairs_dev), _p(gcoords), B, J, P,
+                     self.structure_min_len, self.structure_eps, float(sscale * ls), _p(ls_dev))
+            eng.call('fami_softargmax_bwd_f32', _p(final_nchw), _p(coords), _p(stats), _p(gcoords), _p(dpred), B * J, Hh, Wh,
+                     self._softargmax_beta, 1)
         eng.seed_nchw(aux['final'], dpred)
         if self.use_mi and aux['mis']:
             a, b = self.alpha, self.beta
@@ -1162,6 +1217,18 @@ class Trainer:
         if self._int_key is None or self._int_key not in self._int_bufs:
             return None
         return self._int_bufs[self._int_key][0].reshape(*self._int_key, 2)
+
+    def structure_cosines(self):
+        """structure_cos_weight: the cosine of every limb of the last step, a device tensor [B,P], NaN where the limb was not
+        valid (loss.limb_cosines on the coordinates, target positions and target weights the step's loss saw; None without the
+        option or before the first step).  Logging only: it launches outside the captured plan."""
+        if self.structure_cos_weight is None or self._int_key is None or self._int_key not in self._struct_bufs:
+            return None
+        from .loss import limb_cosines
+        B, J = self._int_key
+        coords, _, txy = self._int_bufs[self._int_key]
+        return limb_cosines(coords.reshape(B, J, 2), txy.reshape(B, J, 2), self._struct_bufs[self._int_key][1].reshape(B, J),
+                            self.structure_pairs, self.structure_min_len, self.structure_eps)
 
     def skipped_steps(self):
         """Optimizer steps skipped so far because the loss-scaled gradients held inf / NaN (fp16 mode; synchronises).
@@ -1445,6 +1512,10 @@ class Trainer:
             wi = self._window_integral
             self._lc('fami_axpby_f32', _p(self.integral_loss), _p(wi[0]) if self.window_position else None,
                      _p(wi[1 if closing else 0]), 1, 1.0, 1.0, _stream(self.dev))
+        if self._window_structure is not None:      # ... and the structure term likewise
+            wsum = self._window_structure
+            self._lc('fami_axpby_f32', _p(self.structure_loss), _p(wsum[0]) if self.window_position else None,
+                     _p(wsum[1 if closing else 0]), 1, 1.0, 1.0, _stream(self.dev))
         self.window_position = 0 if closing else self.window_position + 1
 
     def reset_window(self):
@@ -1459,12 +1530,14 @@ class Trainer:
         total = self._total_loss((self._window_loss[1] / self.accum_steps).tolist())
         if self._window_integral is not None:
             total += self._window_integral[1].item() / self.accum_steps
+        if self._window_structure is not None:
+            total += self._window_structure[1].item() / self.accum_steps
         return total
 
     def accum_state_dict(self):
         """The 'grad_accum' checkpoint entry: {'steps': N, 'position': k} and, inside a window (k > 0), the accumulation
         arena and the open window's loss sum on the host (synchronises); with integral_l1_weight also 'integral_loss_sum',
-        the open window's sum of that term."""
+        the open window's sum of that term, and with structure_cos_weight 'structure_loss_sum'."""
         sd = {'steps': self.accum_steps, 'position': self.window_position}
         if self.window_position > 0:
             sd['arena'] = self.accum.detach().cpu().clone()
@@ -1472,6 +1545,9 @@ class Trainer:
             wi = getattr(self, '_window_integral', None)      # (getattr: checkpoint code borrows this method for host objects)
             if wi is not None:
                 sd['integral_loss_sum'] = wi[0].detach().cpu().clone()
+            wsum = getattr(self, '_window_structure', None)
+            if wsum is not None:
+                sd['structure_loss_sum'] = wsum[0].detach().cpu().clone()
         return sd
 
     def load_accum_state_dict(self, sd):
@@ -1490,6 +1566,11 @@ class Trainer:
                 if 'integral_loss_sum' not in sd:
                     raise ValueError('the checkpoint was written inside a window without the integral L1 term')
                 wi[0].copy_(sd['integral_loss_sum'])
+            wsum = getattr(self, '_window_structure', None)
+            if wsum is not None:
+                if 'structure_loss_sum' not in sd:
+                    raise ValueError('the checkpoint was written inside a window without the structure cosine term')
+                wsum[0].copy_(sd['structure_loss_sum'])
         self.window_position = k
 
     def _accum_eager_step(self, kf_x, sup_x, target, weight):
@@ -1691,7 +1772,7 @@ class Trainer:
                              (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape)))
         if self.ohkm_topk is not None:
             self._sel_key = (target.shape[0], target.shape[1])       # (a replay does not pass through _forward_backward)
-        if self.integral_l1_weight is not None:
+        if self.integral_l1_weight is not None or self.structure_cos_weight is not None:
             self._int_key = (target.shape[0], target.shape[1])
         if not self.use_graph:
             return self._eager_step(kf_x, sup_x, target, weight)
@@ -1733,7 +1814,12 @@ class Trainer:
 
     def loss_value(self):
         """Total loss of the last step (host float; forces a sync -- logging only)."""
-        return self._total_loss(self.loss_parts.tolist()) + self.integral_loss_value()
+        return self._total_loss(self.loss_parts.tolist()) + self.integral_loss_value() + self.structure_loss_value()
+
+    def structure_loss_value(self):
+        """The structure cosine term of the last step, weight included (host float; forces a sync -- logging only); 0.0 without
+        structure_cos_weight."""
+        return 0.0 if self.structure_loss is None else self.structure_loss.item()
 
     def integral_loss_value(self):
         """The integral L1 term of the last step, weight included (host float; forces a sync -- logging only); 0.0 without

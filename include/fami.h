@@ -542,6 +542,41 @@ int fami_integral_l1_bwd_f32(const float* hm, const float* coords, const float* 
 int fami_softargmax_preds_f32(const float* hm, const float* center, const float* scale, float beta, float* preds,
                               float* maxvals, int B, int J, int H, int W, fami_stream_t stream);
 
+/* ---- structure (limb-direction cosine) loss term (csrc/loss.hip) ---------------------------------
+ * The third criterion the reference's train loop constructs (alignment_mi_function_term6_1.py:60-70,
+ * LOSS.STRUCTURE_COSINE.USE / .WEIGHT), again from a file that was never released: this project's definition.  It
+ * supervises the DIRECTION of every limb: 1 - cosine between the predicted limb (soft-argmax coordinates) and the target limb.
+ * Inputs: coords [B J, 2] fp32, the soft-argmax of the final map in heatmap pixels (fami_softargmax_fwd_f32); target_xy
+ *   [B J, 2] fp32 (fami_heatmap_xy_f32); w [B J] fp32, the target weights (NULL: all 1); pairs [P, 2] int32 ON THE DEVICE:
+ *   limb p goes from joint a_p to joint b_p.
+ * Per sample s and limb p, in fp64 on the fp32 inputs, every operation rounded on its own (never contracted), in this order:
+ *   t = txy[b] - txy[a], u = c[b] - c[a] (exact in fp64); tt = tx tx + ty ty, uu = ux ux + uy uy, ut = ux tx + uy ty;
+ *   valid = w[a] > 0 && w[b] > 0 && tt > min_len^2 (a comparison with NaN is false: such a limb is not valid);
+ *   nu = sqrt(uu), nt = sqrt(tt), mu = nu <= eps ? eps : nu, mt = nt <= eps ? eps : nt, cos = ut / (mu mt):
+ *   torch.nn.functional.cosine_similarity's rule (with `valid` the clamp on nt is active only for min_len < eps).
+ *   Row value l[s,p] = valid ? 1 - cos : 0, rounded ONCE to fp32 and stored in ws [B P].
+ * Loss: L = scale * sum l, summed in fp64 in the fixed order of fami_integral_l1_fwd_f32.  The caller's scale is
+ *   weight / (B P): the denominator is fixed, NOT the number of valid limbs (the integral term's convention).
+ * Gradient with respect to the coordinates: nu > eps: dcos/du = t / (nu mt) - (cos u) / (nu nu); otherwise (the clamp's
+ *   gradient in torch) dcos/du = t / (eps mt).  gcoords[s,j] = g sum_p valid_p (-dcos/du_p) (+1 if j == b_p, -1 if j == a_p),
+ *   the limbs walked in list order, summed in fp64, the product with g rounded once to fp32; g = scale * (gdev ? gdev[0] : 1)
+ *   as an fp32 product, the fami_wmse_bwd_f32 convention (a dynamic loss scale needs no host read-back).  A joint on no valid
+ *   limb gets 0.  Every entry of gcoords [B J, 2] is written.  The heatmap gradient is
+ *   fami_softargmax_bwd_f32(hm, coords, stats, gcoords, dhm, ..., accumulate).
+ * min_len is in heatmap pixels; eps as in torch (1e-8).  1 <= P <= 64, 2 <= J <= 64.  The pair table lives on the device, so
+ * the HOST checks it before upload (loss.check_structure_options: indices in 0..J-1, a != b); the kernels treat a limb that
+ * breaks either rule as not valid and read nothing through it.
+ * Forward: one thread per (sample, limb), then the one-workgroup fp64 sum.  Backward: one wavefront per sample, limbs then
+ * joints through LDS.  No atomics, no workspace beyond ws; run-to-run bitwise reproducible.
+ * A size outside the limits, min_len not finite or < 0, eps not finite or <= 0, a NULL among the required pointers (all but
+ * w and gdev): -1, nothing written. */
+int fami_structure_cos_fwd_f32(const float* coords, const float* target_xy, const float* w, const int* pairs, float* loss,
+                               int B, int J, int P, float min_len, float eps, double scale, float* ws,
+                               fami_stream_t stream);
+int fami_structure_cos_bwd_f32(const float* coords, const float* target_xy, const float* w, const int* pairs,
+                               float* gcoords, int B, int J, int P, float min_len, float eps, float scale,
+                               const float* gdev, fami_stream_t stream);
+
 /* PCK accuracy on heatmap argmax, engine/core/utils/evaluate.py:39-75 (`accuracy`, called twice per training step at
  * engine/core/functions/alignment_mi_function_term6_1.py:159-163 after D2H copies of four heatmap stacks): here
  * three launches and no host sync.  pred_hm / target_hm [B,J,H,W]; out[J+3] = {acc[0] = mean of the defined
