@@ -30,6 +30,7 @@ import torch.distributed as dist
 from . import options
 from ._lib import lib
 from .engine import Engine, _p
+from .head import SupervisionHead
 
 
 def _stream(dev):
@@ -687,43 +688,36 @@ class Trainer:
     modules keys the captured plans next to the optimizer hyper-parameters: a later freeze_batchnorm call re-captures.
     The reference has no such switch, so there is no config key; None (default) leaves every launch as it is.
 
-    The supervision (the target, loss and seed launches between the forward and the backward pass) has three options, all
-    fixed at construction like mse_weight and baked into the captured plans; the defaults leave the three launches
-    fami_gauss_target_f32 / fami_wmse_fwd_f32 / fami_wmse_bwd_f32 as they are.
+    The supervision (targets, loss terms and seeds between the forward and the backward pass) lives in one object, `head`
+    (head.SupervisionHead: its docstring lists each option's launches, their order and the per-shape buffers).  Its options are
+    fixed at construction like mse_weight and baked into the captured plans; the defaults leave the launch sequence as it is.
     joint_weights (needs targets_from_joints): J factors of the target weights, the reference's
     LOSS.USE_DIFFERENT_JOINTS_WEIGHT (heatmaps_process.py:200-201; from_cfg reads the key and passes data.JOINTS_WEIGHT).
     target_encoding='subpixel' (needs targets_from_joints): Gaussians centred at the real-valued joint position, the
-    encoding the DARK decode assumes (loss.generate_heatmaps); both go through fami_gauss_target_ex_f32.  The PCK rows take
-    the argmax of the target map: for a joint at exactly half a pixel the sub-pixel map's first maximum is the lower
-    pixel where the quantised one has the upper.
-    ohkm_topk = k (either kind of target): online hard keypoint mining, loss.JointOHKMMSELoss -- fami_ohkm_fwd_f32 in
-    place of fami_wmse_fwd_f32 ranks the J row losses of each sample on the device and writes the selected weights;
-    loss_parts[0] = mse_weight * (1/B) sum_b (1/k) sum_{top-k} mean_p (w (pred - gt))^2, and the seeds are
-    fami_wmse_bwd_f32 on the selected weights with mse_weight / (B L k).  k = J is the default loss.  PCK and the MI
-    terms are untouched.  ohkm_selection() is the last step's selection.
+    encoding the DARK decode assumes (loss.generate_heatmaps).  The PCK rows take the argmax of the target map: for a joint at
+    exactly half a pixel the sub-pixel map's first maximum is the lower pixel where the quantised one has the upper.
+    ohkm_topk = k (either kind of target): online hard keypoint mining, loss.JointOHKMMSELoss -- the J row losses of each
+    sample are ranked on the device; loss_parts[0] = mse_weight * (1/B) sum_b (1/k) sum_{top-k} mean_p (w (pred - gt))^2, and
+    the seeds carry mse_weight / (B L k) on the selected weights.  k = J is the default loss.  PCK and the MI terms are
+    untouched.  ohkm_selection() is the last step's selection.
 
     integral_l1_weight = W_I (needs targets_from_joints; None = none): the integral L1 coordinate term, loss.IntegralL1Loss
     (definition: include/fami.h) -- W_I / (B J) sum_bj w_bj (|cx - tx| / W + |cy - ty| / H) with (cx, cy) the soft-argmax of the
-    final map at integral_beta and (tx, ty) = joint / stride.  Fixed at construction and baked into the captured plans.
-    Behind the heatmap loss: fami_softargmax_fwd_f32, fami_heatmap_xy_f32, fami_integral_l1_fwd_f32; its seed
-    fami_integral_l1_bwd_f32 directly behind fami_wmse_bwd_f32, accumulating into the same buffer under the same loss scale.
-    It reads the target weights, also where OHKM selects.  loss_parts keeps its 7 entries: the term lives in its own device
-    scalar (integral_loss_value(); loss_value() and window_loss_value() include it; under accumulation its window sum is a
-    tensor of its own and accum_state_dict() gains 'integral_loss_sum').  integral_coords(): the last step's coordinates.
-    LOSS.INTEGRAL_L1.USE / .WEIGHT in from_cfg.
+    final map at integral_beta and (tx, ty) = joint / stride.  Its seed accumulates into the heat-map seed's buffer under the
+    same loss scale.  It reads the target weights, also where OHKM selects.  loss_parts keeps its 7 entries: the term lives in
+    its own device scalar (integral_loss_value(); loss_value() and window_loss_value() include it; under accumulation its
+    window sum is a tensor of its own and accum_state_dict() gains a key for it).  integral_coords(): the last step's
+    coordinates.  LOSS.INTEGRAL_L1.USE / .WEIGHT in from_cfg.
 
     structure_cos_weight = W_S (needs targets_from_joints; None = none): the structure term, loss.StructureCosineSimilarity
     (definition: include/fami.h) -- W_S / (B P) sum_bp valid_bp (1 - cos) between the predicted limb (the soft-argmax of the
     final map at integral_beta) and the target limb (joint / stride), over the P limbs of structure_pairs (None:
     data.LIMB_PAIRS); a limb is valid when both its joints have a target weight > 0 and its target is longer than
-    structure_min_len heatmap pixels (1.0: a starting value, not tuned on data).  Fixed at construction and baked into the
-    captured plans.  Behind the heatmap loss: fami_softargmax_fwd_f32, fami_heatmap_xy_f32 (both ONCE, their buffers shared,
-    when integral_l1_weight is set as well), fami_structure_cos_fwd_f32; its seeds fami_structure_cos_bwd_f32 and
-    fami_softargmax_bwd_f32 (accumulate = 1) behind fami_wmse_bwd_f32 (and fami_integral_l1_bwd_f32), into the same buffer
-    under the same loss scale.  It reads the target weights, also where OHKM selects.  Its device scalar, window sum and
-    checkpoint key ('structure_loss_sum') are the integral term's arrangement: structure_loss_value(); loss_value() and
-    window_loss_value() include it.  structure_cosines(): the last step's cosines [B,P].  LOSS.STRUCTURE_COSINE.USE / .WEIGHT in
-    from_cfg.
+    structure_min_len heatmap pixels (1.0: a starting value, not tuned on data).  The soft-argmax and the target positions are
+    computed once and shared when integral_l1_weight is set as well; its seeds go into the same buffer under the same loss
+    scale.  It reads the target weights, also where OHKM selects.  Its device scalar, window sum and checkpoint key are the
+    integral term's arrangement: structure_loss_value(); loss_value() and window_loss_value() include it.
+    structure_cosines(): the last step's cosines [B,P].  LOSS.STRUCTURE_COSINE.USE / .WEIGHT in from_cfg.
     """
 
     def __init__(self, model, lr=1e-3, mse_weight=1.0, alpha=0.5, beta=0.1, use_mi=True, bucket_mb=32,
@@ -745,30 +739,10 @@ class Trainer:
         integral_l1_weight / integral_beta: the integral L1 coordinate term (class docstring; LOSS.INTEGRAL_L1.USE / .WEIGHT;
         None = none).  structure_cos_weight / structure_pairs / structure_min_len: the structure term (class docstring;
         LOSS.STRUCTURE_COSINE.USE / .WEIGHT; None = none; its soft-argmax is the one at integral_beta)."""
-        from .loss import check_integral_options, check_ohkm_topk, check_structure_options, check_target_options
-        self.integral_l1_weight = self.integral_beta = self._softargmax_beta = None
-        if integral_l1_weight is not None:
-            self.integral_l1_weight, self.integral_beta = check_integral_options(integral_l1_weight, integral_beta)
-            if not targets_from_joints:
-                raise ValueError('integral_l1_weight supervises the joint position itself: it needs targets_from_joints=True '
-                                 '(precomputed targets carry no real-valued position; loss.IntegralL1Loss takes one)')
-        num_joints = getattr(model, 'num_joints', None)
-        self.structure_cos_weight = self.structure_pairs = self.structure_min_len = self.structure_eps = None
-        if structure_cos_weight is not None:
-            from .data import LIMB_PAIRS
-            _, self._softargmax_beta = check_integral_options(1.0, integral_beta)
-            self.structure_cos_weight, self.structure_pairs, self.structure_min_len, self.structure_eps = check_structure_options(
-                structure_cos_weight, LIMB_PAIRS if structure_pairs is None else structure_pairs, structure_min_len, 1e-8, num_joints)
-            if not targets_from_joints:
-                raise ValueError('structure_cos_weight supervises the joint position itself: it needs targets_from_joints=True '
-                                 '(precomputed targets carry no real-valued position; loss.StructureCosineSimilarity takes one)')
-        elif self.integral_l1_weight is not None:
-            self._softargmax_beta = self.integral_beta
-        self.subpixel, self.joint_weights = check_target_options(target_encoding, joint_weights, num_joints)
-        if (self.subpixel or self.joint_weights is not None) and not targets_from_joints:
-            raise ValueError("target_encoding='subpixel' and joint_weights act where the Trainer makes the targets: they need "
-                             "targets_from_joints=True (precomputed targets: loss.generate_heatmaps takes both)")
-        self.ohkm_topk = None if ohkm_topk is None else check_ohkm_topk(ohkm_topk, num_joints)
+        self.head = head = SupervisionHead(
+            model, targets_from_joints, sigma, mse_weight, alpha, beta, use_mi, pck, target_encoding, joint_weights, ohkm_topk,
+            integral_l1_weight, integral_beta, structure_cos_weight, structure_pairs, structure_min_len)
+        self.integral_beta = None if head.integral_l1_weight is None else head.softargmax_beta
         if frozen_bn is not None:
             freeze_batchnorm(model, frozen_bn)
         self._bn_modules = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
@@ -781,11 +755,9 @@ class Trainer:
         self.accum_steps = 1 if accum_steps is None else accum_steps
         self.model = model
         self.route = getattr(model, 'route', None)      # kernel-routing state (None: process default), as the model's engines
-        self.targets_from_joints, self.sigma = targets_from_joints, sigma
         self.dev = next(model.parameters()).device
         if self.dev.type != 'cuda':
             raise RuntimeError('Trainer needs the model on the GPU (HIP path only)')
-        self.mse_weight, self.alpha, self.beta, self.use_mi = mse_weight, alpha, beta, use_mi
         self.act_dtype = getattr(model, 'act_dtype', torch.float32)
         self.dynamic_scale = isinstance(loss_scale, str)
         if self.dynamic_scale and loss_scale != 'dynamic':
@@ -891,31 +863,9 @@ class Trainer:
         # (eager launches, all-reduces fired from the Engine.backward hooks)
         self.ddp_plan = options.get('FAMI_DDP_PLAN')
         self.use_graph = use_graph and (not self.ddp or options.flag('FAMI_DDP_GRAPH'))
-        self.loss_parts = torch.zeros(7, device=self.dev)     # mse, mi_1..6 (device scalars of the last step)
-        self.pck = pck
-        self.acc = None           # [2, J+3] device floats of the last step: PCK of final_hm / kf_bb_hm (see accuracy())
         self._cache = {}          # batch shapes -> (plan, static inputs, static outputs, optimizer hyper version)
-        self._joint_w = (None if self.joint_weights is None else
-                         torch.tensor(self.joint_weights, dtype=torch.float32, device=self.dev))
-        self._sel_w = {}          # OHKM: (B, J) -> selected weights [B*J], written by that batch shape's launches
-        self._sel_key = None      # ... and the shape of the last step
-        # integral L1 term: its device scalar of the last step, (B, J) -> (coords, stats, target_xy) [B*J,2] each, the shape of
-        # the last step, and under accumulation {open window, last closed window} sums of the scalar
-        self.integral_loss = self._window_integral = None
-        self._int_bufs = {}
-        self._int_key = None
-        if self.integral_l1_weight is not None:
-            self.integral_loss = torch.zeros(1, device=self.dev)
-            if self.accum_steps > 1:
-                self._window_integral = torch.zeros(2, 1, device=self.dev)
-        # structure term: the same arrangement; (B, J) -> (gcoords [B*J,2], target weights [B*J]) and the pair table on the device
-        self.structure_loss = self._window_structure = self._pairs_dev = None
-        self._struct_bufs = {}
-        if self.structure_cos_weight is not None:
-            self.structure_loss = torch.zeros(1, device=self.dev)
-            self._pairs_dev = torch.tensor(self.structure_pairs, dtype=torch.int32).reshape(-1, 2).to(self.dev)
-            if self.accum_steps > 1:
-                self._window_structure = torch.zeros(2, 1, device=self.dev)
+        head.place(self.dev, self.accum_steps > 1)
+        self.scalar_terms = head.terms       # the terms kept beside loss_parts (head.ScalarTerm): integral first, structure second
         if hasattr(model, '_ensure_nbt'):
             model._ensure_nbt(self.dev)      # BatchNorm counters move into their arena BEFORE any snapshot is taken
         if self.ddp:
@@ -1070,110 +1020,13 @@ class Trainer:
         eng.prepacked_dcn_bwd = {id(w): buf for w, buf, _, _ in dcn}
         eng.prepacked_dcn_fwd = {id(w): fbuf for w, _, _, fbuf in dcn}
         eng.dcn_fwd_ready = packed_fwd          # event the first DCN forward waits for
-        if self.targets_from_joints:
-            # on-device Gaussian targets (generate_heatmaps): `target` carries joints [B,J,2], `weight` visibility [B,J]
-            joints, vis = target, weight
-            B, J = joints.shape[:2]
-            Hh, Wh = kf_x.shape[2] // 4, kf_x.shape[3] // 4
-            target = eng.empty(B, J, Hh, Wh)
-            if self.structure_cos_weight is None:
-                weight = eng.empty(B, J)
-            else:      # structure_cosines() reads the step's target weights afterwards: a buffer of the Trainer's own
-                if (B, J) not in self._struct_bufs:
-                    self._struct_bufs[(B, J)] = (torch.zeros(B * J, 2, device=self.dev), torch.zeros(B * J, device=self.dev))
-                weight = self._struct_bufs[(B, J)][1].view(B, J)
-            if self.subpixel or self._joint_w is not None:
-                if self._joint_w is not None and self._joint_w.numel() != J:
-                    raise ValueError('joint_weights holds %d values, the batch has %d joints' % (self._joint_w.numel(), J))
-                eng.call('fami_gauss_target_ex_f32', _p(joints), _p(vis), _p(self._joint_w), _p(target), _p(weight), B, J,
-                         Hh, Wh, kf_x.shape[2], kf_x.shape[3], self.sigma, int(self.subpixel))
-            else:
-                eng.call('fami_gauss_target_f32', _p(joints), _p(vis), _p(target), _p(weight), B, J, Hh, Wh,
-                         kf_x.shape[2], kf_x.shape[3], self.sigma)
+        target, weight, joints = self.head.targets(eng, kf_x, target, weight)
         outs, _ = model._body(eng, kf_x, sup_x)
         model._advance_bn_counters(eng)
-        aux = eng.aux
-        final_nchw = outs[0]
-        B, J, Hh, Wh = final_nchw.shape
-        L = Hh * Wh
-        scale = self.mse_weight / (B * L * (J if self.ohkm_topk is None else self.ohkm_topk))
-        w = weight.reshape(B * J)
-        ws = eng.ws(B * J * 4)
-        if self.ohkm_topk is None:
-            eng.call('fami_wmse_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]), B * J, L,
-                     float(scale), _p(ws))
-        else:
-            # the selection between the loss rows and the seeds, on the device: the seeds below read the selected weights
-            if self.ohkm_topk > J:
-                raise ValueError('ohkm_topk = %d, the model has %d joints' % (self.ohkm_topk, J))
-            self._sel_key = (B, J)
-            if self._sel_key not in self._sel_w:
-                self._sel_w[self._sel_key] = torch.zeros(B * J, device=self.dev)
-            eng.call('fami_ohkm_fwd_f32', _p(final_nchw), _p(target), _p(w), _p(self.loss_parts[0:1]),
-                     _p(self._sel_w[self._sel_key]), B, J, L, self.ohkm_topk, float(scale), _p(ws))
-            w = self._sel_w[self._sel_key]
-        if self.integral_l1_weight is not None or self.structure_cos_weight is not None:
-            # the coordinate terms: soft-argmax of the final map against joint / stride, on the TARGET weights (not OHKM's);
-            # coordinates and target positions once, whichever of the two terms read them
-            self._int_key = (B, J)
-            if self._int_key not in self._int_bufs:
-                self._int_bufs[self._int_key] = tuple(torch.zeros(B * J, 2, device=self.dev) for _ in range(3))
-            coords, stats, txy = self._int_bufs[self._int_key]
-            tw = weight.reshape(B * J)
-            eng.call('fami_softargmax_fwd_f32', _p(final_nchw), _p(coords), _p(stats), B * J, Hh, Wh, self._softargmax_beta)
-            eng.call('fami_heatmap_xy_f32', _p(joints), _p(txy), B * J, Hh, Wh, kf_x.shape[2], kf_x.shape[3])
-        if self.integral_l1_weight is not None:
-            iscale = self.integral_l1_weight / (B * J)
-            eng.call('fami_integral_l1_fwd_f32', _p(coords), _p(txy), _p(tw), _p(self.integral_loss), B * J, Hh, Wh,
-                     float(iscale), _p(eng.ws(B * J * 4)))
-        if self.structure_cos_weight is not None:
-            P = len(self.structure_pairs)
-            sscale = self.structure_cos_weight / (B * P)
-            gcoords = self._struct_bufs[(B, J)][0]
-            eng.call('fami_structure_cos_fwd_f32', _p(coords), _p(txy), _p(tw), _p(self._pairs_dev), _p(self.structure_loss), B, J,
-                     P, self.structure_min_len, self.structure_eps, float(sscale), _p(eng.ws(B * P * 4)))
-        if self.pck:
-            # accuracy(pred_heatmaps, target) and accuracy(kf_bb_heatmaps, target), core fn :159-163, without the four
-            # device-to-host heatmap copies
-            if self.acc is None or self.acc.shape[1] != J + 3:
-                self.acc = torch.zeros(2, J + 3, device=self.dev)
-            iws = eng.empty(2 * B * J, dtype=torch.int64)
-            mws = eng.empty(2 * B * J)
-            for k, hm in enumerate((final_nchw, outs[1])):
-                eng.call('fami_pck_accuracy_f32', _p(hm), _p(target), _p(self.acc[k]), _p(iws), _p(mws), B, J, Hh, Wh,
-                         0.5)
+        seed = self.head.forward(eng, kf_x, outs, target, weight, joints)
         # the loss scale of the seeds: a host factor, or (dynamic) the device scalar the scale update rewrites
         ls, ls_dev = (1.0, self.scaler_state[0:1]) if self.dynamic_scale else (self.loss_scale, None)
-        dpred = torch.empty_like(final_nchw)
-        eng.call('fami_wmse_bwd_f32', _p(final_nchw), _p(target), _p(w), _p(dpred), B * J, L, float(scale * ls), _p(ls_dev), 0)
-        if self.integral_l1_weight is not None:
-            eng.call('fami_integral_l1_bwd_f32', _p(final_nchw), _p(coords), _p(stats), _p(txy), _p(tw), _p(dpred), B * J,
-                     Hh, Wh, self.integral_beta, float(iscale * ls), _p(ls_dev), 1)
-        if self.structure_cos_weight is not None:
-            eng.call('fami_structure_cos_bwd_f32', _p(coords), _p(txy), _p(tw), _p(self._pairs_dev), _p(gcoords), B, J, P,
-                     self.structure_min_len, self.structure_eps, float(sscale * ls), _p(ls_dev))
-            eng.call('fami_softargmax_bwd_f32', _p(final_nchw), _p(coords), _p(stats), _p(gcoords), _p(dpred), B * J, Hh, Wh,
-                     self._softargmax_beta, 1)
-        eng.seed_nchw(aux['final'], dpred)
-        if self.use_mi and aux['mis']:
-            a, b = self.alpha, self.beta
-            coef = [-b * a, b * a, a, -a, a, -a]        # core fn :119-148
-            if eng.use_lanes:      # the six seeds on three lanes
-                eng._do_fork(3)        # (not taped: the seeds are enqueued here, ahead of the tape walk)
-            pending = []
-            same = aux.get('mi_same', {})      # repeated terms (mi_6 is mi_2): one gradient pass with the summed coefficient
-            for k, j in same.items():
-                coef[j] += coef[k]
-            for k, ((val, seed), c) in enumerate(zip(aux['mis'], coef)):
-                if eng.use_lanes:
-                    eng.set_lane(k % 3)
-                eng.call('fami_axpby_f32', _p(val), None, _p(self.loss_parts[1 + k:2 + k]), 1, 1.0, 0.0)
-                if k not in same:
-                    pending.append(seed(c * ls, ls_dev, True))
-            if eng.use_lanes:
-                eng._do_join(3)
-            for fin in pending:        # the accumulations into the (shared) gradient buffers, in term order, on lane 0
-                fin()
+        seeded = seed(ls, ls_dev)       # noqa: F841  (the seed buffer, held until the backward pass is enqueued)
         hook = None
         if on_bucket is not None:
             def bucket_ready(lo, hi):
@@ -1207,28 +1060,18 @@ class Trainer:
         """OHKM: the joints the last step's loss counted, a device bool tensor [B,J] (None without ohkm_topk or before the
         first step): the selected weights are non-zero there.  A joint of weight 0 that fills one of the k places -- a
         sample with fewer than k visible joints -- adds nothing to loss or gradient and reads False."""
-        if self._sel_key is None:
-            return None
-        return (self._sel_w[self._sel_key] != 0).reshape(self._sel_key)
+        return self.head.ohkm_selection()
 
     def integral_coords(self):
         """integral_l1_weight: the soft-argmax coordinates the last step's loss saw, a device tensor [B,J,2] in heatmap pixels
         (None without the option or before the first step)."""
-        if self._int_key is None or self._int_key not in self._int_bufs:
-            return None
-        return self._int_bufs[self._int_key][0].reshape(*self._int_key, 2)
+        return self.head.integral_coords()
 
     def structure_cosines(self):
         """structure_cos_weight: the cosine of every limb of the last step, a device tensor [B,P], NaN where the limb was not
         valid (loss.limb_cosines on the coordinates, target positions and target weights the step's loss saw; None without the
         option or before the first step).  Logging only: it launches outside the captured plan."""
-        if self.structure_cos_weight is None or self._int_key is None or self._int_key not in self._struct_bufs:
-            return None
-        from .loss import limb_cosines
-        B, J = self._int_key
-        coords, _, txy = self._int_bufs[self._int_key]
-        return limb_cosines(coords.reshape(B, J, 2), txy.reshape(B, J, 2), self._struct_bufs[self._int_key][1].reshape(B, J),
-                            self.structure_pairs, self.structure_min_len, self.structure_eps)
+        return self.head.structure_cosines()
 
     def skipped_steps(self):
         """Optimizer steps skipped so far because the loss-scaled gradients held inf / NaN (fp16 mode; synchronises).
@@ -1504,18 +1347,10 @@ class Trainer:
 
     def _window_call_done(self, closing):
         """the loss parts of this call into the window sum (one 7-element launch; row 0: the open window, row 1: the last
-        closed one) and the host-side position"""
-        w = self._window_loss
-        self._lc('fami_axpby_f32', _p(self.loss_parts), _p(w[0]) if self.window_position else None, _p(w[1 if closing else 0]),
-                 7, 1.0, 1.0, _stream(self.dev))
-        if self._window_integral is not None:       # ... and the integral term into a sum of its own
-            wi = self._window_integral
-            self._lc('fami_axpby_f32', _p(self.integral_loss), _p(wi[0]) if self.window_position else None,
-                     _p(wi[1 if closing else 0]), 1, 1.0, 1.0, _stream(self.dev))
-        if self._window_structure is not None:      # ... and the structure term likewise
-            wsum = self._window_structure
-            self._lc('fami_axpby_f32', _p(self.structure_loss), _p(wsum[0]) if self.window_position else None,
-                     _p(wsum[1 if closing else 0]), 1, 1.0, 1.0, _stream(self.dev))
+        closed one), every scalar term into a sum of its own, and the host-side position"""
+        for value, w, n in [(self.loss_parts, self._window_loss, 7)] + [(t.value, t.window, 1) for t in self.scalar_terms]:
+            self._lc('fami_axpby_f32', _p(value), _p(w[0]) if self.window_position else None, _p(w[1 if closing else 0]),
+                     n, 1.0, 1.0, _stream(self.dev))
         self.window_position = 0 if closing else self.window_position + 1
 
     def reset_window(self):
@@ -1527,27 +1362,19 @@ class Trainer:
         only).  None without accumulation."""
         if self._window_loss is None:
             return None
-        total = self._total_loss((self._window_loss[1] / self.accum_steps).tolist())
-        if self._window_integral is not None:
-            total += self._window_integral[1].item() / self.accum_steps
-        if self._window_structure is not None:
-            total += self._window_structure[1].item() / self.accum_steps
-        return total
+        return sum((t.window[1].item() / self.accum_steps for t in self.scalar_terms),
+                   self._total_loss((self._window_loss[1] / self.accum_steps).tolist()))
 
     def accum_state_dict(self):
         """The 'grad_accum' checkpoint entry: {'steps': N, 'position': k} and, inside a window (k > 0), the accumulation
-        arena and the open window's loss sum on the host (synchronises); with integral_l1_weight also 'integral_loss_sum',
-        the open window's sum of that term, and with structure_cos_weight 'structure_loss_sum'."""
+        arena and the open window's loss sum on the host (synchronises); with integral_l1_weight / structure_cos_weight also the
+        open window's sum of that term under the term's own key (head.ScalarTerm.key)."""
         sd = {'steps': self.accum_steps, 'position': self.window_position}
         if self.window_position > 0:
             sd['arena'] = self.accum.detach().cpu().clone()
             sd['loss_sum'] = self._window_loss[0].detach().cpu().clone()
-            wi = getattr(self, '_window_integral', None)      # (getattr: checkpoint code borrows this method for host objects)
-            if wi is not None:
-                sd['integral_loss_sum'] = wi[0].detach().cpu().clone()
-            wsum = getattr(self, '_window_structure', None)
-            if wsum is not None:
-                sd['structure_loss_sum'] = wsum[0].detach().cpu().clone()
+            for t in getattr(self, 'scalar_terms', ()):      # (getattr: checkpoint code borrows this method for host objects)
+                sd[t.key] = t.window[0].detach().cpu().clone()
         return sd
 
     def load_accum_state_dict(self, sd):
@@ -1561,16 +1388,10 @@ class Trainer:
         if k > 0:
             self.accum.copy_(sd['arena'])
             self._window_loss[0].copy_(sd['loss_sum'])
-            wi = getattr(self, '_window_integral', None)
-            if wi is not None:
-                if 'integral_loss_sum' not in sd:
-                    raise ValueError('the checkpoint was written inside a window without the integral L1 term')
-                wi[0].copy_(sd['integral_loss_sum'])
-            wsum = getattr(self, '_window_structure', None)
-            if wsum is not None:
-                if 'structure_loss_sum' not in sd:
-                    raise ValueError('the checkpoint was written inside a window without the structure cosine term')
-                wsum[0].copy_(sd['structure_loss_sum'])
+            for t in getattr(self, 'scalar_terms', ()):
+                if t.key not in sd:
+                    raise ValueError('the checkpoint was written inside a window without ' + t.without)
+                t.window[0].copy_(sd[t.key])
         self.window_position = k
 
     def _accum_eager_step(self, kf_x, sup_x, target, weight):
@@ -1770,10 +1591,7 @@ class Trainer:
         if not (kf_x.shape[0] == sup_x.shape[0] == target.shape[0] == weight.shape[0]):
             raise ValueError('batch sizes differ: kf %s sup %s target %s weight %s' %
                              (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape)))
-        if self.ohkm_topk is not None:
-            self._sel_key = (target.shape[0], target.shape[1])       # (a replay does not pass through _forward_backward)
-        if self.integral_l1_weight is not None or self.structure_cos_weight is not None:
-            self._int_key = (target.shape[0], target.shape[1])
+        self.head.shape = (target.shape[0], target.shape[1])       # (here: a replay does not pass through _forward_backward)
         if not self.use_graph:
             return self._eager_step(kf_x, sup_x, target, weight)
         key = (tuple(kf_x.shape), tuple(sup_x.shape), tuple(target.shape), tuple(weight.shape))
@@ -1814,7 +1632,7 @@ class Trainer:
 
     def loss_value(self):
         """Total loss of the last step (host float; forces a sync -- logging only)."""
-        return self._total_loss(self.loss_parts.tolist()) + self.integral_loss_value() + self.structure_loss_value()
+        return sum((t.value.item() for t in self.scalar_terms), self._total_loss(self.loss_parts.tolist()))
 
     def structure_loss_value(self):
         """The structure cosine term of the last step, weight included (host float; forces a sync -- logging only); 0.0 without
@@ -1840,3 +1658,11 @@ class Trainer:
         rows = self.acc.cpu().numpy().astype('float64')
         J = rows.shape[1] - 3
         return [(r[:J + 1].copy(), float(r[J + 1]), int(r[J + 2])) for r in rows]
+
+
+# the head's options (as it checked them) and its device results of the last step, read-only on the Trainer: loss_parts
+# [mse * W, mi_1..mi_6], integral_loss / structure_loss [1] (None without the term), acc [2, J+3] (PCK rows; None before a step)
+for _name in ('targets_from_joints', 'sigma', 'mse_weight', 'alpha', 'beta', 'use_mi', 'pck', 'subpixel', 'joint_weights', 'ohkm_topk',
+              'integral_l1_weight', 'structure_cos_weight', 'structure_pairs', 'structure_min_len', 'structure_eps', 'loss_parts',
+              'integral_loss', 'structure_loss', 'acc'):
+    setattr(Trainer, _name, property(lambda self, _name=_name: getattr(self.head, _name)))

@@ -202,11 +202,11 @@ def batch(dev, seed=9):
     return tuple(t.to(dev) for t in (kf, sup, joints, vis))
 
 
-def record_trainer(dev, key, graph=None, **kw):
+def record_trainer(dev, key, graph=None, cases=CASES, **kw):
     """-> ([(rows, marks) of the first two step() calls of a fresh Trainer], its last Engine's counters, which are the Trainer's
-    last_nfused); the environment of the case has been set by the caller"""
+    last_nfused); the environment of the case has been set by the caller.  cases: the table `key` is looked up in."""
     from fami_pose_amd.train import Trainer
-    mode, det, use_graph, _, opts = CASES[key]
+    mode, det, use_graph, _, opts = cases[key]
     fresh_case()
     m = model(dev, mode)
     if det:

@@ -35,7 +35,9 @@ CONFIGS = {
     10: (None, dict(ema_decay=0.5)),
 }
 NAMED = ('flat', 'grad', 'accum', 'ema', 'ema_state', 'overflow', 'clip', '_partials', 'scaler_state', '_group_flags',
-         'loss_parts', '_window_loss')
+         'loss_parts', '_window_loss', 'integral_loss', 'structure_loss')
+# (`acc` stays unnamed: the cases of tests/golden/engine_launches.json were recorded with it as an ordinal)
+HEAD_BUFFERS = ('sel_w', 'coords', 'stats', 'txy', 'gcoords', 'tw')      # per batch shape: `coords[2x17]`
 INSIDE = ('fami_adam_', 'fami_sgd_')
 
 
@@ -47,9 +49,26 @@ def _with_stream():
             if m.group(2).split(',')[-1].split()[:1] == ['fami_stream_t']}
 
 
+def _head_named(tr):
+    """[(symbol, tensor)] of the supervision head's private tensors, under one set of symbols on both kinds of tree: one whose
+    Trainer owns a head object (`tr.head`: joint weights, limb pairs, the scalar terms' window sums, one record of buffers per
+    batch shape), and the tree the head fixtures were recorded on, which keeps the same tensors on the Trainer itself"""
+    head = getattr(tr, 'head', None)
+    if head is not None:
+        named = [('_joint_w', head.joint_w), ('_pairs_dev', head.pairs_dev)] + [('_window_' + t.name, t.window) for t in head.terms]
+        for (B, J), r in head.bufs.items():
+            named += [('%s[%dx%d]' % (k, B, J), getattr(r, k)) for k in HEAD_BUFFERS]
+        return named
+    named = [(k, getattr(tr, k, None)) for k in ('_joint_w', '_pairs_dev', '_window_integral', '_window_structure')]
+    for attr, fields in (('_sel_w', ('sel_w',)), ('_int_bufs', ('coords', 'stats', 'txy')), ('_struct_bufs', ('gcoords', 'tw'))):
+        for (B, J), ts in getattr(tr, attr, {}).items():
+            named += [('%s[%dx%d]' % (k, B, J), t) for k, t in zip(fields, ts if isinstance(ts, tuple) else (ts,))]
+    return named
+
+
 def _spans(tr):
     """[(symbol, first byte, one past the last)] of the Trainer's named tensors, in lookup order"""
-    named = [(k, getattr(tr, k, None)) for k in NAMED]
+    named = [(k, getattr(tr, k, None)) for k in NAMED] + _head_named(tr)
     for i, o in enumerate(tr.optimizers):
         named += [('opt%d.%s' % (i, k), getattr(o, k, None)) for k in ('m', 'v', 'buf', 'state')]
     return [(k, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for k, t in named if torch.is_tensor(t)]

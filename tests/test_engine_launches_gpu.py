@@ -41,8 +41,8 @@ def _release_graphs():
         gc.collect()
 
 
-def _load():
-    with open(FIXTURE) as f:
+def _load(fixture=FIXTURE):
+    with open(fixture) as f:
         return json.load(f)
 
 
@@ -88,21 +88,22 @@ def _conditions(key, calls, counters):
                                   for r in last), key
 
 
-def _check(key, calls, counters, tmp_path):
-    """compare with the fixture's entry (or, recording, write it)"""
+def _check(key, calls, counters, tmp_path, fixture=FIXTURE, record_parent=None):
+    """compare with the entry of `fixture` (or, recording -- this module's RECORD_PARENT or the caller's -- write it)"""
     calls = json.loads(json.dumps(calls))
     assert len(calls) == 2 and calls[0][0], key
     _conditions(key, calls, counters)
     got = summary(calls, counters)
-    if RECORD_PARENT is not None:
-        data = _load() if os.path.isfile(FIXTURE) else {}
-        data['recorded_on_commit'] = RECORD_PARENT
+    record_parent = record_parent or RECORD_PARENT
+    if record_parent is not None:
+        data = _load(fixture) if os.path.isfile(fixture) else {}
+        data['recorded_on_commit'] = record_parent
         data.setdefault('cases', {})[key] = got
-        with open(FIXTURE, 'w') as f:
+        with open(fixture, 'w') as f:
             json.dump(data, f, indent=0, sort_keys=True)
             f.write('\n')
         return
-    want = _load()['cases'][key]
+    want = _load(fixture)['cases'][key]
     for k, (g, e) in enumerate(zip(got['calls'], want['calls'])):
         for j, (gb, eb) in enumerate(zip(g['blocks'], e['blocks'])):
             if gb != eb:

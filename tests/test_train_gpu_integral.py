@@ -27,7 +27,7 @@ def _record(monkeypatch):
 def test_default_trainer_launches_none_of_it(dev, monkeypatch):
     names = _record(monkeypatch)
     tr = _trainer(dev, False)
-    assert tr.integral_l1_weight is None and tr.integral_loss is None and tr.integral_coords() is None and not tr._int_bufs
+    assert tr.integral_l1_weight is None and tr.integral_loss is None and tr.integral_coords() is None and not tr.head.bufs
     tr.step(*_batch(dev))
     torch.cuda.synchronize(dev)
     assert names and not [n for n in names if 'softargmax' in n or 'integral' in n or 'heatmap_xy' in n]
@@ -150,7 +150,7 @@ def test_window_loss_includes_the_term(dev):
             assert sd['position'] == 1 and sd['integral_loss_sum'].item() == pytest.approx(terms[0], rel=1e-6)
     assert terms[0] > 0 and terms[0] != terms[1]
     assert tr.window_loss_value() == pytest.approx(sum(per_call) / 2, rel=1e-6)
-    assert tr._window_integral[1].item() == pytest.approx(sum(terms), rel=1e-6)
+    assert tr.head.integral.window[1].item() == pytest.approx(sum(terms), rel=1e-6)
     assert tr.loss_parts.numel() == 7 and tr._window_loss.shape == (2, 7)
     # without the option the checkpoint entry has no such key, inside a window too
     off = _trainer(dev, False, accum_steps=2)

@@ -29,11 +29,11 @@ def test_default_trainer_launches_none_of_it(dev, monkeypatch):
     names = _record(monkeypatch)
     tr = _trainer(dev, False)
     assert tr.structure_cos_weight is None and tr.structure_loss is None and tr.structure_cosines() is None
-    assert not tr._struct_bufs and not tr._int_bufs and tr._pairs_dev is None
+    assert not tr.head.bufs and tr.head.pairs_dev is None
     tr.step(*_batch(dev))
     torch.cuda.synchronize(dev)
     assert names and not [n for n in names if any(k in n for k in ('structure', 'softargmax', 'heatmap_xy'))]
-    assert tr.structure_loss_value() == 0.0 and tr.structure_cosines() is None and not tr._struct_bufs
+    assert tr.structure_loss_value() == 0.0 and tr.structure_cosines() is None and not tr.head.bufs
     # with the option: the three forward launches behind the heatmap loss, the two seed launches directly behind the MSE seed
     names.clear()
     tr = _trainer(dev, False, structure_cos_weight=WS)
@@ -177,7 +177,7 @@ def test_window_loss_includes_the_term(dev):
             assert 'integral_loss_sum' not in sd
     assert terms[0] > 0 and terms[0] != terms[1]
     assert tr.window_loss_value() == pytest.approx(sum(per_call) / 2, rel=1e-6)
-    assert tr._window_structure[1].item() == pytest.approx(sum(terms), rel=1e-6)
+    assert tr.head.structure.window[1].item() == pytest.approx(sum(terms), rel=1e-6)
     assert tr.loss_parts.numel() == 7 and tr._window_loss.shape == (2, 7)
     # without the option the checkpoint entry has no such key, inside a window too ...
     off = _trainer(dev, False, accum_steps=2)
@@ -188,7 +188,7 @@ def test_window_loss_includes_the_term(dev):
     with pytest.raises(ValueError, match='without the structure cosine term'):
         tr.load_accum_state_dict(sd_off)
     tr.load_accum_state_dict(sd)
-    assert tr.window_position == 1 and tr._window_structure[0].item() == pytest.approx(terms[0], rel=1e-6)
+    assert tr.window_position == 1 and tr.head.structure.window[0].item() == pytest.approx(terms[0], rel=1e-6)
 
 
 def test_ohkm_selection_is_unaffected_and_the_term_reads_the_target_weights(dev):

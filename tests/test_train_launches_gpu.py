@@ -39,23 +39,24 @@ def _release_graphs():
         gc.collect()
 
 
-def _load():
-    with open(FIXTURE) as f:
+def _load(fixture=FIXTURE):
+    with open(fixture) as f:
         return json.load(f)
 
 
-def _check(key, records):
-    """compare with the fixture's entry (or, recording, write it)"""
+def _check(key, records, fixture=FIXTURE, record_parent=None):
+    """compare with the entry of `fixture` (or, recording -- this module's RECORD_PARENT or the caller's -- write it)"""
     records = json.loads(json.dumps(records))
-    if RECORD_PARENT is not None:
-        data = _load() if os.path.isfile(FIXTURE) else {}
-        data['recorded_on_commit'] = RECORD_PARENT
+    record_parent = record_parent or RECORD_PARENT
+    if record_parent is not None:
+        data = _load(fixture) if os.path.isfile(fixture) else {}
+        data['recorded_on_commit'] = record_parent
         data.setdefault('cases', {})[key] = records
-        with open(FIXTURE, 'w') as f:
+        with open(fixture, 'w') as f:
             json.dump(data, f, indent=0, sort_keys=True)
             f.write('\n')
         return
-    want = _load()['cases'][key]
+    want = _load(fixture)['cases'][key]
     assert len(records) == len(want), key
     for k, (got, exp) in enumerate(zip(records, want)):
         for j, (g, e) in enumerate(zip(got, exp)):
