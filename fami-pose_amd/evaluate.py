@@ -74,6 +74,9 @@
   `pose_nms` keeps by the similarity `pose_nms` uses.  Box / segm IoU types, several categories, COCOeval's `scores` and
   `evalImgs` and COCO dataset indexing are out of scope.
 
+`_Words` is the one upload of all of these: a list of named fields -> ONE buffer of 4-byte words, pointers, views and the one
+download.
+
 Out of scope: motmetrics' other metrics (MT / ML, fragmentations), per-sequence metric files, motion models and
 appearance re-identification, the PoseTrack18 `images` / `annotations` file layout (poseval's convert.py) and PCKh
 (evaluatePCKh.py).
@@ -113,6 +116,112 @@ MOT_COUNTS = ('num_misses', 'num_switches', 'num_false_positives', 'num_detectio
 POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_knee', 'left_ankle', 'right_wrist',
                    'right_elbow', 'right_shoulder', 'left_shoulder', 'left_elbow', 'left_wrist', 'neck', 'nose',
                    'head_top']
+
+
+# ---------------------------------------------------------------------------------------- host plumbing of the set kernels
+class _Words:
+    """The ONE buffer of 4-byte words a set kernel's arrays travel in: declared as an ordered list of fields
+    (name, 'f32' | 'f64' | 'i32', shape[, host array or fill value]) -- zeros without the last --, laid out in that order with
+    every f64 field on an even word (8-byte aligned), and uploaded once.  `ptr` is a field's device address, `view` its
+    device-side tensor, `download` ONE copy to the host of everything from a field to the end.  The alignment rule holds for an
+    EMPTY f64 field too: behind an odd word count it still costs a padding word."""
+    TYPES = {'f32': (np.float32, torch.float32), 'f64': (np.float64, torch.float64), 'i32': (np.int32, torch.int32)}
+
+    def __init__(self, dev, fields):
+        self.fields, filled, words = {}, [], 0
+        for name, dt, shape, *init in fields:
+            shape = shape if isinstance(shape, tuple) else (int(shape),)
+            at = words + (words & 1 if dt == 'f64' else 0)
+            words = at + math.prod(shape) * (2 if dt == 'f64' else 1)
+            self.fields[name] = (at, words, dt, shape)
+            filled += [(name, init[0])] if init else []
+        buf = np.zeros(words, dtype=np.int32)
+        for name, init in filled:
+            at, to, dt, _ = self.fields[name]
+            buf[at:to].view(self.TYPES[dt][0])[:] = np.reshape(init, -1)
+        self.d = torch.from_numpy(buf).to(dev)
+
+    def ptr(self, name):
+        return self.d.data_ptr() + 4 * self.fields[name][0]
+
+    def view(self, name):
+        at, to, dt, shape = self.fields[name]
+        return self.d[at:to].view(self.TYPES[dt][1]).view(shape)
+
+    def download(self, first):
+        """-> {name: numpy array of the field's dtype and shape} for `first` and every field behind it (views of one array)"""
+        names = list(self.fields)
+        start = self.fields[first][0]
+        out = self.d[start:].cpu().numpy()
+        res = {}
+        for name in names[names.index(first):]:
+            at, to, dt, shape = self.fields[name]
+            res[name] = out[at - start:to - start].view(self.TYPES[dt][0]).reshape(shape)
+        return res
+
+
+def _hip_device(who, device):
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('%s runs on the HIP path only (device is %s)' % (who, dev))
+    return dev
+
+
+def _int_option(who, text, value, lo, hi, *names):
+    """ValueError '<who>: <text % names>, got <value>' unless `value` is an integer (no bool) in lo .. hi"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+        raise ValueError('%s: %s, got %r' % (who, text % names, value))
+
+
+def _sigmas(who, J, sigmas, holder, dtype):
+    """The per-joint OKS constants as a flat `dtype` array: default COCO_SIGMAS for J = 17, else J finite positive values
+    (judged after the rounding to `dtype`, which is what the kernel reads)."""
+    if sigmas is None:
+        if J != len(COCO_SIGMAS):
+            raise ValueError('%s: COCO_SIGMAS has %d joints, %s has %d: pass sigmas' % (who, len(COCO_SIGMAS), holder, J))
+        sigmas = COCO_SIGMAS
+    sig = np.asarray(sigmas, dtype=np.float64).reshape(-1).astype(dtype)
+    if sig.shape != (J,) or not np.isfinite(sig).all() or not (sig > 0).all():
+        raise ValueError('%s: sigmas must be %d finite positive values' % (who, J))
+    return sig
+
+
+def _pose_set(who, preds, boxes, sigmas):
+    """The pose set of `pose_nms` / `pose_track`: preds [N,J,3] and boxes [N,6] with J in range -> (preds, boxes, N, J, sigmas
+    fp32 [J])."""
+    preds, boxes = np.asarray(preds), np.asarray(boxes)
+    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
+        raise ValueError('%s expects preds [N,J,3] and boxes [N,6], got %s and %s' % (who, preds.shape, boxes.shape))
+    N, J = preds.shape[:2]
+    if not 1 <= J <= NMS_MAX_JOINTS:
+        raise ValueError('%s: J = %d joints, supported 1 .. %d' % (who, J, NMS_MAX_JOINTS))
+    return preds, boxes, N, J, _sigmas(who, J, sigmas, 'preds', np.float32)
+
+
+def _fp32(who, what, *arrays):
+    """`arrays` rounded to fp32 as they are uploaded (a value beyond fp32 becomes inf) -> list; ValueError if not finite then"""
+    with np.errstate(over='ignore'):
+        out = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    if not all(np.isfinite(a).all() for a in out):
+        raise ValueError('%s: %s must be finite (in fp32)' % (who, what))
+    return out
+
+
+def _index_range(who, N, J):
+    if N * J * 3 > 0x7fffffff:
+        raise ValueError('%s: N * J * 3 = %d exceeds 2^31 - 1' % (who, N * J * 3))
+
+
+def _ascends(seg, n):
+    """seg [groups + 1] ascends from 0 to n?"""
+    return len(seg) >= 2 and seg[0] == 0 and seg[-1] == n and not (np.diff(seg) < 0).any()
+
+
+def _first_over(counts_a, cap_a, counts_b, cap_b):
+    """-> the first group with more than cap_a of the one kind or more than cap_b of the other, None if there is none"""
+    if counts_a.max() > cap_a or counts_b.max() > cap_b:
+        return int(np.argmax((counts_a > cap_a) | (counts_b > cap_b)))
+    return None
 
 
 # ---------------------------------------------------------------------------------------- flip testing
@@ -413,66 +522,34 @@ def pose_nms(preds, boxes, filenames_map, in_vis_thre=0.0, oks_thre=0.5, soft=Fa
     fp64.  One upload, one launch, one download.  ValueError before any device work for: J != 17 without sigmas, J > 32,
     non-finite inputs, an image with more than 256 detections, a row index outside [0, N) or used twice, max_dets < 1,
     oks_thre <= 0 with soft=True."""
-    preds, boxes = np.asarray(preds), np.asarray(boxes)
-    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
-        raise ValueError('pose_nms expects preds [N,J,3] and boxes [N,6], got %s and %s' % (preds.shape, boxes.shape))
-    N, J = preds.shape[:2]
-    if not 1 <= J <= NMS_MAX_JOINTS:
-        raise ValueError('pose_nms: J = %d joints, supported 1 .. %d' % (J, NMS_MAX_JOINTS))
-    if sigmas is None:
-        if J != len(COCO_SIGMAS):
-            raise ValueError('pose_nms: COCO_SIGMAS has %d joints, preds has %d: pass sigmas' % (len(COCO_SIGMAS), J))
-        sigmas = COCO_SIGMAS
-    sig32 = np.asarray(sigmas, dtype=np.float64).reshape(-1).astype(np.float32)
-    if sig32.shape != (J,) or not np.isfinite(sig32).all() or not (sig32 > 0).all():
-        raise ValueError('pose_nms: sigmas must be %d finite positive values' % J)
-    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or max_dets < 1:
-        raise ValueError('pose_nms: max_dets must be an integer >= 1, got %r' % (max_dets,))
+    preds, boxes, N, J, sig32 = _pose_set('pose_nms', preds, boxes, sigmas)
+    _int_option('pose_nms', 'max_dets must be an integer >= 1', max_dets, 1, math.inf)
     in_vis_thre, oks_thre = float(in_vis_thre), float(oks_thre)
     vis = None if vis_thre is None else float(vis_thre)
     if not (np.isfinite(in_vis_thre) and np.isfinite(oks_thre) and (vis is None or np.isfinite(vis))):
         raise ValueError('pose_nms: thresholds must be finite')
     if soft and not oks_thre > 0:
         raise ValueError('pose_nms: soft mode divides by oks_thre, which must be > 0 (got %r)' % oks_thre)
-    with np.errstate(over='ignore'):
-        k32 = np.ascontiguousarray(preds, dtype=np.float32)
-        a32 = np.ascontiguousarray(boxes[:, 4], dtype=np.float32)
-        b32 = np.ascontiguousarray(boxes[:, 5], dtype=np.float32)
-    if not (np.isfinite(k32).all() and np.isfinite(a32).all() and np.isfinite(b32).all()):
-        raise ValueError('pose_nms: preds, box areas and box scores must be finite (in fp32)')
+    k32, a32, b32 = _fp32('pose_nms', 'preds, box areas and box scores', preds, boxes[:, 4], boxes[:, 5])
     index, seg = _nms_lists(filenames_map, N)
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('pose_nms runs on the HIP path only (device is %s)' % dev)
+    dev = _hip_device('pose_nms', device)
     M, n = len(seg) - 1, int(index.size)
     keys = list(filenames_map.keys())
     if N == 0 or M == 0:
         return np.zeros(N, dtype=np.float64), {k: [] for k in keys}
-    if N * J * 3 > 0x7fffffff:
-        raise ValueError('pose_nms: N * J * 3 = %d exceeds 2^31 - 1' % (N * J * 3))
-    # ONE buffer of 4-byte words: the six inputs, then the three outputs with their initial values (score 0 and rank -1
-    # for rows that no image lists) -- one upload; the tail comes back in one download
-    sizes = [N * J * 3, N, N, J, N, M + 1, N, N, M]
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    buf = np.zeros(int(off[-1]), dtype=np.int32)
-    fbuf = buf.view(np.float32)
-    fbuf[off[0]:off[1]] = k32.reshape(-1)
-    fbuf[off[1]:off[2]] = a32
-    fbuf[off[2]:off[3]] = b32
-    fbuf[off[3]:off[4]] = sig32
-    buf[off[4]:off[4] + n] = index
-    buf[off[5]:off[6]] = seg
-    buf[off[7]:off[8]] = -1
-    d = torch.from_numpy(buf).to(dev)
-    base = d.data_ptr()
-    p = [base + 4 * int(o) for o in off[:-1]]
+    _index_range('pose_nms', N, J)
+    # the six inputs (index holds n <= N rows, zeros behind them), then the three outputs with their initial values (score 0
+    # and rank -1 for rows that no image lists): the outputs come back in one download
+    w = _Words(dev, [('kpts', 'f32', (N, J, 3), k32), ('area', 'f32', N, a32), ('box_score', 'f32', N, b32),
+                     ('sigmas', 'f32', J, sig32), ('index', 'i32', N, np.pad(index, (0, N - n))), ('seg', 'i32', M + 1, seg),
+                     ('score', 'f32', N), ('rank', 'i32', N, -1), ('kept', 'i32', M)])
     with torch.cuda.device(dev):
-        lib().call('fami_pose_nms_f32', p[0], p[1], p[2], p[3], p[4], p[5], N, J, M, in_vis_thre, oks_thre,
-                   1 if soft else 0, int(max_dets), 0.0 if vis is None else vis, 0 if vis is None else 1, p[6], p[7], p[8],
+        lib().call('fami_pose_nms_f32', w.ptr('kpts'), w.ptr('area'), w.ptr('box_score'), w.ptr('sigmas'), w.ptr('index'),
+                   w.ptr('seg'), N, J, M, in_vis_thre, oks_thre, 1 if soft else 0, int(max_dets), 0.0 if vis is None else vis,
+                   0 if vis is None else 1, w.ptr('score'), w.ptr('rank'), w.ptr('kept'),
                    torch.cuda.current_stream(dev).cuda_stream)
-    out = d[int(off[6]):].cpu().numpy()
-    scores = out[:N].view(np.float32).astype(np.float64)
-    rank, kept = out[N:2 * N], out[2 * N:]
+    out = w.download('score')
+    scores, rank, kept = out['score'].astype(np.float64), out['rank'], out['kept']
     if (kept < 0).any():
         raise RuntimeError('pose_nms: the kernel refused image %r' % (keys[int(np.argmax(kept < 0))],))
     # the kept rows of all images, ordered by (image, rank), then cut at the per-image counts
@@ -511,8 +588,7 @@ def _track_tables(filenames_map, N, frame_of=None):
         if not isinstance(where, tuple) or len(where) != 2:
             raise ValueError('pose_track: frame_of(%r) must return (video, frame_number), got %r' % (key, where))
         video, f = where
-        if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, np.integer)) or not -2 ** 31 <= f < 2 ** 31:
-            raise ValueError('pose_track: the frame number of %r must be an integer that fits int32, got %r' % (key, f))
+        _int_option('pose_track', 'the frame number of %r must be an integer that fits int32', f, -2 ** 31, 2 ** 31 - 1, key)
         if (video, int(f)) in seen:
             raise ValueError('pose_track: %r and %r are both frame %d of video %r' % (seen[(video, int(f))], key, f, video))
         seen[(video, int(f))] = key
@@ -556,59 +632,30 @@ def pose_track(preds, boxes, filenames_map, oks_thre=0.3, max_gap=3, vis_thre=No
     max_gap no integer >= 1, a key frame_of cannot place, two keys with the same (video, frame number), a frame with more
     than 256 rows, a row outside [0, N) or listed twice.  ValueError naming the video after the download if it had more
     than 256 live tracks at once (the other videos of the call are computed as if alone, but nothing is returned)."""
-    preds, boxes = np.asarray(preds), np.asarray(boxes)
-    if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
-        raise ValueError('pose_track expects preds [N,J,3] and boxes [N,6], got %s and %s' % (preds.shape, boxes.shape))
-    N, J = preds.shape[:2]
-    if not 1 <= J <= NMS_MAX_JOINTS:
-        raise ValueError('pose_track: J = %d joints, supported 1 .. %d' % (J, NMS_MAX_JOINTS))
-    if sigmas is None:
-        if J != len(COCO_SIGMAS):
-            raise ValueError('pose_track: COCO_SIGMAS has %d joints, preds has %d: pass sigmas' % (len(COCO_SIGMAS), J))
-        sigmas = COCO_SIGMAS
-    sig32 = np.asarray(sigmas, dtype=np.float64).reshape(-1).astype(np.float32)
-    if sig32.shape != (J,) or not np.isfinite(sig32).all() or not (sig32 > 0).all():
-        raise ValueError('pose_track: sigmas must be %d finite positive values' % J)
-    if isinstance(max_gap, (bool, np.bool_)) or not isinstance(max_gap, (int, np.integer)) or not 1 <= max_gap < 2 ** 31:
-        raise ValueError('pose_track: max_gap must be an integer >= 1, got %r' % (max_gap,))
+    preds, boxes, N, J, sig32 = _pose_set('pose_track', preds, boxes, sigmas)
+    _int_option('pose_track', 'max_gap must be an integer >= 1', max_gap, 1, 2 ** 31 - 1)
     oks_thre = float(oks_thre)
     vis = None if vis_thre is None else float(vis_thre)
     if not (np.isfinite(oks_thre) and (vis is None or np.isfinite(vis))):
         raise ValueError('pose_track: thresholds must be finite')
-    with np.errstate(over='ignore'):
-        k32 = np.ascontiguousarray(preds, dtype=np.float32)
-        a32 = np.ascontiguousarray(boxes[:, 4], dtype=np.float32)
-    if not (np.isfinite(k32).all() and np.isfinite(a32).all()):
-        raise ValueError('pose_track: preds and box areas must be finite (in fp32)')
+    k32, a32 = _fp32('pose_track', 'preds and box areas', preds, boxes[:, 4])
     index, fseg, fnum, vseg, videos = _track_tables(filenames_map, N, frame_of)
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('pose_track runs on the HIP path only (device is %s)' % dev)
+    dev = _hip_device('pose_track', device)
     M, V, n = len(fnum), len(videos), int(index.size)
     if N == 0 or M == 0:
         return np.full(N, -1, dtype=np.int32), {}
-    if N * J * 3 > 0x7fffffff:
-        raise ValueError('pose_track: N * J * 3 = %d exceeds 2^31 - 1' % (N * J * 3))
-    # ONE buffer of 4-byte words: the seven inputs, then the two outputs (track pre-filled with -1 for the rows that no
-    # image lists) -- one upload; the tail comes back in one download
-    sizes = [N * J * 3, N, J, n, M + 1, M, V + 1, N, V]
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    buf = np.zeros(int(off[-1]), dtype=np.int32)
-    fbuf = buf.view(np.float32)
-    fbuf[off[0]:off[1]] = k32.reshape(-1)
-    fbuf[off[1]:off[2]] = a32
-    fbuf[off[2]:off[3]] = sig32
-    for k, a in zip(range(3, 7), (index, fseg, fnum, vseg)):
-        buf[off[k]:off[k + 1]] = a
-    buf[off[7]:off[8]] = -1
-    d = torch.from_numpy(buf).to(dev)
-    base = d.data_ptr()
-    p = [base + 4 * int(o) for o in off[:-1]]
+    _index_range('pose_track', N, J)
+    # the seven inputs, then the two outputs (track pre-filled with -1 for the rows that no image lists), which come back in
+    # one download
+    w = _Words(dev, [('kpts', 'f32', (N, J, 3), k32), ('area', 'f32', N, a32), ('sigmas', 'f32', J, sig32),
+                     ('index', 'i32', n, index), ('fseg', 'i32', M + 1, fseg), ('fnum', 'i32', M, fnum),
+                     ('vseg', 'i32', V + 1, vseg), ('track', 'i32', N, -1), ('ntracks', 'i32', V)])
     with torch.cuda.device(dev):
-        lib().call('fami_pose_track_f32', p[0], p[1], p[2], p[3], p[4], p[5], p[6], N, J, n, M, V, oks_thre, int(max_gap),
-                   0.0 if vis is None else vis, 0 if vis is None else 1, p[7], p[8], torch.cuda.current_stream(dev).cuda_stream)
-    out = d[int(off[7]):].cpu().numpy()
-    tracks, count = out[:N].copy(), out[N:]
+        lib().call('fami_pose_track_f32', w.ptr('kpts'), w.ptr('area'), w.ptr('sigmas'), w.ptr('index'), w.ptr('fseg'),
+                   w.ptr('fnum'), w.ptr('vseg'), N, J, n, M, V, oks_thre, int(max_gap), 0.0 if vis is None else vis,
+                   0 if vis is None else 1, w.ptr('track'), w.ptr('ntracks'), torch.cuda.current_stream(dev).cuda_stream)
+    out = w.download('track')
+    tracks, count = out['track'].copy(), out['ntracks']
     if (count < 0).any():
         raise ValueError('pose_track: video %r has more than %d live tracks at once (the limit of one workgroup)'
                          % (videos[int(np.argmax(count < 0))], NMS_MAX_PER_IMAGE))
@@ -988,14 +1035,14 @@ def _posetrack_check(who, frames, dist_thresh, device, ap, mot):
         raise ValueError('%s: dist_thresh must be finite' % who)
     if ap and P > AP_MAX_SET:
         raise ValueError('%s: %d predicted poses, the limit is %d per set' % (who, P, AP_MAX_SET))
-    counts = np.diff(frames['pr_seg']), np.diff(frames['gt_seg'])
-    if counts[0].max() > AP_MAX_PRED or counts[1].max() > AP_MAX_GT:
-        m = int(np.argmax((counts[0] > AP_MAX_PRED) | (counts[1] > AP_MAX_GT)))
+    n_pr, n_gt = np.diff(frames['pr_seg']), np.diff(frames['gt_seg'])
+    m = _first_over(n_pr, AP_MAX_PRED, n_gt, AP_MAX_GT)
+    if m is not None:
         raise ValueError('%s: kept frame %d has %d predicted and %d annotated poses, the limits are %d and %d'
-                         % (who, m, counts[0][m], counts[1][m], AP_MAX_PRED, AP_MAX_GT))
+                         % (who, m, n_pr[m], n_gt[m], AP_MAX_PRED, AP_MAX_GT))
     if mot:
-        seg, gt_track, pr_track = frames['seq_seg'], frames['gt_track'], frames['pr_track']
-        if len(seg) < 2 or seg[0] != 0 or seg[-1] != F or (np.diff(seg) < 0).any():
+        gt_track, pr_track = frames['gt_track'], frames['pr_track']
+        if not _ascends(frames['seq_seg'], F):
             raise ValueError('%s: seq_seg must ascend from 0 to the %d kept frames' % (who, F))
         if len(gt_track) != G or len(pr_track) != P:
             raise ValueError('%s: gt_track / pr_track must have one entry per pose' % who)
@@ -1003,10 +1050,7 @@ def _posetrack_check(who, frames, dist_thresh, device, ap, mot):
             raise ValueError('%s: annotated track ids must be in 0 .. %d (renumbered per sequence)' % (who, MOT_MAX_TRACKS - 1))
         if P and pr_track.min() < 0:
             raise ValueError('%s: predicted track ids must be >= 0' % who)
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('%s runs on the HIP path only (device is %s)' % (who, dev))
-    return dist_thresh, dev
+    return dist_thresh, _hip_device(who, device)
 
 
 def _posetrack_run(who, frames, dist_thresh, dev, ap, mot):
@@ -1015,40 +1059,32 @@ def _posetrack_run(who, frames, dist_thresh, dev, ap, mot):
     F, P, G = len(frames['pr_seg']) - 1, len(frames['pr_has']), len(frames['gt_has'])
     NP, NV = len(frames['vert_seg']) - 1, len(frames['verts'])
     S = len(frames['seq_seg']) - 1 if mot else 0
-    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), the int inputs, the int outputs, [the MOT step's
-    # int inputs and outputs,] then (on an even word) ap / pre / rec [and the MOT step's fp64 outputs] -- one upload;
-    # everything from the first output on comes back in one download
-    f64 = [frames[k] for k in ('pr_xys', 'gt_xy', 'gt_head', 'verts')]
-    i32 = [frames[k] for k in ('pr_has', 'gt_has', 'pr_seg', 'gt_seg', 'poly_seg', 'vert_seg')]
-    sizes = [2 * a.size for a in f64] + [a.size for a in i32] + [P, G, P, P, F * AP_JOINTS, AP_JOINTS]
+    # the fp64 inputs, the int inputs, the int outputs, [the MOT step's int inputs and outputs,] then ap / pre / rec [and the MOT
+    # step's fp64 outputs]; everything from the first output on comes back in one download
+    fields = [(k, 'f64', frames[k].shape, frames[k]) for k in ('pr_xys', 'gt_xy', 'gt_head', 'verts')]
+    fields += [(k, 'i32', frames[k].shape, frames[k]) for k in ('pr_has', 'gt_has', 'pr_seg', 'gt_seg', 'poly_seg', 'vert_seg')]
+    fields += [('pr_has_out', 'i32', P), ('gt_has_out', 'i32', G), ('label', 'i32', P), ('assigned', 'i32', P),
+               ('ngt_frame', 'i32', (F, AP_JOINTS)), ('ngt', 'i32', AP_JOINTS)]
     if mot:
-        sizes += [P, G, S + 1, S * AP_JOINTS * 5, S, AP_JOINTS * 5]
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    tail = int(off[-1] + (off[-1] & 1))
-    n_res = 3 * (AP_JOINTS + 1)
-    buf = np.zeros(tail + 2 * (n_res + ((S + 1) * AP_JOINTS + 4 * (AP_JOINTS + 1) if mot else 0)), dtype=np.int32)
-    for a, o in zip(f64, off):
-        buf[o:o + 2 * a.size] = np.ascontiguousarray(a, dtype=np.float64).reshape(-1).view(np.int32)
-    for a, o in zip(i32, off[4:]):
-        buf[o:o + a.size] = a
+        fields += [(k, 'i32', frames[k].shape, frames[k]) for k in ('pr_track', 'gt_track', 'seq_seg')]
+        fields += [('counts', 'i32', (S, AP_JOINTS, 5)), ('status', 'i32', S), ('totals', 'i32', (AP_JOINTS, 5))]
+    fields += [('res', 'f64', (3, AP_JOINTS + 1))]
     if mot:
-        for k, o in zip(('pr_track', 'gt_track', 'seq_seg'), off[16:]):
-            buf[o:o + frames[k].size] = frames[k]
-    d = torch.from_numpy(buf).to(dev)
-    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]]
-    p_res = d.data_ptr() + 4 * tail
-    p_sumd = p_res + 8 * n_res
+        fields += [('sumd', 'f64', (S, AP_JOINTS)), ('sumd_tot', 'f64', AP_JOINTS), ('table', 'f64', (4, AP_JOINTS + 1))]
+    w = _Words(dev, fields)
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev).cuda_stream
-        lib().call('fami_posetrack_assign_f64', p[0], p[4], p[1], p[5], p[2], p[6], p[7], p[8], p[9], p[3], P, G, F, NP, NV,
-                   dist_thresh, p[10], p[11], p[12], p[13], p[14], s)
+        lib().call('fami_posetrack_assign_f64', w.ptr('pr_xys'), w.ptr('pr_has'), w.ptr('gt_xy'), w.ptr('gt_has'),
+                   w.ptr('gt_head'), w.ptr('pr_seg'), w.ptr('gt_seg'), w.ptr('poly_seg'), w.ptr('vert_seg'), w.ptr('verts'),
+                   P, G, F, NP, NV, dist_thresh, w.ptr('pr_has_out'), w.ptr('gt_has_out'), w.ptr('label'), w.ptr('assigned'),
+                   w.ptr('ngt_frame'), s)
         if ap:
             # plumbing between the two kernels: per joint, the predictions that still have it, by descending score
             if P:
                 bits = torch.arange(AP_JOINTS, dtype=torch.int32, device=dev)[:, None]
-                has_out, label = d[int(off[10]):int(off[10]) + P], d[int(off[12]):int(off[12]) + P]
+                has_out, label = w.view('pr_has_out'), w.view('label')
                 present = ((has_out[None, :] >> bits) & 1).bool()
-                score = d[:2 * P * AP_JOINTS * 3].view(torch.float64).view(P, AP_JOINTS, 3)[:, :, 2].t()
+                score = w.view('pr_xys').view(P, AP_JOINTS, 3)[:, :, 2].t()
                 order = torch.sort(torch.where(present, score, score.new_tensor(float('-inf'))), dim=1, descending=True,
                                    stable=True).indices
                 lab = ((label[order] >> bits) & 1).to(torch.uint8).contiguous()
@@ -1056,30 +1092,26 @@ def _posetrack_run(who, frames, dist_thresh, dev, ap, mot):
             else:                                                        # annotated poses only: 15 empty lists
                 lab = torch.zeros(AP_JOINTS, dtype=torch.uint8, device=dev)
                 n_valid = torch.zeros(AP_JOINTS, dtype=torch.int32, device=dev)
-            lib().call('fami_posetrack_curve_f64', lab.data_ptr(), n_valid.data_ptr(), p[14], P, F, p_res, p[15], s)
+            lib().call('fami_posetrack_curve_f64', lab.data_ptr(), n_valid.data_ptr(), w.ptr('ngt_frame'), P, F, w.ptr('res'),
+                       w.ptr('ngt'), s)
         if mot:
             # on the masks the assign launch wrote: the ignore filter runs once, and MOTA and AP see the same points
-            lib().call('fami_posetrack_mot_f64', p[0], p[10], p[1], p[11], p[2], p[6], p[7], p[8], p[16], p[17], p[18], P, G, F,
-                       S, dist_thresh, p[19], p_sumd, p[20], s)
-            lib().call('fami_posetrack_mot_final_f64', p[19], p_sumd, p[20], S, p[21], p_sumd + 8 * S * AP_JOINTS,
-                       p_sumd + 8 * (S + 1) * AP_JOINTS, s)
-    out = d[int(off[10]):].cpu().numpy()
-    o = [int(x - off[10]) for x in off[10:]]
-    raw = dict(zip(('pr_has', 'gt_has', 'label', 'assigned'), (out[o[i]:o[i + 1]].copy() for i in range(4))))
-    ngt_frame, raw['ngt'] = out[o[4]:o[5]].reshape(F, AP_JOINTS), out[o[5]:o[6]].copy()
-    if (ngt_frame < 0).any():
-        raise RuntimeError('%s: the kernel refused kept frame %d' % (who, int(np.argmax((ngt_frame < 0).any(1)))))
-    dbl = out[tail - int(off[10]):].view(np.float64)
-    raw['res'] = dbl[:n_res].reshape(3, AP_JOINTS + 1)
+            lib().call('fami_posetrack_mot_f64', w.ptr('pr_xys'), w.ptr('pr_has_out'), w.ptr('gt_xy'), w.ptr('gt_has_out'),
+                       w.ptr('gt_head'), w.ptr('pr_seg'), w.ptr('gt_seg'), w.ptr('poly_seg'), w.ptr('pr_track'),
+                       w.ptr('gt_track'), w.ptr('seq_seg'), P, G, F, S, dist_thresh, w.ptr('counts'), w.ptr('sumd'),
+                       w.ptr('status'), s)
+            lib().call('fami_posetrack_mot_final_f64', w.ptr('counts'), w.ptr('sumd'), w.ptr('status'), S, w.ptr('totals'),
+                       w.ptr('sumd_tot'), w.ptr('table'), s)
+    out = w.download('pr_has_out')
+    if (out['ngt_frame'] < 0).any():
+        raise RuntimeError('%s: the kernel refused kept frame %d' % (who, int(np.argmax((out['ngt_frame'] < 0).any(1)))))
+    if mot and out['status'].any():
+        raise RuntimeError('%s: the kernel refused sequence %d' % (who, int(np.argmax(out['status'] != 0))))
+    taken = ('pr_has_out', 'gt_has_out', 'label', 'assigned', 'ngt', 'res')
     if mot:
-        raw['counts'] = out[o[9]:o[10]].reshape(S, AP_JOINTS, 5).copy()
-        status = out[o[10]:o[11]]
-        if status.any():
-            raise RuntimeError('%s: the kernel refused sequence %d' % (who, int(np.argmax(status != 0))))
-        raw['totals'] = out[o[11]:o[12]].reshape(AP_JOINTS, 5).copy()
-        m = dbl[n_res:]
-        raw['sumd'], raw['sumd_tot'] = m[:S * AP_JOINTS].reshape(S, AP_JOINTS).copy(), m[S * AP_JOINTS:(S + 1) * AP_JOINTS].copy()
-        raw['table'] = m[(S + 1) * AP_JOINTS:].reshape(4, AP_JOINTS + 1).copy()
+        taken += ('counts', 'totals', 'sumd', 'sumd_tot', 'table')
+    raw = {k: out[k].copy() for k in taken}                                 # (copies: nothing returned holds the download)
+    raw['pr_has'], raw['gt_has'] = raw.pop('pr_has_out'), raw.pop('gt_has_out')
     return raw
 
 
@@ -1295,15 +1327,8 @@ def _coco_summarize(precision, recall, iou_thrs):
 
 def _coco_thresholds(J, max_dets, sigmas, iou_thrs, rec_thrs, area_rngs):
     who = 'coco_keypoint_ap'
-    if isinstance(max_dets, (bool, np.bool_)) or not isinstance(max_dets, (int, np.integer)) or not 1 <= max_dets <= COCO_MAX_KEPT:
-        raise ValueError('%s: max_dets must be an integer in 1 .. %d, got %r' % (who, COCO_MAX_KEPT, max_dets))
-    if sigmas is None:
-        if J != len(COCO_SIGMAS):
-            raise ValueError('%s: COCO_SIGMAS has %d joints, the set has %d: pass sigmas' % (who, len(COCO_SIGMAS), J))
-        sigmas = COCO_SIGMAS
-    sig = np.asarray(sigmas, dtype=np.float64).reshape(-1)
-    if sig.shape != (J,) or not np.isfinite(sig).all() or not (sig > 0).all():
-        raise ValueError('%s: sigmas must be %d finite positive values' % (who, J))
+    _int_option(who, 'max_dets must be an integer in 1 .. %d' % COCO_MAX_KEPT, max_dets, 1, COCO_MAX_KEPT)
+    sig = _sigmas(who, J, sigmas, 'the set', np.float64)
     iou = np.ascontiguousarray(COCO_IOU_THRS if iou_thrs is None else iou_thrs, dtype=np.float64).reshape(-1)
     rec = np.ascontiguousarray(COCO_REC_THRS if rec_thrs is None else rec_thrs, dtype=np.float64).reshape(-1)
     rng = np.ascontiguousarray(COCO_AREA_RNGS if area_rngs is None else area_rngs, dtype=np.float64)
@@ -1312,6 +1337,11 @@ def _coco_thresholds(J, max_dets, sigmas, iou_thrs, rec_thrs, area_rngs):
     if not (np.isfinite(iou).all() and np.isfinite(rec).all() and np.isfinite(rng).all()):
         raise ValueError('%s: thresholds must be finite' % who)
     return int(max_dets), np.ascontiguousarray((sig * 2) ** 2), iou, rec, rng
+
+
+def _coco_result(precision, recall, iou, num_kept):
+    return {'stats': _coco_summarize(precision, recall, iou), 'names': list(COCO_STAT_NAMES), 'precision': precision,
+            'recall': recall, 'num_kept': num_kept}
 
 
 def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None, rec_thrs=None, area_rngs=None, device='cuda'):
@@ -1338,14 +1368,12 @@ def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None,
     gt_seg, dt_seg = np.asarray(packed['gt_seg'], dtype=np.int32), np.asarray(packed['dt_seg'], dtype=np.int32)
     M, G, D = len(gt_seg) - 1, len(packed['gt_flags']), len(packed['dt_score'])
     if M <= 0 or G + D == 0:
-        precision, recall = -np.ones((T, R, A)), -np.ones((T, A))
-        return {'stats': _coco_summarize(precision, recall, iou), 'names': list(COCO_STAT_NAMES), 'precision': precision,
-                'recall': recall, 'num_kept': 0}
-    n_gt, n_dt = np.diff(gt_seg), np.diff(dt_seg)
-    if len(dt_seg) != M + 1 or gt_seg[0] != 0 or dt_seg[0] != 0 or gt_seg[-1] != G or dt_seg[-1] != D or n_gt.min() < 0 or n_dt.min() < 0:
+        return _coco_result(-np.ones((T, R, A)), -np.ones((T, A)), iou, 0)
+    if len(dt_seg) != M + 1 or not _ascends(gt_seg, G) or not _ascends(dt_seg, D):
         raise ValueError('coco_keypoint_ap: gt_seg / dt_seg must ascend from 0 to the %d annotations / %d detections' % (G, D))
-    if n_gt.max() > COCO_MAX_GT or n_dt.max() > COCO_MAX_PER_IMAGE:
-        m = int(np.argmax((n_gt > COCO_MAX_GT) | (n_dt > COCO_MAX_PER_IMAGE)))
+    n_gt, n_dt = np.diff(gt_seg), np.diff(dt_seg)
+    m = _first_over(n_gt, COCO_MAX_GT, n_dt, COCO_MAX_PER_IMAGE)
+    if m is not None:
         raise ValueError('coco_keypoint_ap: image %d has %d annotations and %d detections, the limits are %d and %d'
                          % (m, n_gt[m], n_dt[m], COCO_MAX_GT, COCO_MAX_PER_IMAGE))
     kept = np.minimum(n_dt, K)
@@ -1354,29 +1382,22 @@ def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None,
         raise ValueError('coco_keypoint_ap: %d detections after the cut, the limit is %d per set' % (N, COCO_MAX_SET))
     if M * K * A * T > 0x7fffffff or max(G, D) * J * 3 > 0x7fffffff:
         raise ValueError('coco_keypoint_ap: the set is too large for 32-bit indices')
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('coco_keypoint_ap runs on the HIP path only (device is %s)' % dev)
+    dev = _hip_device('coco_keypoint_ap', device)
     # the kept slots of every image, as the match launch lays them out: m * K + k for k < min(detections of m, K)
     first = np.concatenate([[0], np.cumsum(kept)[:-1]])
     slots = (np.repeat(np.arange(M, dtype=np.int64) * K - first, kept) + np.arange(N, dtype=np.int64)).astype(np.int32)
-    # ONE buffer of 4-byte words: the fp64 inputs first (8-byte aligned), then the int inputs -- one upload
-    f64 = [np.ascontiguousarray(packed[k], dtype=np.float64).reshape(-1)
-           for k in ('gt_kpts', 'gt_area', 'gt_bbox', 'dt_kpts', 'dt_score', 'dt_area')]
-    i32 = [np.ascontiguousarray(packed['gt_flags'], dtype=np.int32).reshape(-1), gt_seg, dt_seg, slots]
-    if [a.size for a in f64] != [G * J * 3, G, G * 4, D * J * 3, D, D]:
+    f64 = {k: np.ascontiguousarray(packed[k], dtype=np.float64).reshape(-1)
+           for k in ('gt_kpts', 'gt_area', 'gt_bbox', 'dt_kpts', 'dt_score', 'dt_area')}
+    gt_flags = np.ascontiguousarray(packed['gt_flags'], dtype=np.int32).reshape(-1)
+    if [a.size for a in f64.values()] != [G * J * 3, G, G * 4, D * J * 3, D, D]:
         raise ValueError('coco_keypoint_ap: the packed arrays do not fit %d annotations and %d detections of %d joints' % (G, D, J))
-    if not all(np.isfinite(a).all() for a in f64):
+    if not all(np.isfinite(a).all() for a in f64.values()):
         raise ValueError('coco_keypoint_ap: the packed arrays must be finite')
-    sizes = [2 * a.size for a in f64] + [a.size for a in i32]
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    buf = np.zeros(int(off[-1]) + 2, dtype=np.int32)
-    for a, o in zip(f64, off):
-        buf[o:o + 2 * a.size] = a.view(np.int32)
-    for a, o in zip(i32, off[6:]):
-        buf[o:o + a.size] = a
-    d = torch.from_numpy(buf).to(dev)
-    p = [d.data_ptr() + 4 * int(o) for o in off[:-1]]
+    # the fp64 inputs, then the int inputs: inputs only (the outputs are torch.empty tensors of their own: in here they would be
+    # megabytes of uploaded zeros).  Two spare words have always followed `slots`; the pinned buffer length keeps them.
+    w = _Words(dev, [(k, 'f64', a.size, a) for k, a in f64.items()] +
+               [('gt_flags', 'i32', gt_flags.size, gt_flags), ('gt_seg', 'i32', M + 1, gt_seg), ('dt_seg', 'i32', M + 1, dt_seg),
+                ('slots', 'i32', N, slots), ('spare', 'i32', 2)])
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev).cuda_stream
         out_score = torch.empty(M * K, dtype=torch.float64, device=dev)
@@ -1384,11 +1405,12 @@ def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None,
         out_flags = torch.empty(M * K, A * T, dtype=torch.uint8, device=dev)
         npig = torch.empty(M * A, dtype=torch.int32, device=dev)
         res = torch.empty(T * R * A + T * A + 1, dtype=torch.float64, device=dev)
-        lib().call('fami_coco_kpt_match_f64', p[0], p[1], p[2], p[6], p[3], p[4], p[5], p[7], p[8], var.ctypes.data,
+        lib().call('fami_coco_kpt_match_f64', w.ptr('gt_kpts'), w.ptr('gt_area'), w.ptr('gt_bbox'), w.ptr('gt_flags'),
+                   w.ptr('dt_kpts'), w.ptr('dt_score'), w.ptr('dt_area'), w.ptr('gt_seg'), w.ptr('dt_seg'), var.ctypes.data,
                    iou.ctypes.data, rng.ctypes.data, G, D, M, J, T, A, K, out_score.data_ptr(), out_row.data_ptr(),
                    out_flags.data_ptr(), npig.data_ptr(), s)
         # plumbing between the two kernels: the kept detections of the whole set by descending score, images in order
-        slot = d[int(off[9]):int(off[9]) + N].long()
+        slot = w.view('slots').long()
         order = torch.sort(out_score[slot], descending=True, stable=True).indices
         flags = out_flags[slot[order]].t().contiguous()
         lib().call('fami_coco_kpt_curve_f64', flags.data_ptr() if N else None, npig.data_ptr(), rec.ctypes.data, N, M, T, A, R,
@@ -1397,9 +1419,7 @@ def coco_keypoint_ap(packed, max_dets=COCO_MAX_DETS, sigmas=None, iou_thrs=None,
     out = res.cpu().numpy()
     if out[-1] < 0:
         raise RuntimeError('coco_keypoint_ap: the kernel refused an image')
-    precision, recall = out[:T * R * A].reshape(T, R, A).copy(), out[T * R * A:T * R * A + T * A].reshape(T, A).copy()
-    return {'stats': _coco_summarize(precision, recall, iou), 'names': list(COCO_STAT_NAMES), 'precision': precision,
-            'recall': recall, 'num_kept': N}
+    return _coco_result(out[:T * R * A].reshape(T, R, A).copy(), out[T * R * A:T * R * A + T * A].reshape(T, A).copy(), iou, N)
 
 
 def load_coco_keypoints(gt_json, dt_json):
