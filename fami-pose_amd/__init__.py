@@ -18,7 +18,8 @@ from .config import CfgNode, default_cfg
 from .zoo import (MODEL_REGISTRY, CORE_FUNCTION_REGISTRY, DATASET_REGISTRY, TRAIN_PHASE, VAL_PHASE, TEST_PHASE,
                   build_model, get_model_hyperparameter, Alignment_V15, HRNet, HRNetPlus)
 from .train import freeze_batchnorm
-from .evaluate import (COCO_SIGMAS, pose_nms, pose_nms_options, pose_track, pack_posetrack_frames, load_posetrack_dirs, posetrack_ap,
+from .evaluate import (COCO_SIGMAS, pose_nms, pose_nms_options, pose_track, track_refine, pack_posetrack_frames,
+                       load_posetrack_dirs, posetrack_ap,
                        evaluate_posetrack_ap, posetrack_mota, evaluate_posetrack_mota, evaluate_posetrack,
                        pack_coco_keypoints, coco_keypoint_ap, load_coco_keypoints, evaluate_coco_keypoints,
                        coco_keypoint_results)
@@ -26,9 +27,8 @@ from .data import draw_degradation, check_degradation, DEGRADE_DEFAULTS
 
 __all__ = ['CfgNode', 'default_cfg', 'MODEL_REGISTRY', 'CORE_FUNCTION_REGISTRY', 'DATASET_REGISTRY', 'TRAIN_PHASE',
            'VAL_PHASE', 'TEST_PHASE', 'build_model', 'get_model_hyperparameter', 'Alignment_V15', 'HRNet',
-           'HRNetPlus', 'freeze_batchnorm', 'COCO_SIGMAS', 'pose_nms', 'pose_nms_options', 'pose_track',
-           'pack_posetrack_frames',
-           'load_posetrack_dirs', 'posetrack_ap', 'evaluate_posetrack_ap', 'posetrack_mota',
+           'HRNetPlus', 'freeze_batchnorm', 'COCO_SIGMAS', 'pose_nms', 'pose_nms_options', 'pose_track', 'track_refine',
+           'pack_posetrack_frames', 'load_posetrack_dirs', 'posetrack_ap', 'evaluate_posetrack_ap', 'posetrack_mota',
            'evaluate_posetrack_mota', 'evaluate_posetrack', 'pack_coco_keypoints', 'coco_keypoint_ap',
            'load_coco_keypoints', 'evaluate_coco_keypoints', 'coco_keypoint_results', 'draw_degradation',
            'check_degradation', 'DEGRADE_DEFAULTS']

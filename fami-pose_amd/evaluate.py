@@ -41,6 +41,12 @@
   launch with one workgroup per video (csrc/track.hip, `fami_pose_track_f32`), one download.  No cfg switch: the live
   config tree has no tracking key.  `write_posetrack_results(..., tracks=)` carries the ids into the JSON; with
   tracks=None it writes what it always wrote.
+* `track_refine` / `EvalAccumulator.track_refine` -- the first consumer of those ids, between `pose_track` and the writer:
+  gaps of at most max_fill frame numbers inside a track are filled by linear interpolation (new rows, new keys where a
+  frame had none), x and y are filtered along the track with confidence-weighted Gaussian weights, box scores can become
+  the track's mean, tracks shorter than min_len leave the lists.  The reference has no tracker and no such step: the rule
+  is this project's (include/fami.h), its defaults starting values, not tuned.  One upload, at most three launches
+  (csrc/track_refine.hip: fill, smooth, score), one download; with every stage off it returns copies and launches nothing.
 * `write_posetrack_results` -- the PoseTrack JSON writer of
   datasets/zoo/posetrack/PoseTrack_Alignment.py:883-1017 (`evaluate` up to the poseval call): COCO->PoseTrack joint
   conversion (datasets/process/structure/keypoints_ord.py:14-73), the annorect structure
@@ -111,6 +117,7 @@ AP_MAX_PRED = 256               # ... one thread per predicted pose of a frame
 AP_MAX_GT = 64                  # ... the annotated poses of a frame are LDS-resident
 AP_MAX_SET = 458752             # ... one label bit per predicted pose of the set in 56 KiB of LDS
 AP_MIN_SCORE = -9999            # eval_helpers.MIN_SCORE: a predicted point without a score
+REFINE_MAX = 16                 # csrc/track_refine.hip: the largest max_fill and smooth_radius (33 neighbour reads per thread)
 MOT_MAX_TRACKS = 256            # csrc/posetrack_mot.hip: annotated tracks of a sequence (the map m is LDS-resident)
 MOT_COUNTS = ('num_misses', 'num_switches', 'num_false_positives', 'num_detections', 'num_objects')
 POSETRACK_JOINT = ['right_ankle', 'right_knee', 'right_hip', 'left_hip', 'left_knee', 'left_ankle', 'right_wrist',
@@ -189,13 +196,19 @@ def _sigmas(who, J, sigmas, holder, dtype):
 def _pose_set(who, preds, boxes, sigmas):
     """The pose set of `pose_nms` / `pose_track`: preds [N,J,3] and boxes [N,6] with J in range -> (preds, boxes, N, J, sigmas
     fp32 [J])."""
+    preds, boxes, N, J = _pose_shapes(who, preds, boxes)
+    return preds, boxes, N, J, _sigmas(who, J, sigmas, 'preds', np.float32)
+
+
+def _pose_shapes(who, preds, boxes):
+    """preds [N,J,3] and boxes [N,6] with J in range -> (preds, boxes, N, J)"""
     preds, boxes = np.asarray(preds), np.asarray(boxes)
     if preds.ndim != 3 or preds.shape[2] != 3 or boxes.ndim != 2 or boxes.shape[1] != 6 or boxes.shape[0] != preds.shape[0]:
         raise ValueError('%s expects preds [N,J,3] and boxes [N,6], got %s and %s' % (who, preds.shape, boxes.shape))
     N, J = preds.shape[:2]
     if not 1 <= J <= NMS_MAX_JOINTS:
         raise ValueError('%s: J = %d joints, supported 1 .. %d' % (who, J, NMS_MAX_JOINTS))
-    return preds, boxes, N, J, _sigmas(who, J, sigmas, 'preds', np.float32)
+    return preds, boxes, N, J
 
 
 def _fp32(who, what, *arrays):
@@ -402,6 +415,16 @@ class EvalAccumulator:
         `write_posetrack_results`.  The accumulator itself is not modified."""
         fmap = self.filenames_map if filenames_map is None else filenames_map
         return pose_track(self.all_preds[:self.idx], self.all_boxes[:self.idx], fmap, **kw)
+
+    def track_refine(self, tracks, filenames_map=None, boxes=None, **kw):
+        """Gap filling, smoothing, rescoring and pruning of the tracks of everything accumulated so far (module-level
+        `track_refine`, same keywords) -> (preds2, boxes2, filenames_map2, tracks2), the arguments of
+        `write_posetrack_results(..., tracks=tracks2)`.  `tracks`: what `pose_track` returned; `filenames_map`: the map it
+        was given (default the accumulator's own); `boxes`: the rescored copy `pose_nms` returned (default all_boxes, the
+        detector's box scores).  The accumulator itself is not modified."""
+        fmap = self.filenames_map if filenames_map is None else filenames_map
+        boxes = self.all_boxes[:self.idx] if boxes is None else boxes
+        return track_refine(self.all_preds[:self.idx], boxes, fmap, tracks, **kw)
 
     def coco_results(self, image_ids, keep=None, boxes=None, category_id=1):
         """Everything accumulated so far as COCO result dicts (module-level `coco_keypoint_results`): image_ids [idx] the
@@ -660,6 +683,201 @@ def pose_track(preds, boxes, filenames_map, oks_thre=0.3, max_gap=3, vis_thre=No
         raise ValueError('pose_track: video %r has more than %d live tracks at once (the limit of one workgroup)'
                          % (videos[int(np.argmax(count < 0))], NMS_MAX_PER_IMAGE))
     return tracks, {video: int(c) for video, c in zip(videos, count)}
+
+
+# ---------------------------------------------------------------------------------------- track refinement
+def posetrack_key_of(video, frame_number, sibling_key):
+    """The key of a frame that had none, after a frame of the same video: the sibling's directory, the number zero-padded to
+    the width of the sibling's stem, the sibling's extension ('.../000001_bonn/00000007.jpg', 9 -> '.../000001_bonn/00000009.jpg')."""
+    head, name = osp.split(str(sibling_key))
+    stem, ext = osp.splitext(name)
+    return osp.join(head, '%0*d%s' % (len(stem), frame_number, ext))
+
+
+def _refine_options(max_fill, fill_conf, smooth_radius, smooth_sigma, conf_thre, min_len):
+    """-> (fill_conf, smooth_sigma as floats, conf_thre as np.float32) or ValueError"""
+    _int_option('track_refine', 'max_fill must be an integer in 0 .. %d', max_fill, 0, REFINE_MAX, REFINE_MAX)
+    _int_option('track_refine', 'smooth_radius must be an integer in 0 .. %d', smooth_radius, 0, REFINE_MAX, REFINE_MAX)
+    _int_option('track_refine', 'min_len must be an integer >= 1', min_len, 1, 2 ** 31 - 1)
+    fill_conf, sigma, thre = float(fill_conf), float(smooth_sigma), float(conf_thre)
+    with np.errstate(over='ignore'):
+        thre32 = np.float32(thre)
+    if not (np.isfinite(fill_conf) and np.isfinite(sigma) and np.isfinite(thre32)):
+        raise ValueError('track_refine: fill_conf, smooth_sigma and conf_thre must be finite (conf_thre in fp32)')
+    if not sigma > 0:
+        raise ValueError('track_refine: smooth_sigma must be > 0, got %r' % sigma)
+    if not 0 <= fill_conf <= 1:
+        raise ValueError('track_refine: fill_conf must be in [0, 1], got %r' % fill_conf)
+    if thre32 < 0:
+        raise ValueError('track_refine: conf_thre must be >= 0 (a weight is a confidence above it), got %r' % thre)
+    return fill_conf, sigma, thre32
+
+
+def _refine_members(filenames_map, N, tracks, frame_of):
+    """The members of all tracks sorted by (video, id, frame) -> (rows, video numbers, ids, frame numbers: int64 [n] each,
+    videos, key_at {(video, frame number): key}).  ValueError for what `_track_tables` refuses, a listed row with a
+    negative id, an id twice in one frame."""
+    index, fseg, fnum, vseg, videos = _track_tables(filenames_map, N, frame_of)
+    frame_of = posetrack_frame_of if frame_of is None else frame_of
+    key_at = {}
+    for key in filenames_map:
+        video, f = frame_of(key)
+        key_at[(video, int(f))] = key
+    frame = np.repeat(np.arange(len(fnum)), np.diff(fseg))              # of every position of index
+    rows, f = index.astype(np.int64), fnum.astype(np.int64)[frame]
+    vid = np.repeat(np.arange(len(videos)), np.diff(vseg))[frame]
+    ids = tracks[rows].astype(np.int64)
+    if (ids < 0).any():
+        r = int(rows[np.argmax(ids < 0)])
+        raise ValueError('track_refine: row %d is listed by an image and has track id %d' % (r, tracks[r]))
+    order = np.lexsort((f, ids, vid))
+    rows, vid, ids, f = rows[order], vid[order], ids[order], f[order]
+    twice = (vid[1:] == vid[:-1]) & (ids[1:] == ids[:-1]) & (f[1:] == f[:-1])
+    if twice.any():
+        i = int(np.argmax(twice))
+        raise ValueError('track_refine: track id %d occurs twice in frame %d of video %r (rows %d and %d)'
+                         % (ids[i], f[i], videos[vid[i]], rows[i], rows[i + 1]))
+    return rows, vid, ids, f, videos, key_at
+
+
+def _refine_tables(mrow, mvid, mid, mf, max_fill, N):
+    """The members sorted by (video, id, frame) -> (fill [G,5]: the end rows a and b, the frame number and the ends' frame
+    numbers of every new row, in (video, id, frame) order -- they get the rows N, N + 1, ...; their video numbers and ids;
+    the members after the fill sorted the same way: rows [Mm], frame numbers [Mm], track of each [Mm], tseg [T+1])."""
+    same = (mvid[1:] == mvid[:-1]) & (mid[1:] == mid[:-1])
+    gap = mf[1:] - mf[:-1] - 1
+    pa = np.flatnonzero(same & (gap >= 1) & (gap <= max_fill))
+    cnt = gap[pa]
+    G = int(cnt.sum())
+    g_f = np.repeat(mf[pa], cnt) + np.arange(G) - np.repeat(np.cumsum(cnt) - cnt, cnt) + 1
+    fill = np.stack([np.repeat(mrow[pa], cnt), np.repeat(mrow[pa + 1], cnt), g_f, np.repeat(mf[pa], cnt),
+                     np.repeat(mf[pa + 1], cnt)], axis=1)
+    g_vid, g_id = np.repeat(mvid[pa], cnt), np.repeat(mid[pa], cnt)
+    avid, aid, af = np.concatenate([mvid, g_vid]), np.concatenate([mid, g_id]), np.concatenate([mf, g_f])
+    order = np.lexsort((af, aid, avid))
+    srow, svid, sid = np.concatenate([mrow, N + np.arange(G)])[order], avid[order], aid[order]
+    start = np.ones(len(srow), dtype=bool)
+    start[1:] = (svid[1:] != svid[:-1]) | (sid[1:] != sid[:-1])
+    return fill, g_vid, g_id, srow, af[order], np.cumsum(start) - 1, np.concatenate([np.flatnonzero(start), [len(srow)]])
+
+
+def track_refine(preds, boxes, filenames_map, tracks, max_fill=2, fill_conf=1.0, smooth_radius=2, smooth_sigma=1.0,
+                 conf_thre=0.0, rescore=False, min_len=1, frame_of=None, key_of=None, device='cuda'):
+    """Refinement of the tracks `pose_track` handed out, between it and the writer (csrc/track_refine.hip; include/fami.h
+    has the rule, which is this project's: the reference has no tracker).  preds [N,J,3], boxes [N,6], filenames_map and
+    frame_of as for `pose_track`; tracks [N] integer, its output.
+    -> (preds2 [N+G,J,3] float32, boxes2 [N+G,6] float64, filenames_map2, tracks2 [N+G] int32): the arguments of
+    `write_posetrack_results(preds2, boxes2, filenames_map2, ..., tracks=tracks2)`.  The first N rows keep their numbers; G
+    rows are new.  The members of a track are the listed rows of one (video, id), by ascending frame number.
+    1. Fill (max_fill >= 1): consecutive members a, b of a track with 1 <= f_b - f_a - 1 <= max_fill get a new row for every
+       frame number between them: x, y and box columns 0 .. 4 are v_a + (v_b - v_a) * t with t = (f - f_a) / (f_b - f_a), the
+       confidences and box column 5 are min(of a, of b) * fill_conf.  New rows are numbered N, N + 1, ... in (video, id,
+       frame) order and appended to the list of their frame's key; a frame without a key gets key_of(video, frame_number,
+       sibling_key) -- default `posetrack_key_of`; the sibling is the key of end a of the first new row of that frame --
+       behind all existing keys, in (video, frame) order.  A longer gap is left alone.
+    2. Smooth (smooth_radius >= 1): x, y of joint j of member i with confidence > conf_thre become the mean of the members
+       within smooth_radius frame numbers whose joint j passes conf_thre too, weighted with exp(-d^2 / (2 smooth_sigma^2))
+       times the confidence; copied bit for bit if no other member contributes.  Always from unsmoothed neighbours;
+       confidences do not change.
+    3. rescore=True: box column 5 of every member becomes the mean score of its track (after the fill).
+    4. Prune (min_len >= 2): tracks with fewer members (after the fill) leave the lists of filenames_map2 (the keys stay)
+       and get tracks2 = -1.
+    Arithmetic: fp64 on the inputs rounded to fp32, one rounding per operation, results rounded to fp32 once; preds2 is the
+    fp32 set, boxes2 holds the input's values in its first N rows except where a stage wrote.  Rows that no image lists
+    are carried through.  With max_fill=0, smooth_radius=0, rescore=False, min_len=1 nothing is rounded and nothing
+    launched: the four results are copies of the inputs (tracks as int32).
+    The defaults are STARTING VALUES, NOT TUNED: no PoseTrack data was available where this was built.
+    One upload, at most three launches (fill, smooth, score), one download.  ValueError before any device work for:
+    everything `pose_track` refuses about shapes, J and the map; tracks not [N] integer (int32 range); a listed row with a
+    negative id; an id twice in one frame of a video; non-finite inputs or options; max_fill or smooth_radius outside
+    0 .. 16; smooth_sigma <= 0; fill_conf outside [0, 1]; conf_thre < 0; min_len < 1; a key_of whose key frame_of does not
+    place at (video, frame_number) or that exists already; a frame with more than 256 rows after the fill.  The inputs are
+    not modified."""
+    who = 'track_refine'
+    preds, boxes, N, J = _pose_shapes(who, preds, boxes)
+    tracks = np.asarray(tracks)
+    if tracks.ndim != 1 or tracks.dtype.kind not in 'iu' or len(tracks) != N:
+        raise ValueError('%s: tracks must be an integer array of %d entries, got %s %s' % (who, N, tracks.dtype, tracks.shape))
+    if N and (tracks.min() < -2 ** 31 or tracks.max() > 2 ** 31 - 1):
+        raise ValueError('%s: track ids must fit int32' % who)
+    fill_conf, sigma, thre32 = _refine_options(max_fill, fill_conf, smooth_radius, smooth_sigma, conf_thre, min_len)
+    k32, b32 = _fp32(who, 'preds and boxes', preds, boxes)
+    mrow, mvid, mid, mf, videos, key_at = _refine_members(filenames_map, N, tracks, frame_of)
+    fmap2 = {key: [int(r) for r in rows] for key, rows in filenames_map.items()}
+    if max_fill == 0 and smooth_radius == 0 and not rescore and min_len == 1:
+        return preds.copy(), boxes.copy(), fmap2, tracks.astype(np.int32)
+    fill, g_vid, g_id, srow, sf, mtrk, tseg = _refine_tables(mrow, mvid, mid, mf, int(max_fill), N)
+    G = len(fill)
+    R = N + G
+    _index_range(who, R, J)
+    _refine_keys(fmap2, key_at, videos, g_vid, fill, N, frame_of, key_of)
+    Mm, T, radius = len(srow), len(tseg) - 1, int(smooth_radius)
+    dev = _hip_device(who, device)
+    preds2, boxes2 = np.concatenate([k32, np.zeros((G, J, 3), np.float32)]), np.concatenate([boxes.astype(np.float64), np.zeros((G, 6))])
+    tracks2 = np.concatenate([tracks.astype(np.int32), g_id.astype(np.int32)])
+    if Mm and (G or radius or rescore):
+        d = np.arange(radius + 1, dtype=np.float64)
+        # the tables, the inputs with room for the new rows behind them, then the outputs, which come back in one download
+        w = _Words(dev, [('gauss', 'f64', radius + 1, np.exp(-(d * d) / (2.0 * sigma * sigma))), ('fill', 'i32', (G, 5), fill),
+                         ('mrow', 'i32', Mm, srow), ('mfr', 'i32', Mm, sf), ('mtrk', 'i32', Mm, mtrk), ('tseg', 'i32', T + 1, tseg),
+                         ('kpts', 'f32', (N, J, 3), k32), ('kpts_new', 'f32', (G, J, 3)), ('boxes', 'f32', (N, 6), b32),
+                         ('boxes_new', 'f32', (G, 6)), ('out', 'f32', (R if radius else 0, J, 3)),
+                         ('score', 'f32', T if rescore else 0), ('flag', 'i32', 3)])
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev).cuda_stream
+            if G:
+                lib().call('fami_track_fill_f32', w.ptr('kpts'), w.ptr('boxes'), w.ptr('fill'), N, J, G, fill_conf,
+                           w.ptr('kpts_new'), w.ptr('boxes_new'), w.ptr('flag'), s)
+            if radius:
+                lib().call('fami_track_smooth_f32', w.ptr('kpts'), w.ptr('mrow'), w.ptr('mfr'), w.ptr('mtrk'), w.ptr('tseg'),
+                           w.ptr('gauss'), R, J, Mm, T, radius, float(thre32), w.ptr('out'), w.ptr('flag') + 4, s)
+            if rescore:
+                lib().call('fami_track_score_f32', w.ptr('boxes'), w.ptr('mrow'), w.ptr('tseg'), R, Mm, T, w.ptr('score'),
+                           w.ptr('flag') + 8, s)
+        out = w.download('boxes_new' if radius else 'kpts_new')     # (without the filter the new poses come back as filled)
+        if out['flag'].any():
+            raise RuntimeError('%s: the %s kernel refused its tables' % (who, ('fill', 'smooth', 'score')[int(np.argmax(out['flag'] != 0))]))
+        boxes2[N:] = out['boxes_new']
+        if radius:
+            preds2[srow] = out['out'][srow]
+        else:
+            preds2[N:] = out['kpts_new']
+        if rescore:
+            boxes2[srow, 5] = out['score'][mtrk]
+    # 4. tracks that are too short leave the lists
+    short = (np.diff(tseg) < min_len)[mtrk]
+    if short.any():
+        dead = set(srow[short].tolist())
+        tracks2[srow[short]] = -1
+        for key, rows in fmap2.items():
+            fmap2[key] = [r for r in rows if r not in dead]
+    return preds2, boxes2, fmap2, tracks2
+
+
+def _refine_keys(fmap2, key_at, videos, g_vid, fill, N, frame_of, key_of):
+    """Appends the new rows N, N + 1, ... (fill [G,5]: end rows, frame number, the ends' frame numbers; g_vid their video
+    numbers) to the lists of `fmap2`; a frame without a key gets one from key_of, behind all existing keys in (video, frame)
+    order.  ValueError for a key that frame_of does not place there or that exists, and for a list over the cap."""
+    frame_of = posetrack_frame_of if frame_of is None else frame_of
+    key_of = posetrack_key_of if key_of is None else key_of
+    made, key_g = {}, []
+    for v, (_, _, f, fa, _) in zip(g_vid.tolist(), fill.tolist()):
+        key = key_at.get((videos[v], f), made.get((v, f)))
+        if key is None:
+            key = made[(v, f)] = key_of(videos[v], f, key_at[(videos[v], fa)])
+            where = frame_of(key)
+            if not isinstance(where, tuple) or len(where) != 2 or where[0] != videos[v] or where[1] != f:
+                raise ValueError('track_refine: key_of(%r, %d, ...) gave %r, which frame_of places at %r'
+                                 % (videos[v], f, key, where))
+            if key in fmap2:
+                raise ValueError('track_refine: key_of(%r, %d, ...) gave %r, which exists already' % (videos[v], f, key))
+        key_g.append(key)
+    for where in sorted(made):
+        fmap2[made[where]] = []
+    for g, key in enumerate(key_g):
+        fmap2[key].append(N + g)
+        if len(fmap2[key]) > NMS_MAX_PER_IMAGE:
+            raise ValueError('track_refine: image %r would list more than %d rows after the fill' % (key, NMS_MAX_PER_IMAGE))
 
 
 # ---------------------------------------------------------------------------------------- PoseTrack JSON writer

@@ -658,6 +658,65 @@ int fami_pose_track_f32(const float* kpts, const float* area, const float* sigma
                         const int* fnum, const int* vseg, int N, int J, int n, int M, int V, double oks_thre,
                         int max_gap, double vis_thre, int use_vis, int* track, int* ntracks, fami_stream_t stream);
 
+/* Track refinement: what follows fami_pose_track_f32 -- short gaps of a track filled, the poses filtered along the track,
+ * the box scores replaced by the track's mean, short tracks pruned (csrc/track_refine.hip; the lists, the keys and the
+ * pruning are host work, fami_pose_amd.evaluate.track_refine).  The reference has no tracker and no such step: THE RULE IS
+ * THIS PROJECT'S, and this text is its contract.  Its defaults (max_fill 2, fill_conf 1, smooth_radius 2, smooth_sigma 1,
+ * conf_thre 0, no rescoring, min_len 1) are STARTING VALUES, NOT TUNED: no PoseTrack data was available where it was built.
+ *
+ * Members.  The members of a track are the rows that the image lists name, with their id (>= 0), grouped by (video, id)
+ *   -- videos in the order of their first key, ids ascending within a video -- and ordered by ascending frame number; an
+ *   id occurs at most once per frame.  Rows that no image lists are carried through untouched.
+ * Arithmetic.  fp64 on the inputs rounded to fp32; every operation is rounded on its own (nothing is contracted into a
+ *   fused multiply-add) in the order written here; a result is rounded to fp32 once.  Nothing transcendental runs on the
+ *   device: the Gaussian table g is built on the host.  fill_conf and g are doubles; conf_thre is an fp32 value and is
+ *   compared with the fp32 confidences as such.
+ * 1. Fill (max_fill >= 1).  For consecutive members a, b of a track with m = f_b - f_a - 1 missing frame numbers and
+ *    1 <= m <= max_fill, every f in f_a + 1 .. f_b - 1 gets a new row: with t = (f - f_a) / (f_b - f_a), x and y of every
+ *    joint and box columns 0 .. 4 are v_a + (v_b - v_a) * t; the confidence of joint j is min(c_a, c_b) * fill_conf and box
+ *    column 5 is min(s_a, s_b) * fill_conf (min: a's value unless b's is smaller); the id is the track's.  The new rows get
+ *    the numbers N, N + 1, ... in (video, id, frame) order.  A gap longer than max_fill is left alone.
+ *    (The host refuses a fill that leaves a frame with more than 256 rows: the result stays a map fami_pose_track_f32's
+ *    tables accept.)
+ * 2. Smooth (smooth_radius >= 1; on the filled set).  For member i and joint j whose own confidence is > conf_thre: over the
+ *    members k of the same track with |f_k - f_i| <= radius, in ascending frame order, those with c_kj > conf_thre
+ *    contribute w = g[|f_k - f_i|] * c_kj:  sw += w; sx += w * x_k; sy += w * y_k;  then x' = sx / sw, y' = sy / sw.  If no
+ *    member other than i contributes, or the own confidence fails the threshold, x and y are copied bit for bit.
+ *    Confidences are never changed.  g[d] = exp(-d * d / (2 sigma^2)), d = 0 .. radius.  The output is a second array:
+ *    neighbours always read unsmoothed values.  conf_thre >= 0, so every weight is positive and sw > 0.
+ * 3. Rescore.  Box column 5 of every member becomes the mean of the scores its track has after the fill and before the
+ *    rescoring: summed in frame order, divided by the count.
+ * 4. Prune (min_len >= 2).  A track with fewer than min_len members after the fill is dropped: its rows leave the image
+ *    lists (the images stay, possibly with an empty list) and hold id -1, as every row that no image lists.
+ *
+ * All pointers are DEVICE memory, 4-byte aligned (gauss: 8).  R = N + G rows in all.
+ * fami_track_fill_f32: kpts [N,J,3], boxes [N,6]; fill [G,5] int: the end rows a and b (in [0, N)), the frame number f of
+ *   the new row, and f_a, f_b with f_a < f < f_b -> kpts_new [G,J,3], boxes_new [G,6].  One thread per (new row, value).
+ * fami_track_smooth_f32: kpts [R,J,3] (the new rows behind the first N); the members of all tracks as one list sorted by
+ *   (track, frame): mrow [Mm] the row, mfr [Mm] the frame number, mtrk [Mm] the track of each, tseg [T+1] the members of
+ *   track t are tseg[t] .. tseg[t+1); gauss [radius+1] fp64; radius in 1 .. 16 -> out [R,J,3]: x', y' and the confidence of
+ *   every MEMBER row; other rows are not written.  out must not be kpts.  One thread per (member, joint); the window is
+ *   found by walking at most `radius` members to either side (frame numbers ascend strictly within a track), so a thread
+ *   makes at most 33 neighbour reads of 12 bytes.
+ * fami_track_score_f32: boxes [R,6], mrow and tseg as above -> score [T], the mean of column 5 over each track's members.
+ *   One thread per track, sequential over its segment.
+ * No atomics, no workspace, no host read-back, every output word has one writer: bitwise reproducible.
+ * Each returns -1 before any launch for a null or misaligned pointer, J outside 1 .. 32, a count < 1 (launch nothing for
+ * an empty stage), R * J * 3 (fill: (N + G) * J * 3) > 2^31 - 1, T > Mm or Mm > R, fill_conf outside [0, 1], radius outside
+ * 1 .. 16, a NaN threshold.  The tables are in device memory and are not checked here (evaluate.track_refine builds them):
+ * every index read from one is checked against the array it addresses before use -- an end row outside [0, N) or a frame
+ * number outside its gap (fill); a track outside [0, T), a segment that is no sub-range of [0, Mm] or does not hold its
+ * member, a row outside [0, R) anywhere in the window (smooth); an empty or out-of-range segment, a row outside [0, R)
+ * (score).  A thread whose check fails writes 1 to *flag (the caller zeroes it; every writer writes the same value) and
+ * NOTHING else: nothing is read or written through such an index, and the other threads' outputs are what they would be. */
+int fami_track_fill_f32(const float* kpts, const float* boxes, const int* fill, int N, int J, int G, double fill_conf,
+                        float* kpts_new, float* boxes_new, int* flag, fami_stream_t stream);
+int fami_track_smooth_f32(const float* kpts, const int* mrow, const int* mfr, const int* mtrk, const int* tseg,
+                          const double* gauss, int R, int J, int Mm, int T, int radius, float conf_thre, float* out,
+                          int* flag, fami_stream_t stream);
+int fami_track_score_f32(const float* boxes, const int* mrow, const int* tseg, int R, int Mm, int T, float* score,
+                         int* flag, fami_stream_t stream);
+
 /* PoseTrack AP, the pose half of the evaluation tool the reference vendors (poseval/py/eval_helpers.py:322-367
  * removeIgnoredPoints, :453-668 assignGTmulti, :192-228 computeRPC / VOCap; evaluateAP.py:8-47 computeMetrics;
  * csrc/posetrack_ap.hip).  All pointers are DEVICE memory; fp64 arrays 8-byte, int arrays 4-byte aligned.  15 joints.
